@@ -471,14 +471,17 @@ __global__ __launch_bounds__(256) void k_train_wgrad(const float* __restrict__ d
             for (int u = 0; u < NK; ++u) multiply(u, u);
         }
     };
-    for (;;) {
-        if (k0 + kWgradRows <= rows) run(std::true_type{});
-        else run(std::false_type{});
-        k0 += gridDim.y * kWgradRows;      // more than 64 chunks (batches beyond 12,288 rows): the workgroup goes on with chunk + 64, ... into the same accumulators
-        if (k0 >= rows) break;
-        k1 = min(rows, k0 + kWgradRows);
+    // more than 64 chunks (batches beyond 12,288 rows): the workgroup goes on with chunk + 64, ... into the same accumulators.  Its full chunks come first and a ragged
+    // one - only ever the job's last chunk - after the loop: one loop body holding both paths kept their registers live together (268 instead of 236 for MT = 4)
+    while (k0 + kWgradRows <= rows) {
+        run(std::true_type{});
+        k0 += gridDim.y * kWgradRows;
         ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(dy + (size_t)k0 * M), 0, 0x7fffffff, 0x00020000);
         rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(x + (size_t)k0 * N), 0, 0x7fffffff, 0x00020000);
+    }
+    if (k0 < rows) {
+        k1 = rows;
+        run(std::false_type{});
     }
     // C fragment: lane (g, r), element v = tile row 4 g + v, tile column r  ->  dW row m0 + MT (4 g + v) + t, columns n0 + 2 r + {0, 1}
     float* o = part + (size_t)blockIdx.y * M * N;

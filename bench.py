@@ -13,7 +13,12 @@ that figure is flat in N by construction; the shape in whi
 - every rank its own 256 clips, global clip indices rank * 256 ... - is measured beside it and reported
 as `weak_scaling`.
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints the headline (`value`, `ms_per_step` = one timed step).  --dump-outputs DIR
+writes what the last timed step returned (latents, SMPL-X poses, root translations) as DIR/<name>.npy - the inputs are seeded, so two
+builds can be compared output for output.  --full adds every side measurement and check: the roofline's own kernel timing, single-clip
+latency, decode and its attention, the saturating point, the parity / fp16 / DDIM-50 modes, diffusion-only, the audio front-end, the
+train_gesture step, the CPU and PyTorch-eager baselines and, at N > 1, the weak-scaling companion and the edit batch.
 N > 1: one process per GPU.  Under torch.distributed.run (RANK / WORLD_SIZE in the environment) this process IS a rank;
 typed directly, it starts the N ranks itself as children (amuse_amd/launch.py - before anything touches the GPU) and
 passes rank 0's line through.  Prints ONE JSON line on rank 0.
@@ -357,6 +362,32 @@ def edit_batch_extra(eng, dev, rank, world, red_dev, share_gpu, precision="bf16"
         aeng.close()
 
 
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(out, B, dirname, rank, world):
+    """--dump-outputs: the arrays the timed path's last step handed back (this rank's B clips: latents [B, 128], poses [B, 300, 55, 3], trans [B, 300, 3])
+    as DIR/<name>.npy in float32 (DIR/<name>.rank<r>.npy per rank at N > 1).  Past 64 MB in all (more than 332 clips) a fixed sample of clips stands in for
+    the whole: the same clips for the same --clips and --gpus, in clip order."""
+    import numpy as np
+    import torch
+    d = Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    if B == 0 or not out:
+        return
+    arrs = {k: v[:B] for k, v in out.items()}
+    clip_bytes = sum(v[0].numel() * 4 for v in out.values())
+    keep = max(1, DUMP_BYTES_MAX // world // clip_bytes)
+    idx = None
+    if B > keep:
+        idx = torch.from_numpy(np.sort(np.random.default_rng(0).choice(B, keep, replace=False))).to(next(iter(out.values())).device)
+    suffix = f".rank{rank}" if world > 1 else ""
+    for k, v in arrs.items():
+        if idx is not None:
+            v = v.index_select(0, idx)
+        np.save(d / f"{k}{suffix}.npy", v.float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -369,12 +400,18 @@ def main():
                     help="sample: BASELINE configs[2] (the headline metric); train: configs[3] train_gesture data-parallel step")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-audio", action="store_true", help="skip the audio front-end side measurement")
-    ap.add_argument("--no-extras", action="store_true", help="headline + roofline only (profiling runs)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: headline + roofline only (profiling runs)")
     ap.add_argument("--train-batch", dest="train_batch", type=int, default=32, help="--config train: clips per GPU and iteration (BASELINE config 4: 32)")
     ap.add_argument("--no-torch-baseline", dest="no_torch_baseline", action="store_true", help="skip the PyTorch-ROCm eager restatement of the job (torch_eager_baseline, ~3 s)")
     ap.add_argument("--no-graph", dest="no_graph", action="store_true", help="--config train: the eager step instead of the two captured HIP graphs (A/B)")
-    ap.add_argument("--edit-batch", action="store_true", help="with --no-extras: still run the edit_batch extra (BASELINE config 5's shape, every rank takes part)")
+    ap.add_argument("--edit-batch", action="store_true", help="run the edit_batch extra (BASELINE config 5's shape, every rank takes part) without --full, or with --full --no-extras")
+    ap.add_argument("--full", action="store_true", help="every side measurement and check beside the headline (see the module docstring; --no-extras, --no-audio, "
+                                                        "--no-cpu-baseline and --no-torch-baseline trim it); off: set-up, warm-up, the timed steps and the headline only")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="after the timed steps: what the last step computed as DIR/<name>.npy, float32, at most 64 MB in all (--config sample)")
     args = ap.parse_args()
+    if args.dump_outputs and args.config != "sample":
+        raise SystemExit("--dump-outputs: the sample configuration only")
     from amuse_amd import launch
     if args.gpus > 1 and not launch.launched_by_torchrun():
         # typed as `python bench.py --gpus N`: this process becomes the launcher of N ranks and never initialises the GPU
@@ -433,11 +470,11 @@ def main():
         return eng.diffusion_backward(c, e, s, args.precision, seed=2024, clip_index0=clip_index0, out=out)
 
     def step_strong():   # the product's sharding path: tiling from the job's total, aligned contiguous shard, global clip index
-        shard.sample_sharded(sample_fn, con, emo, sty, rank, world, set_clips_per_group=eng.set_clips_per_group,
-                             set_decode_path=eng.set_decode_path)
+        return shard.sample_sharded(sample_fn, con, emo, sty, rank, world, set_clips_per_group=eng.set_clips_per_group,
+                                    set_decode_path=eng.set_decode_path)
 
     step = step_strong   # the timed workload at every N: BASELINE config 3 - `total` clips in all, this rank's contiguous shard
-    if world > 1:
+    if world > 1 and args.full:
         # weak-scaling companion: this rank's own `total` clips (another draw per rank), global clip indices rank * total ...; the
         # same code path as a whole single-GPU job (tiling and decode kernel chosen from the job's clip count)
         con_w, emo_w, sty_w = (torch.randn(total, 256, generator=torch.Generator().manual_seed(99 + rank)).to(dev) for _ in range(3))
@@ -456,18 +493,21 @@ def main():
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     barrier()
     elapsed = time.perf_counter() - t0
     if world > 1:
         t = torch.tensor([elapsed], device=red_dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    assert B == 0 or bool(torch.isfinite(out["poses"][:B]).all())
+    if args.dump_outputs and args.steps > 0:
+        dump_outputs(last, B, args.dump_outputs, rank, world)   # before the extras: they reuse the output buffers
+    if args.full:
+        assert B == 0 or bool(torch.isfinite(out["poses"][:B]).all())
 
     # ---- weak-scaling companion, N > 1 only: every rank its own `total` clips (the shape in which the path scales)
     weak = None
-    if world > 1:
+    if world > 1 and args.full:
         step_weak()
         barrier()
         t1 = time.perf_counter()
@@ -485,7 +525,7 @@ def main():
 
     # ---- BASELINE config 5 beside the headline, at every N (all ranks take part: audio shares, one all-gather, job ranges)
     edit_batch = None
-    if (not args.no_extras or args.edit_batch) and not args.no_audio and args.precision in ("bf16", "fp16", "fp32x"):
+    if ((args.full and not args.no_extras) or args.edit_batch) and not args.no_audio and args.precision in ("bf16", "fp16", "fp32x"):
         try:
             edit_batch = edit_batch_extra(eng, dev, rank, world, red_dev, share_gpu, args.precision)
         except Exception as e:          # the headline must not depend on an extra.  A rank that fails on ITS share agrees with the others before the exchange
@@ -496,28 +536,22 @@ def main():
     # (HipEngine launches on torch's current stream, which is the stream these events are recorded on)
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     kt = []
-    eng.set_clips_per_group(g_job)
-    for _ in range(max(3, min(args.steps, 10))):
-        if B == 0:
-            break
-        ev0.record()
-        eng.sample(con[lo:hi], emo[lo:hi], sty[lo:hi], args.precision, seed=2024, clip_index0=lo)
-        ev1.record()
-        ev1.synchronize()
-        kt.append(ev0.elapsed_time(ev1) * 1e-3)
-    eng.set_clips_per_group(0)
+    if args.full:
+        eng.set_clips_per_group(g_job)
+        for _ in range(max(3, min(args.steps, 10))):
+            if B == 0:
+                break
+            ev0.record()
+            eng.sample(con[lo:hi], emo[lo:hi], sty[lo:hi], args.precision, seed=2024, clip_index0=lo)
+            ev1.record()
+            ev1.synchronize()
+            kt.append(ev0.elapsed_time(ev1) * 1e-3)
+        eng.set_clips_per_group(0)
     k_avg = sum(kt) / len(kt) if kt else float("nan")
 
     line = None
     if rank == 0:
         value = total * 300 * args.steps / elapsed
-        flop = B * args.T * FLOP_PER_CLIP_STEP
-        achieved = flop / k_avg / 1e12
-        peak = MFMA_PEAK_TFLOPS[args.precision]
-        traffic, traffic_src = pmc_traffic_bytes(B, args.T, args.precision)
-        us_step = k_avg / args.T * 1e6
-        clk_ghz = getattr(torch.cuda.get_device_properties(dev), "clock_rate", 2.4e6) / 1e6   # kHz -> GHz (2.4 if torch does not say)
-        stream_floor_us = STREAM_MB_PER_STEP[args.precision] * 1e6 / CU_LOAD_BYTES_PER_CLK / (clk_ghz * 1e9) * 1e6
         line = {
             "metric": "SMPL-X frames/sec (10 s clip, 1000-step DDPM)", "value": round(value, 1), "unit": "frames/s",
             "n_gpus": world, "world_size_seen": dist.get_world_size() if world > 1 else 1, "steps": args.steps, "warmup": args.warmup,
@@ -534,6 +568,16 @@ def main():
                                                "reference tree's own GaussianDiffusion / SpacedDiffusion (tests/test_gpu_pins.py, tests/golden/sched_ref.npz); "
                                                "unpinned conventions: DDIM last-step alpha_bar_prev = abar[0], un-clipped eps_hat in the DDIM direction term, "
                                                "fp32 cumprod (DESIGN.md section 2)"},
+        }
+    if rank == 0 and args.full:
+        peak = MFMA_PEAK_TFLOPS[args.precision]
+        clk_ghz = getattr(torch.cuda.get_device_properties(dev), "clock_rate", 2.4e6) / 1e6   # kHz -> GHz (2.4 if torch does not say)
+        flop = B * args.T * FLOP_PER_CLIP_STEP
+        achieved = flop / k_avg / 1e12
+        traffic, traffic_src = pmc_traffic_bytes(B, args.T, args.precision)
+        us_step = k_avg / args.T * 1e6
+        stream_floor_us = STREAM_MB_PER_STEP[args.precision] * 1e6 / CU_LOAD_BYTES_PER_CLK / (clk_ghz * 1e9) * 1e6
+        line.update({
             "roofline": {"bound": "chain+l2_stream", "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s",
                          "frac": round(achieved / peak, 5), "traffic": traffic, "traffic_source": traffic_src,
                          "kernel": KERNEL_NAME[args.precision] + " (persistent T-step denoising loop)",
@@ -546,12 +590,12 @@ def main():
                                  f"({STREAM_MB_PER_STEP[args.precision]:.2f} MB per CU and step at {CU_LOAD_BYTES_PER_CLK:.0f} B/clk = "
                                  f"{stream_floor_us:.1f} us at the {clk_ghz:.2f} GHz this device reports). The kernel is bound by the "
                                  f"serial per-step dependency chain + that stream, not by HBM or MFMA issue (DESIGN.md 4.1, 4.1b, 5)"},
-        }
+        })
         if weak is not None:
             line["weak_scaling"] = weak
-        if edit_batch is not None:
-            line["edit_batch"] = edit_batch
-    if rank == 0 and not args.no_extras:
+    if rank == 0 and edit_batch is not None:
+        line["edit_batch"] = edit_batch
+    if rank == 0 and args.full and not args.no_extras:
         # single-clip latency (BASELINE configs[1]): B = 1, same sampler, 5 warm-ups, 50 HIP-event-timed repeats
         c1, e1, s1 = con[:1].contiguous(), emo[:1].contiguous(), sty[:1].contiguous()
         o1 = {"latents": torch.empty(1, 128, device=dev), "poses": torch.empty(1, 300, 55, 3, device=dev),
@@ -771,7 +815,7 @@ def main():
                 line["torch_eager_baseline"] = dict(tb, what=WHAT, speedup_of_value=round(line["value"] / tb["frames_per_s"], 1))
             except Exception as e:   # the headline must not depend on the extra
                 line["torch_eager_baseline"] = {"error": f"{type(e).__name__}: {e}"}
-    if line is not None:
+    if line is not None and args.full:
         # every headline carries its parity-grade twin at the TOP level (the driver's parsed block keeps top-level scalars and `config`):
         # `value` is the configuration BASELINE.json names (bf16 operands); the mode that meets the north star's "< 1e-4" is fp32x
         pm, att = line.get("parity_mode", {}), line.get("decode", {}).get("attention", {})

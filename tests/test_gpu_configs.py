@@ -222,7 +222,7 @@ def test_bench_line_with_two_ranks_sharing_the_gpu():
     from conftest import REPO
     env = dict(os.environ, AMUSE_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, str(REPO / "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--T", "20", "--clips", "64",
-                        "--no-extras"], env=env, capture_output=True, text=True, timeout=900)
+                        "--full", "--no-extras"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]

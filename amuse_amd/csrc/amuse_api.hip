@@ -483,6 +483,18 @@ int ensure_vae_ws(amuse_ctx* c, int chunk) {
     return 0;
 }
 
+// train-mode sampling (amuse_set_sample_dropout) of one amuse_sample / amuse_denoise_step / amuse_profile_sample call: refused where no kernel draws
+// the masks (AMUSE_ARCH_ENC in fp32, bf16 and fp16 only), so that dropout is never silently dropped
+int sample_dropout(const amuse_ctx* c, int precision, SampleArgs& a) {
+    if (c->drop_thr == 0) return 0;
+    if (c->arch != AMUSE_ARCH_ENC)
+        return fail(AMUSE_ESTATE, "train-mode sampling (amuse_set_sample_dropout p > 0) exists for AMUSE_ARCH_ENC only, this context is arch %d", c->arch);
+    if (precision == AMUSE_PREC_F32X)
+        return fail(AMUSE_ESTATE, "train-mode sampling (amuse_set_sample_dropout p > 0) has no fp32x kernel: use fp32, bf16 or fp16");
+    a.drop_thr = c->drop_thr; a.drop_scale = c->drop_scale; a.drop_seed = c->drop_seed;
+    return 0;
+}
+
 int check_common(amuse_ctx* c, const float* con, int B, int precision) {
     if (!c) return fail(AMUSE_EINVAL, "ctx is NULL");
     if (!con) return fail(AMUSE_EINVAL, "con is NULL (the content embedding is mandatory, denoiser.py:153-157)");
@@ -690,6 +702,15 @@ int amuse_set_clips_per_group(amuse_ctx* c, int g) {
     return 0;
 }
 
+int amuse_set_sample_dropout(amuse_ctx* c, float p, uint64_t seed) {
+    if (!(p >= 0.f) || p >= 1.f) return fail(AMUSE_EINVAL, "dropout probability %g outside [0, 1)", (double)p);
+    if (!c) return fail(AMUSE_EINVAL, "ctx is NULL");
+    c->drop_thr = (uint32_t)(p * 16777216.0f);   // k_train.hip drop_args
+    c->drop_scale = 1.0f / (1.0f - p);
+    c->drop_seed = seed;
+    return 0;
+}
+
 int amuse_set_decode_path(amuse_ctx* c, int path) {
     if (!c) return fail(AMUSE_EINVAL, "ctx is NULL");
     if (path != AMUSE_DECODE_AUTO && path != AMUSE_DECODE_STAGED && path != AMUSE_DECODE_FUSED && path != AMUSE_DECODE_CLIP)
@@ -764,11 +785,12 @@ int amuse_sample(amuse_ctx* c, const float* con, const float* emo, const float* 
     if (c->T < 1) return fail(AMUSE_ESTATE, "amuse_set_schedule has not been called");
     if (!latents_out) return fail(AMUSE_EINVAL, "latents_out is NULL");
     hipStream_t st = (hipStream_t)stream;
+    SampleArgs a{};
+    if (int e = sample_dropout(c, precision, a)) return e;
     if (c->arch != AMUSE_ARCH_ENC)
         return variant_sample(c, con, emo, sty, B, precision, seed, clip_index0, x_init, step_noise, latents_out, traj_out, st);
     int S = 0;
     if (int e = cond_tokens(c, con, emo, sty, B, &S, st)) return e;
-    SampleArgs a{};
     set_stream(c, a, precision);
     a.pvec = c->den_pvec; a.time_tok = c->d_time_tok; a.cond_tok = c->cond_tok; a.pe0 = c->den_pe;
     a.coef = c->d_coef; a.x_init = x_init; a.step_noise = step_noise;
@@ -786,11 +808,12 @@ int amuse_profile_sample(amuse_ctx* c, const float* con, const float* emo, const
     if (!stamps_out || prof_step < 0 || prof_step >= c->T) return fail(AMUSE_EINVAL, "bad stamps_out / prof_step");
     if (c->arch != AMUSE_ARCH_ENC) return fail(AMUSE_ESTATE, "phase stamps exist for the AMUSE_ARCH_ENC sampling kernels only");
     hipStream_t st = (hipStream_t)stream;
+    SampleArgs a{};
+    if (int e = sample_dropout(c, precision, a)) return e;
     int S = 0;
     if (int e = cond_tokens(c, con, emo, sty, B, &S, st)) return e;
     if (int e = ensure(&c->lat_tmp, &c->lat_cap, (size_t)B * kD)) return e;
     HIP_TRY(hipMemsetAsync(stamps_out, 0, 4 * kProfStamps * sizeof(unsigned long long), st));
-    SampleArgs a{};
     set_stream(c, a, precision);
     a.pvec = c->den_pvec; a.time_tok = c->d_time_tok; a.cond_tok = c->cond_tok; a.pe0 = c->den_pe;
     a.coef = c->d_coef; a.latents_out = c->lat_tmp;
@@ -807,6 +830,8 @@ int amuse_denoise_step(amuse_ctx* c, const float* x_t, int timestep, const float
     if (!x_t || !eps_out) return fail(AMUSE_EINVAL, "x_t / eps_out is NULL");
     if (timestep < 0) return fail(AMUSE_EINVAL, "negative timestep");
     hipStream_t st = (hipStream_t)stream;
+    SampleArgs a{};
+    if (int e = sample_dropout(c, precision, a)) return e;
     if (c->arch != AMUSE_ARCH_ENC) return variant_denoise(c, x_t, &timestep, false, con, emo, sty, nullptr, B, precision, eps_out, tap_out, st);
     HIP_TRY(hipMemcpyAsync(c->d_ts1, &timestep, sizeof(int), hipMemcpyHostToDevice, st));
     HIP_TRY(hipStreamSynchronize(st));  // `timestep` lives on this call's stack
@@ -814,7 +839,6 @@ int amuse_denoise_step(amuse_ctx* c, const float* x_t, int timestep, const float
                                c->d_tt1, st));
     int S = 0;
     if (int e = cond_tokens(c, con, emo, sty, B, &S, st)) return e;
-    SampleArgs a{};
     set_stream(c, a, precision);
     a.pvec = c->den_pvec; a.time_tok = c->d_tt1; a.cond_tok = c->cond_tok; a.pe0 = c->den_pe;
     a.coef = c->d_coef1; a.x_init = x_t; a.step_noise = nullptr;
@@ -1151,6 +1175,8 @@ int amuse_denoise_step_pose(amuse_ctx* c, const float* x_t, int timestep, const 
     if (!(c->arch & 2)) return fail(AMUSE_ESTATE, "amuse_denoise_step_pose needs a pose-space variant (AMUSE_ARCH_ENC_POSE / _DEC_POSE)");
     if (!x_t || !eps_out) return fail(AMUSE_EINVAL, "x_t / eps_out is NULL");
     if (timestep < 0) return fail(AMUSE_EINVAL, "negative timestep");
+    SampleArgs a{};
+    if (int e = sample_dropout(c, precision, a)) return e;   // (always refused: a pose-space variant)
     return variant_denoise(c, x_t, &timestep, false, con, emo, sty, lengths, B, precision, eps_out, nullptr, (hipStream_t)stream);
 }
 

@@ -532,6 +532,32 @@ __device__ __forceinline__ void exchange_sum(f32x4 (&part)[kTiles], f32x4* exch,
 }
 constexpr int kExchBytes = 2 * 4 * kTiles * 64 * 16;  // 64 KiB
 
+// ---- Philox4x32-10 (counter-based normals below, train-mode sampling dropout masks)
+__device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int i = 0; i < 10; ++i) {
+        const uint32_t hi0 = __umulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
+        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
+        const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
+        c[0] = n0; c[1] = lo1; c[2] = n2; c[3] = lo0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+}
+// ---- train-mode sampling dropout (amuse_hip.h amuse_set_sample_dropout): keep bits of elements 4 e4 .. 4 e4 + 3 of dropout site
+// ls = 4 layer + site; element e uses draw e % 4 of Philox4x32-10(key = seed, counter = (clip, step, ls << 16 | e / 4, 2 + epoch)),
+// keep <=> draw >> 8 >= thr (k_train.hip drop_scale4).  Bit m of the result = element 4 e4 + m kept.
+__device__ __forceinline__ uint32_t sdrop_bits4(uint64_t seed, uint32_t clip, uint32_t step, uint32_t ls, uint32_t e4, uint32_t epoch2,
+                                                uint32_t thr) {
+    uint32_t c[4] = {clip, step, (ls << 16) | e4, epoch2};
+    philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+    return ((c[0] >> 8) >= thr ? 1u : 0u) | ((c[1] >> 8) >= thr ? 2u : 0u) | ((c[2] >> 8) >= thr ? 4u : 0u) | ((c[3] >> 8) >= thr ? 8u : 0u);
+}
+// v . mask / (1 - p) for the four elements whose keep bits are bits 0..3 of `bits`
+__device__ __forceinline__ f32x4 sdrop_apply4(f32x4 v, uint32_t bits, float scale) {
+    return f32x4{(bits & 1u) ? v[0] * scale : 0.f, (bits & 2u) ? v[1] * scale : 0.f, (bits & 4u) ? v[2] * scale : 0.f,
+                 (bits & 8u) ? v[3] * scale : 0.f};
+}
+
 // ------------------------------------------------------------------------------------------------
 // Split-K combine as reduce-scatter + (LayerNorm) + all-gather.  exchange_sum makes every wave read all
 // partials and then repeat the same residual + LayerNorm on the full [16 x 128] tile - 4x redundant VALU and
@@ -546,10 +572,10 @@ constexpr int kExchBytes = 2 * 4 * kTiles * 64 * 16;  // 64 KiB
 constexpr int kCombA = 4 * kTiles * 64;                 // f32x4 elements
 constexpr int kCombBytes = kCombA * 16 + 4 * 16 * 8 + kTiles * 64 * 16;   // 41,472 B
 
-template <int W, bool DO_LN, bool FAST, int NC, int R, int IPH>
+template <int W, bool DO_LN, bool FAST, int NC, int R, int IPH, bool DRP>
 __device__ __forceinline__ void combine_rs_impl(f32x4 (&part)[kTiles], f32x4 (&x)[kTiles], bool residual,
                                                 const float* bias, const float* gamma, const float* beta,
-                                                char* lds, int lane, WRing<R>* rg) {
+                                                char* lds, int lane, WRing<R>* rg, uint32_t dbits, float dscale) {
     f32x4* A = reinterpret_cast<f32x4*>(lds);
     float2* stats = reinterpret_cast<float2*>(lds + kCombA * 16);
     f32x4* Bq = reinterpret_cast<f32x4*>(lds + kCombA * 16 + 4 * 16 * 8);
@@ -582,7 +608,9 @@ __device__ __forceinline__ void combine_rs_impl(f32x4 (&part)[kTiles], f32x4 (&x
         for (int i = 0; i < 2; ++i) {
             p[W][i] = part[T0 + i];
             const f32x4 sum = ((p[0][i] + p[1][i]) + p[2][i]) + p[3][i];
-            y[i] = residual ? x[T0 + i] + (sum + bi[i]) : sum + bi[i];
+            f32x4 br = sum + bi[i];
+            if constexpr (DRP) br = sdrop_apply4(br, dbits >> (4 * i), dscale);   // dropout1 / dropout2 of train-mode sampling
+            y[i] = residual ? x[T0 + i] + br : br;
         }
     }
     if constexpr (DO_LN) {
@@ -626,30 +654,21 @@ __device__ __forceinline__ void combine_rs_impl(f32x4 (&part)[kTiles], f32x4 (&x
     for (int t = 0; t < kTiles; ++t)
         if (t != T0 && t != T0 + 1) x[t] = Bq[t * 64 + lane];
 }
-// x <- [LayerNorm]( [x +] (sum over waves of part) + bias );  NI weight-stream units issued in four chunks
-template <bool DO_LN, bool FAST, int NI = 0, int R = 1, int IPH = 0>
+// x <- [LayerNorm]( [x +] (sum over waves of part) + bias );  NI weight-stream units issued in four chunks.
+// DRP: (sum + bias) of this wave's tiles 2 wave + i is multiplied by sdrop_apply4(., dbits >> 4 i, dscale) first
+template <bool DO_LN, bool FAST, int NI = 0, int R = 1, int IPH = 0, bool DRP = false>
 __device__ __forceinline__ void combine_rs(f32x4 (&part)[kTiles], f32x4 (&x)[kTiles], bool residual, const float* bias,
                                            const float* gamma, const float* beta, char* lds, int wave, int lane,
-                                           WRing<R>* rg = nullptr) {
+                                           WRing<R>* rg = nullptr, uint32_t dbits = 0, float dscale = 1.f) {
     static_assert(NI % 4 == 0, "issue count is split in four chunks");
     constexpr int NC = NI / 4;
-    if (wave == 0) combine_rs_impl<0, DO_LN, FAST, NC, R, IPH>(part, x, residual, bias, gamma, beta, lds, lane, rg);
-    else if (wave == 1) combine_rs_impl<1, DO_LN, FAST, NC, R, IPH>(part, x, residual, bias, gamma, beta, lds, lane, rg);
-    else if (wave == 2) combine_rs_impl<2, DO_LN, FAST, NC, R, IPH>(part, x, residual, bias, gamma, beta, lds, lane, rg);
-    else combine_rs_impl<3, DO_LN, FAST, NC, R, IPH>(part, x, residual, bias, gamma, beta, lds, lane, rg);
+    if (wave == 0) combine_rs_impl<0, DO_LN, FAST, NC, R, IPH, DRP>(part, x, residual, bias, gamma, beta, lds, lane, rg, dbits, dscale);
+    else if (wave == 1) combine_rs_impl<1, DO_LN, FAST, NC, R, IPH, DRP>(part, x, residual, bias, gamma, beta, lds, lane, rg, dbits, dscale);
+    else if (wave == 2) combine_rs_impl<2, DO_LN, FAST, NC, R, IPH, DRP>(part, x, residual, bias, gamma, beta, lds, lane, rg, dbits, dscale);
+    else combine_rs_impl<3, DO_LN, FAST, NC, R, IPH, DRP>(part, x, residual, bias, gamma, beta, lds, lane, rg, dbits, dscale);
 }
 
 // ---- counter-based normals: Philox4x32-10, key = seed, counter = (clip, step, feature/4, stream)
-__device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int i = 0; i < 10; ++i) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
-        const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
-        c[0] = n0; c[1] = lo1; c[2] = n2; c[3] = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-}
 __device__ __forceinline__ f32x4 counter_normal4(uint64_t seed, uint64_t clip, uint32_t step, uint32_t q, uint32_t stream) {
     uint32_t c[4] = {(uint32_t)clip, step, q, stream};
     philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));

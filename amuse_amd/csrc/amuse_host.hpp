@@ -331,6 +331,10 @@ struct amuse_ctx {
     int last_plan[4] = {0, 0, 0, 0};   // amuse_debug_last_plan: clips per tile / decode / encode / step path the last call of each kind actually took
     float* decode_tap = nullptr;       // amuse_debug_set_decode_tap
     int ablate = 0;                    // amuse_debug_set_ablation
+    // train-mode sampling (amuse_set_sample_dropout): drop_thr = p 2^24, 0 = eval
+    uint32_t drop_thr = 0;
+    float drop_scale = 1.f;
+    uint64_t drop_seed = 0;
     // denoiser
     uint4* den_w[3] = {nullptr, nullptr, nullptr};   // 4-wave kernel streams: fp32 | bf16 | split-fp16 (fp32x)
     uint32_t den_wave_units[3] = {0, 0, 0};

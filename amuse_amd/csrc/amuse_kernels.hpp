@@ -22,7 +22,8 @@ struct DeviceOnce {
 };
 
 // ---------------------------------------------------------------- sampling loop (k_sampler.hip)
-struct SampleArgs {
+// The sampling kernels' arguments (the layout every pre-dropout kernel takes by value: kept as is, so their code does not change)
+struct SampleKernelArgs {
     const uint4* wstream;     // packed denoiser weights: [4 waves][wave_units + kRing][64] x 16 B (head replicated at the tail)
     uint32_t wave_units;      // 1 KiB units per wave for one pass over the network
     uint32_t wave_units_a, wave_units_b;  // k_sample8: per-step units of a group-A / group-B wave (streams laid out
@@ -45,6 +46,15 @@ struct SampleArgs {
     int no_update;            // 1: teacher-forced (no scheduler update)
     unsigned long long* prof_out;  // [4 waves][kProfStamps] s_memtime stamps of step prof_step, or null
     int prof_step;
+};
+// One sampling launch as the host describes it: the kernel arguments + train-mode sampling (amuse_set_sample_dropout).  The
+// launchers pick the dropout instantiation iff drop_thr > 0 (it takes the whole struct; the eval kernels take the
+// SampleKernelArgs slice) and set drop_epoch themselves (train_epoch_ptr).
+struct SampleArgs : SampleKernelArgs {
+    uint32_t drop_thr;        // p 2^24 (keep <=> draw >> 8 >= drop_thr); 0 = eval
+    float drop_scale;         // 1 / (1 - p)
+    uint64_t drop_seed;       // Philox key of the masks
+    const uint32_t* drop_epoch;  // the training dropout epoch word (counter word 3 = 2 + epoch)
 };
 constexpr int kProfStamps = 192;
 hipError_t launch_sample(const SampleArgs& a, int precision, hipStream_t stream);

@@ -24,9 +24,11 @@ namespace amuse {
 namespace {
 
 // NC weight-stream units are issued after the score MFMA and again after the softmax (ring_issue, amuse_dev.hpp)
-template <int PREC, int NC, int IPH>
+// DROP: site 0 of train-mode sampling on the probabilities - element 4 g + m of this lane keeps iff bit (doff + m) of dbits
+template <int PREC, int NC, int IPH, bool DROP = false>
 __device__ __forceinline__ void attention_head(const f32x4 (&q)[2], const f32x4 (&k)[2], const f32x4 (&v)[2],
-                                               const bool (&kvalid)[4], f32x4 (&o)[2], WRing<kRing>& rg) {
+                                               const bool (&kvalid)[4], f32x4 (&o)[2], WRing<kRing>& rg,
+                                               uint32_t dbits = 0, int doff = 0, float dscale = 1.f) {
     // S^T[j][i] = sum_d K[j][d] Q[i][d]  ->  lane (g, i) holds S[i][4 g + m]
     constexpr bool EXACT = (PREC != PREC_BF16);   // fp32 / fp32x: libm exp and IEEE division, as torch.softmax
     f32x4 st = splat4(0.f);
@@ -62,6 +64,10 @@ __device__ __forceinline__ void attention_head(const f32x4 (&q)[2], const f32x4 
 #pragma unroll
         for (int m = 0; m < 4; ++m) p[m] = EXACT ? p[m] / sum : p[m] * inv;
     }
+    if constexpr (DROP) {
+#pragma unroll
+        for (int m = 0; m < 4; ++m) p[m] = ((dbits >> (doff + m)) & 1u) ? p[m] * dscale : 0.f;
+    }
     ring_issue<NC, kRing, (IPH + NC) % kRing>(rg);
     // O^T[d][i] = sum_j V[j][d] P[i][j]; v is feature-lane: lane (g, d) holds V[4 g + m][d]
 #pragma unroll
@@ -95,12 +101,38 @@ __device__ __forceinline__ void stamp(Prof& pf) {
     }
 }
 
+// Train-mode sampling (amuse_hip.h amuse_set_sample_dropout): what a lane needs to draw its masks.  tok / cl: the lane's row
+// (token of clip slot cl of the tile); clip: the global clip index; epoch2 = 2 + the dropout epoch.
+struct SDrop {
+    uint64_t seed;
+    uint32_t clip, step, epoch2, thr;
+    float scale;
+    int S, tok, cl;
+};
+// keep bits of this lane's 8 elements of the [16 x 128] sites 1 / 3 in tiles 2 wave, 2 wave + 1 (bits 4 i + m)
+__device__ __forceinline__ uint32_t sdrop_row_bits(const SDrop& d, uint32_t ls, int wave, int g) {
+    const uint32_t e4 = (uint32_t)(d.tok * 32 + 8 * wave + g);   // e = tok 128 + 16 t + 4 g + m
+    return sdrop_bits4(d.seed, d.clip, d.step, ls, e4, d.epoch2, d.thr) |
+           (sdrop_bits4(d.seed, d.clip, d.step, ls, e4 + 4, d.epoch2, d.thr) << 4);
+}
+
 // One TransformerEncoderLayer.forward_post (cross_attention.py:259-272) on the row-lane tile x.
-template <int PREC, bool PROF>
+template <int PREC, bool PROF, bool DROP>
 __device__ __forceinline__ void encoder_block(f32x4 (&x)[kTiles], WRing<kRing>& rg, const float* pv,
                                               const bool (&kvalid)[4], char* comb, int wave, int lane,
-                                              bool next_has_skip, Prof& pf) {
+                                              bool next_has_skip, Prof& pf, const SDrop& dr, int blk) {
     const int g = lane >> 4, r = lane & 15;
+    // train-mode sampling, site 0: element (h S + q) S + k of the probabilities; this lane holds keys k = 4 g + m - cl S of
+    // query q = tok, head h = wave: elements base .. base + 3, i.e. inside Philox groups base >> 2 and (base >> 2) + 1
+    uint32_t abits = 0;
+    int aoff = 0;
+    if constexpr (DROP) {
+        const int base = (wave * dr.S + dr.tok) * dr.S + 4 * g - dr.cl * dr.S;
+        const int e4 = base >> 2;   // (floor; groups below 0 only ever hold keys of other clips, whose p is 0)
+        aoff = base - 4 * e4;
+        abits = sdrop_bits4(dr.seed, dr.clip, dr.step, 4u * blk, (uint32_t)e4 & 0xffffu, dr.epoch2, dr.thr) |
+                (sdrop_bits4(dr.seed, dr.clip, dr.step, 4u * blk, (uint32_t)(e4 + 1) & 0xffffu, dr.epoch2, dr.thr) << 4);
+    }
     // ring phases of the five GEMMs of a block (compile-time; a block consumes a whole number of revolutions)
     constexpr int U_QK = gemm_units(PREC, 4, kTiles), U_V = gemm_units(PREC, 2, kTiles);
     constexpr int U_OUT = gemm_units(PREC, kTiles, 2), U_FF = gemm_units(PREC, kTiles, kTiles);
@@ -156,7 +188,7 @@ __device__ __forceinline__ void encoder_block(f32x4 (&x)[kTiles], WRing<kRing>& 
     v[0] += splat4(b_v[0]);
     v[1] += splat4(b_v[1]);
     f32x4 o[2];
-    attention_head<PREC, A8, 8>(q, k, v, kvalid, o, rg);
+    attention_head<PREC, A8, 8, DROP>(q, k, v, kvalid, o, rg, abits, aoff, dr.scale);
     stamp<PROF>(pf);  // 2: attention done
     // ---- out_proj, split-K over heads; combine; residual; LayerNorm1
     f32x4 part[kTiles];
@@ -165,7 +197,8 @@ __device__ __forceinline__ void encoder_block(f32x4 (&x)[kTiles], WRing<kRing>& 
     gemm_ring<PREC, kTiles, 2, false, kRing, P_OUT, !DELAY>(part, o, rg);
     stamp<PROF>(pf);  // 3: out_proj partial done
     // x = LN1(x + sum_w part + b_out): reduce-scatter / LayerNorm / all-gather (amuse_dev.hpp combine_rs)
-    combine_rs<true, FAST, A8, kRing, 24>(part, x, true, pv + PV_OUT_B, pv + PV_LN1_W, pv + PV_LN1_B, comb, wave, lane, &rg);
+    combine_rs<true, FAST, A8, kRing, 24, DROP>(part, x, true, pv + PV_OUT_B, pv + PV_LN1_W, pv + PV_LN1_B, comb, wave, lane, &rg,
+                                                DROP ? sdrop_row_bits(dr, 4u * blk + 1u, wave, g) : 0u, dr.scale);
     stamp<PROF>(pf);  // 4: combine 1 + LN1 done
     stamp<PROF>(pf);  // 5: (kept for timeline compatibility)
     // ---- FFN in four interleaved quarters: linear1 for 2 of this wave's 8 hidden tiles -> bias + GELU ->
@@ -190,6 +223,13 @@ __device__ __forceinline__ void encoder_block(f32x4 (&x)[kTiles], WRing<kRing>& 
             const float h0 = hq[qd][0][m] + b1a[m], h1 = hq[qd][1][m] + b1b[m];
             hq[qd][0][m] = FAST_ACT ? gelu_erf_fast(h0) : gelu_erf(h0);
             hq[qd][1][m] = FAST_ACT ? gelu_erf_fast(h1) : gelu_erf(h1);
+        }
+        if constexpr (DROP) {   // site 2, the FFN's inner dropout: element tok 512 + f of hidden tile 8 wave + 2 qd + j
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const uint32_t e4 = (uint32_t)(dr.tok * 128 + 4 * (kTiles * wave + 2 * qd + j) + g);
+                hq[qd][j] = sdrop_apply4(hq[qd][j], sdrop_bits4(dr.seed, dr.clip, dr.step, 4u * blk + 2u, e4, dr.epoch2, dr.thr), dr.scale);
+            }
         }
     };
     // fp32: always re-arm at consumption; bf16: the first four unit groups re-arm (with the last four), the last
@@ -233,6 +273,9 @@ __device__ __forceinline__ void encoder_block(f32x4 (&x)[kTiles], WRing<kRing>& 
             combine_rs<true, FAST, 16, kRing, 0>(part, x, true, pv + PV_L2_B, pv + PV_LN2_W, pv + PV_LN2_B, comb, wave, lane, &rg);
         else
             combine_rs<true, FAST, 32, kRing, 0>(part, x, true, pv + PV_L2_B, pv + PV_LN2_W, pv + PV_LN2_B, comb, wave, lane, &rg);
+    } else if constexpr (DROP) {   // site 3: dropout2 on linear2's output
+        combine_rs<true, FAST, 0, 1, 0, true>(part, x, true, pv + PV_L2_B, pv + PV_LN2_W, pv + PV_LN2_B, comb, wave, lane, nullptr,
+                                              sdrop_row_bits(dr, 4u * blk + 3u, wave, g), dr.scale);
     } else {
         combine_rs<true, FAST>(part, x, true, pv + PV_L2_B, pv + PV_LN2_W, pv + PV_LN2_B, comb, wave, lane);
     }
@@ -245,8 +288,10 @@ __device__ __forceinline__ void store_tap(float* tap, int slot, const f32x4 (&x)
     for (int t = 0; t < kTiles; ++t) st4(tap + ((size_t)slot * 16 + r) * kD + 16 * t + 4 * g, x[t]);
 }
 
-template <int PREC, bool PROF>
-__global__ __launch_bounds__(256, 1) void k_sample(SampleArgs a) {
+// DROP = true (train-mode sampling, a.drop_thr > 0): the Denoiser's encoder dropouts live, masks drawn in registers at the point of
+// use; that instantiation takes the whole SampleArgs, the eval ones the SampleKernelArgs slice
+template <int PREC, bool PROF, bool DROP, class Args>
+__global__ __launch_bounds__(256, 1) void k_sample(Args a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* comb = smem;                                           // split-K combine buffers (kCombBytes)
     f32x4* skip = reinterpret_cast<f32x4*>(smem + kCombBytes);  // [4][8 tiles][64 lanes]
@@ -291,6 +336,11 @@ __global__ __launch_bounds__(256, 1) void k_sample(SampleArgs a) {
             }
         }
     }
+    SDrop dr{};
+    if constexpr (DROP) {
+        dr.seed = a.drop_seed; dr.clip = (uint32_t)(a.clip0 + (uint64_t)clip); dr.epoch2 = 2u + *a.drop_epoch;
+        dr.thr = a.drop_thr; dr.scale = a.drop_scale; dr.S = S; dr.tok = tok; dr.cl = cl;
+    }
     const bool tap = a.tap_out != nullptr && blockIdx.x == 0 && wave == 0;
     const uint4* wbase = a.wstream + (size_t)wave * (a.wave_units + kRing) * 64 + lane;
     WRing<kRing> rg;
@@ -314,6 +364,7 @@ __global__ __launch_bounds__(256, 1) void k_sample(SampleArgs a) {
             for (int t = 0; t < kTiles; ++t) stat[t] = ld4(tt + 16 * t + 4 * g);
         }
         if (tap && step == 0) store_tap(a.tap_out, 0, x, g, r);
+        dr.step = (uint32_t)step;
         rg.next = wbase + kRing * 64;  // the ring already holds units 0..R-1 of this step (stream tail = its head)
         if constexpr (PROF) {
             pf.on = a.prof_out != nullptr && blockIdx.x == 0 && lane == 0 && step == a.prof_step;
@@ -348,8 +399,8 @@ __global__ __launch_bounds__(256, 1) void k_sample(SampleArgs a) {
                 }
             }
             stamp<PROF>(pf);  // block start (after the skip linear, if any)
-            encoder_block<PREC, PROF>(x, rg, pvl + blk * kEncPv, kvalid, comb, wave, lane,
-                                      blk >= 4 && blk < kLayers - 1, pf);
+            encoder_block<PREC, PROF, DROP>(x, rg, pvl + blk * kEncPv, kvalid, comb, wave, lane,
+                                            blk >= 4 && blk < kLayers - 1, pf, dr, blk);
             if (blk < 4 && wave == 0) {
                 f32x4* sk = skip + (size_t)blk * kTiles * 64;
 #pragma unroll
@@ -445,21 +496,28 @@ __global__ __launch_bounds__(256, 1) void k_sample(SampleArgs a) {
 // The 4-wave kernel serves the fp32 parity mode only: bf16 / fp16 / fp32x sample on the 8-wave kernels (k_sampler8.hip, k_sampler8x.hip).  The template stays
 // parametric in PREC (its building blocks in amuse_dev.hpp are shared with k_sampler_dec.hip and k_vae.hip, which instantiate every mode); the bf16 and fp32x
 // instantiations of THIS kernel and their agreement tests with the 8-wave kernels are shelved under tools/probes/sampler_4wave/.
-hipError_t launch_sample(const SampleArgs& a, int precision, hipStream_t stream) {
+hipError_t launch_sample(const SampleArgs& a_in, int precision, hipStream_t stream) {
     if (precision != PREC_F32) return hipErrorInvalidValue;
+    SampleArgs a = a_in;
+    if (a.drop_thr > 0 && !(a.drop_epoch = train_epoch_ptr())) return hipErrorOutOfMemory;
     const int tiles = (a.B + a.G - 1) / a.G;
     const dim3 grid(tiles), block(256);
     static DeviceOnce once;
     int dev_;
     if (!once.done(&dev_)) {
-        for (const void* k : {reinterpret_cast<const void*>(&k_sample<PREC_F32, false>), reinterpret_cast<const void*>(&k_sample<PREC_F32, true>)}) {
+        for (const void* k : {reinterpret_cast<const void*>(&k_sample<PREC_F32, false, false, SampleKernelArgs>), reinterpret_cast<const void*>(&k_sample<PREC_F32, true, false, SampleKernelArgs>),
+                              reinterpret_cast<const void*>(&k_sample<PREC_F32, false, true, SampleArgs>), reinterpret_cast<const void*>(&k_sample<PREC_F32, true, true, SampleArgs>)}) {
             hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kSampleLdsBytes);
             if (e != hipSuccess) return e;
         }
         once.set(dev_);
     }
-    if (a.prof_out) hipLaunchKernelGGL((k_sample<PREC_F32, true>), grid, block, kSampleLdsBytes, stream, a);
-    else hipLaunchKernelGGL((k_sample<PREC_F32, false>), grid, block, kSampleLdsBytes, stream, a);
+    const SampleKernelArgs ka = a;
+    if (a.drop_thr > 0) {
+        if (a.prof_out) hipLaunchKernelGGL((k_sample<PREC_F32, true, true, SampleArgs>), grid, block, kSampleLdsBytes, stream, a);
+        else hipLaunchKernelGGL((k_sample<PREC_F32, false, true, SampleArgs>), grid, block, kSampleLdsBytes, stream, a);
+    } else if (a.prof_out) hipLaunchKernelGGL((k_sample<PREC_F32, true, false, SampleKernelArgs>), grid, block, kSampleLdsBytes, stream, ka);
+    else hipLaunchKernelGGL((k_sample<PREC_F32, false, false, SampleKernelArgs>), grid, block, kSampleLdsBytes, stream, ka);
     return hipGetLastError();
 }
 

@@ -110,9 +110,10 @@ __device__ __forceinline__ constexpr int part_row(int w, int t) {
     return k + (k >= t ? 1 : 0);
 }
 // LN = false (U-Net skip linear): tiles = sum + bias - no residual, no LayerNorm, and one barrier less.
-template <int W, int NP, bool FAST, bool LN>
+template <int W, int NP, bool FAST, bool LN, bool DRP>
 __device__ __forceinline__ void combine_red(f32x4 (&part)[kTiles], f32x4 (&xo)[2], OPV (&xb)[4], const float* bias,
-                                            const float* gamma, const float* beta, char* lds, int lane) {
+                                            const float* gamma, const float* beta, char* lds, int lane, uint32_t dbits,
+                                            float dscale) {
     float2* stats = reinterpret_cast<float2*>(lds + kStat8Off);
     const int g = lane >> 4, r = lane & 15;
     constexpr int T0 = 2 * W;
@@ -149,7 +150,9 @@ __device__ __forceinline__ void combine_red(f32x4 (&part)[kTiles], f32x4 (&xo)[2
             } else {
                 sum = ((p[0][i] + p[1][i]) + p[2][i]) + p[3][i];
             }
-            y[i] = LN ? xo[i] + (sum + bi[i]) : sum + bi[i];
+            f32x4 br = sum + bi[i];
+            if constexpr (DRP) br = sdrop_apply4(br, dbits >> (4 * i), dscale);   // dropout1 / dropout2 (train-mode sampling)
+            y[i] = LN ? xo[i] + br : br;
         }
     }
     if constexpr (LN) {
@@ -191,29 +194,35 @@ __device__ __forceinline__ void combine_red(f32x4 (&part)[kTiles], f32x4 (&xo)[2
     // pins the arrays in scratch): an immediate operand cannot be merged
     asm volatile("; combine_red case %0" ::"n"(W));
 }
-template <int NP, bool FAST, bool LN = true>
+// DRP: (sum + bias) of tile 2 h + i times sdrop_apply4(., dbits >> 4 i, dscale) before the residual add
+template <int NP, bool FAST, bool LN = true, bool DRP = false>
 __device__ __forceinline__ void combine_reduce(f32x4 (&part)[kTiles], f32x4 (&xo)[2], OPV (&xb)[4],
                                                const float* bias, const float* gamma, const float* beta, char* lds,
-                                               int h, int lane) {
-    if (h == 0) combine_red<0, NP, FAST, LN>(part, xo, xb, bias, gamma, beta, lds, lane);
-    else if (h == 1) combine_red<1, NP, FAST, LN>(part, xo, xb, bias, gamma, beta, lds, lane);
-    else if (h == 2) combine_red<2, NP, FAST, LN>(part, xo, xb, bias, gamma, beta, lds, lane);
-    else combine_red<3, NP, FAST, LN>(part, xo, xb, bias, gamma, beta, lds, lane);
+                                               int h, int lane, uint32_t dbits = 0, float dscale = 1.f) {
+    if (h == 0) combine_red<0, NP, FAST, LN, DRP>(part, xo, xb, bias, gamma, beta, lds, lane, dbits, dscale);
+    else if (h == 1) combine_red<1, NP, FAST, LN, DRP>(part, xo, xb, bias, gamma, beta, lds, lane, dbits, dscale);
+    else if (h == 2) combine_red<2, NP, FAST, LN, DRP>(part, xo, xb, bias, gamma, beta, lds, lane, dbits, dscale);
+    else combine_red<3, NP, FAST, LN, DRP>(part, xo, xb, bias, gamma, beta, lds, lane, dbits, dscale);
 }
 // The A waves' side: publish the partial, then the barriers and the gather - with the issue of N1 + N2 + N3
 // weight-stream units into ring slots IPH0.. in between.  These waves are off the critical path here, so their
 // blocking global_load issue costs nothing as long as it fits the reducers' phases.
 // N0 units go out BEFORE the first barrier: free where the A waves arrive early (the linear2 combine - their FFN half
 // is the shorter one), on the critical path where they arrive last (the out_proj combine: N0 = 0).
-template <int N0, int N1, int N2, int N3, int IPH0, bool LN = true>
+// hook: extra work of the waiting time behind the N1 units (train-mode sampling: this wave's FFN masks)
+struct NoHook {
+    __device__ void operator()() const {}
+};
+template <int N0, int N1, int N2, int N3, int IPH0, bool LN = true, class Hook = NoHook>
 __device__ __forceinline__ void combine_publish(const f32x4 (&part)[kTiles], OPV (&xb)[4], char* lds, int h,
-                                                int lane, Ring& rg) {
+                                                int lane, Ring& rg, Hook hook = {}) {
 #pragma unroll
     for (int t = 0; t < kTiles; ++t)
         *a8_slot(lds, h + (h >= t ? 1 : 0), t, lane) = part[t];  // part_row(h, t), h < 4
     ring_issue<N0, kR8, IPH0 % kR8>(rg);
     __syncthreads();
     ring_issue<N1, kR8, (IPH0 + N0) % kR8>(rg);
+    hook();
     if constexpr (LN) __syncthreads();   // (the reducers' row-statistics exchange)
     ring_issue<N2, kR8, (IPH0 + N0 + N1) % kR8>(rg);
     __syncthreads();
@@ -261,8 +270,11 @@ __device__ __forceinline__ void combine_publish_c2(const f32x4 (&part)[kTiles], 
     for (int c = 0; c < 4; ++c) xb[c] = __builtin_bit_cast(OPV, *xb_slot(lds, c, lane));
 }
 
+// DROP: site 0 of train-mode sampling - probability m of this lane kept iff bit m of dbits
+template <bool DROP = false>
 __device__ __forceinline__ void attention_head8(const f32x4 (&q)[2], const f32x4 (&k)[2], const f32x4 (&v)[2],
-                                                const bool (&kvalid)[4], f32x4 (&o)[2]) {
+                                                const bool (&kvalid)[4], f32x4 (&o)[2], uint32_t dbits = 0,
+                                                float dscale = 1.f) {
     // S^T[j][i] = sum_d K[j][d] Q[i][d]  ->  lane (g, i) holds S[i][4 g + m]   (k_sampler.hip attention_head)
     f32x4 st = OP_MFMA(OP_PACK(k[0], k[1]), OP_PACK(q[0], q[1]), splat4(0.f));
     float mx = -INFINITY;
@@ -281,6 +293,7 @@ __device__ __forceinline__ void attention_head8(const f32x4 (&q)[2], const f32x4
     const float inv = __builtin_amdgcn_rcpf(sum);
 #pragma unroll
     for (int m = 0; m < 4; ++m) p[m] *= inv;
+    if constexpr (DROP) p = sdrop_apply4(p, dbits, dscale);
 #pragma unroll
     for (int td = 0; td < 2; ++td)
         o[td] = OP_MFMA(OP_PACK(v[td], splat4(0.f)), OP_PACK(p, splat4(0.f)), splat4(0.f));
@@ -301,9 +314,15 @@ __device__ __forceinline__ void stamp8(Prof8& pf) {
 
 // GELU (amuse_dev.hpp OP_GELU: the result is an MFMA operand, i.e. rounded to bf16 next) on one FFN quarter (two
 // hidden tiles); linear1's bias is already in the accumulators (ffn_half)
-__device__ __forceinline__ void gelu_pair(f32x4 (&hq)[2]) {
+// DROP: then the FFN's inner dropout (site 2), keep bits 0..3 / 4..7 of dbits for the two tiles
+template <bool DROP>
+__device__ __forceinline__ void gelu_pair(f32x4 (&hq)[2], uint32_t dbits, float dscale) {
     hq[0] = OP_GELU(hq[0]);
     hq[1] = OP_GELU(hq[1]);
+    if constexpr (DROP) {
+        hq[0] = sdrop_apply4(hq[0], dbits, dscale);
+        hq[1] = sdrop_apply4(hq[1], dbits >> 4, dscale);
+    }
 }
 
 // this wave's two FFN quarters (Q0, Q0 + 1 of head h's slice): linear1 for 2 hidden tiles each -> bias + GELU ->
@@ -311,9 +330,10 @@ __device__ __forceinline__ void gelu_pair(f32x4 (&hq)[2]) {
 // slots 0..31, nothing re-armed.
 // LATE8: the last 8 units (F2b) are issued only now, behind the first GEMMs' MFMAs (B waves: their fetch window, the A
 // waves' attention phase, is a little too short for all 32)
-template <int Q0, bool LATE8>
+// DROP: site 2 keep bits of the four hidden tiles in dbits (bits 4 k + m: tile k of the half)
+template <int Q0, bool LATE8, bool DROP = false>
 __device__ __forceinline__ void ffn_half(f32x4 (&part)[kTiles], const OPV (&xb)[4], Ring& rg, const float* pv,
-                                         int h, int g) {
+                                         int h, int g, uint32_t dbits = 0, float dscale = 1.f) {
     constexpr int P = OP_PREC;
     // accumulators start at linear1's bias (this lane's 4 features of each hidden tile)
     const float* b1 = pv + PV_L1_B + 16 * (kTiles * h + 2 * Q0) + 4 * g;
@@ -325,7 +345,7 @@ __device__ __forceinline__ void ffn_half(f32x4 (&part)[kTiles], const OPV (&xb)[
     // first VALU instruction; interleaved 1 : 6 the GELU of one quarter runs in the shadow of the other quarter's
     // MFMAs (the two are independent).
     gemm_xb<2, false, 8>(hb, xb, rg);
-    gelu_pair(ha);
+    gelu_pair<DROP>(ha, dbits, dscale);
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // 1 MFMA
@@ -333,7 +353,7 @@ __device__ __forceinline__ void ffn_half(f32x4 (&part)[kTiles], const OPV (&xb)[
     }
     __builtin_amdgcn_sched_barrier(0);
     gemm_ring<P, kTiles, 2, false, kR8, 16, false>(part, ha, rg);
-    gelu_pair(hb);
+    gelu_pair<DROP>(hb, dbits >> 8, dscale);
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
@@ -343,18 +363,89 @@ __device__ __forceinline__ void ffn_half(f32x4 (&part)[kTiles], const OPV (&xb)[
     gemm_ring<P, kTiles, 2, false, kR8, 24, false>(part, hb, rg);
 }
 
+// per-lane constants of the tile (row-lane layout: lane (g, r) holds row r)
+struct Lane8 {
+    int lane, g, r, cl, tok;
+    long clip;
+    bool valid, is_lat;
+};
+// Cheap to derive, expensive to keep: held across the block loop these constants get spilled to scratch (the ring
+// leaves no slack), so the step loop re-derives them where it needs them from an opaque copy of the lane id.
+__device__ __forceinline__ Lane8 lane_info(const SampleKernelArgs& a, int lane) {
+    asm volatile("" : "+v"(lane));
+    Lane8 L;
+    L.lane = lane;
+    L.g = lane >> 4;
+    L.r = lane & 15;
+    const int S = a.S, R = S * a.G;
+    L.cl = L.r / S;
+    L.tok = L.r - L.cl * S;
+    L.clip = (long)blockIdx.x * a.G + L.cl;
+    L.valid = (L.r < R) && (L.clip < (long)a.B);
+    L.is_lat = L.valid && L.tok == 0;
+    return L;
+}
+
+// ---- train-mode sampling (amuse_hip.h amuse_set_sample_dropout): the uniform part of the mask counters; the per-lane part (global
+// clip, the row's token) is re-derived by lane_info where the bits are drawn, and the bits themselves travel in one register
+struct SDrop8 {
+    uint64_t seed;
+    uint32_t step, epoch2, thr;
+    float scale;
+};
+template <bool DROP, class Args>
+__device__ __forceinline__ SDrop8 sdrop8_of(const Args& a) {
+    SDrop8 d{};
+    if constexpr (DROP) {
+        d.seed = a.drop_seed; d.epoch2 = 2u + *a.drop_epoch; d.thr = a.drop_thr; d.scale = a.drop_scale;
+    }
+    return d;
+}
+// site 0: the probabilities of query q = tok of head h held by this lane - keys k = 4 g + m - cl S, elements (h S + q) S + k =
+// base + m, i.e. inside Philox groups base >> 2 and (base >> 2) + 1 (bits m of the result; groups below 0 only ever cover keys
+// of other clips, whose probability is 0 anyway)
+__device__ __forceinline__ uint32_t sdrop8_attn_bits(const SampleKernelArgs& a, const SDrop8& d, int blk, int h, int lane) {
+    const Lane8 L = lane_info(a, lane);
+    const int S = a.S, base = (h * S + L.tok) * S + 4 * L.g - L.cl * S, e4 = base >> 2;
+    const uint32_t cu = (uint32_t)(a.clip0 + (uint64_t)L.clip), ls = 4u * blk;
+    const uint32_t b = sdrop_bits4(d.seed, cu, d.step, ls, (uint32_t)e4 & 0xffffu, d.epoch2, d.thr) |
+                       (sdrop_bits4(d.seed, cu, d.step, ls, (uint32_t)(e4 + 1) & 0xffffu, d.epoch2, d.thr) << 4);
+    return b >> (base - 4 * e4);
+}
+// site 2 of FFN quarters Q0, Q0 + 1 of slice h (hidden tiles 8 h + 2 Q0 + k, element tok 512 + f): bits 4 k + m
+template <int Q0>
+__device__ __forceinline__ uint32_t sdrop8_ffn_bits(const SampleKernelArgs& a, const SDrop8& d, int blk, int h, int lane) {
+    const Lane8 L = lane_info(a, lane);
+    const uint32_t cu = (uint32_t)(a.clip0 + (uint64_t)L.clip), e4 = (uint32_t)(L.tok * 128 + 4 * (kTiles * h + 2 * Q0) + L.g);
+    uint32_t b = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) b |= sdrop_bits4(d.seed, cu, d.step, 4u * blk + 2u, e4 + 4 * k, d.epoch2, d.thr) << (4 * k);
+    return b;
+}
+// sites 1 / 3 (element tok 128 + f) of the reducer's tiles 2 h, 2 h + 1: bits 4 i + m
+__device__ __forceinline__ uint32_t sdrop8_row_bits(const SampleKernelArgs& a, const SDrop8& d, uint32_t ls, int h, int lane) {
+    const Lane8 L = lane_info(a, lane);
+    const uint32_t cu = (uint32_t)(a.clip0 + (uint64_t)L.clip), e4 = (uint32_t)(L.tok * 32 + 8 * h + L.g);
+    return sdrop_bits4(d.seed, cu, d.step, ls, e4, d.epoch2, d.thr) | (sdrop_bits4(d.seed, cu, d.step, ls, e4 + 4, d.epoch2, d.thr) << 4);
+}
+
 // One TransformerEncoderLayer.forward_post (cross_attention.py:259-272), A / B role split.  The two roles are
 // separate instantiations (and the whole step loop is instantiated per role, OP_KERNEL below): sharing one body
 // behind a runtime branch makes hipcc's register allocator spill hundreds of VGPRs at the merges.
 // xb: the residual stream as four packed bf16 operands (every wave); xo: this B wave's two feature tiles in fp32.
-template <bool ROLEA, bool PROF>
+// DROP: train-mode sampling - the A waves draw the attention bits in front of in_proj and their FFN bits in the out_proj combine's
+// waiting time, the B waves all of theirs (both combines, FFN) while the A waves run attention
+template <bool ROLEA, bool PROF, bool DROP>
 __device__ __forceinline__ void encoder_block8(OPV (&xb)[4], f32x4 (&xo)[2], Ring& rg, const float* pv,
                                                const bool (&kvalid)[4], char* lds, int h, int lane, bool next_has_skip,
-                                               const uint4* skip_next, Prof8& pf) {
+                                               const uint4* skip_next, Prof8& pf, const SampleKernelArgs& a,
+                                               const SDrop8& dr, int blk) {
     constexpr int P = OP_PREC;
     const int g = lane >> 4, r = lane & 15;
     f32x4 part[kTiles];
     if constexpr (ROLEA) {
+        uint32_t abits = 0, fbits = 0;
+        if constexpr (DROP) abits = sdrop8_attn_bits(a, dr, blk, h, lane);
         // ---- ring on entry: in_proj q,k (slots 0..15), v (16..23), out_proj (24..31)
         f32x4 b_qk[4];
         float b_v[2];
@@ -376,32 +467,42 @@ __device__ __forceinline__ void encoder_block8(OPV (&xb)[4], f32x4 (&xo)[2], Rin
         v[0] += splat4(b_v[0]);
         v[1] += splat4(b_v[1]);
         f32x4 o[2];
-        attention_head8(q, k, v, kvalid, o);
+        attention_head8<DROP>(q, k, v, kvalid, o, abits, dr.scale);
 #pragma unroll
         for (int t = 0; t < kTiles; ++t) part[t] = splat4(0.f);
         gemm_ring<P, kTiles, 2, false, kR8, 24, false>(part, o, rg);
         stamp8<PROF>(pf);  // 1: in_proj + attention + out_proj partial
         // ---- out_proj combine (B reduces): meanwhile fetch this wave's FFN half
-        combine_publish<0, kC1N1, kC1N2, 32 - kC1N1 - kC1N2, 0>(part, xb, lds, h, lane, rg);
+        if constexpr (DROP) {
+            auto hook = [&]() { fbits = sdrop8_ffn_bits<0>(a, dr, blk, h, lane); };
+            combine_publish<0, kC1N1, kC1N2, 32 - kC1N1 - kC1N2, 0, true, decltype(hook)>(part, xb, lds, h, lane, rg, hook);
+        } else {
+            combine_publish<0, kC1N1, kC1N2, 32 - kC1N1 - kC1N2, 0>(part, xb, lds, h, lane, rg);
+        }
         stamp8<PROF>(pf);  // 2: combine 1
 #pragma unroll
         for (int t = 0; t < kTiles; ++t) part[t] = splat4(0.f);
-        ffn_half<0, false>(part, xb, rg, pv, h, g);
+        ffn_half<0, false, DROP>(part, xb, rg, pv, h, g, fbits, dr.scale);
         stamp8<PROF>(pf);  // 3: FFN
         // ---- linear2 combine (B reduces): meanwhile fetch the next block's attention weights
         combine_publish_c2<kC2N0, kC2N1, 32 - kC2N0 - kC2N1>(part, xb, lds, h, lane, rg, next_has_skip, skip_next);
     } else {
         // ---- ring empty on entry: fetch this wave's FFN half while the A waves run attention
         ring_issue<kBEarly, kR8, 0>(rg);
+        // bits 0..7: dropout1 of tiles 2 h, 2 h + 1; 8..15: dropout2 of the same; 16..31: the FFN's inner dropout
+        uint32_t bbits = 0;
+        if constexpr (DROP)
+            bbits = sdrop8_row_bits(a, dr, 4u * blk + 1u, h, lane) | (sdrop8_row_bits(a, dr, 4u * blk + 3u, h, lane) << 8) |
+                    (sdrop8_ffn_bits<2>(a, dr, blk, h, lane) << 16);
         stamp8<PROF>(pf);
 #pragma unroll
         for (int t = 0; t < kTiles; ++t) part[t] = splat4(0.f);
-        combine_reduce<4, true>(part, xo, xb, pv + PV_OUT_B, pv + PV_LN1_W, pv + PV_LN1_B, lds, h, lane);
+        combine_reduce<4, true, true, DROP>(part, xo, xb, pv + PV_OUT_B, pv + PV_LN1_W, pv + PV_LN1_B, lds, h, lane, bbits, dr.scale);
         stamp8<PROF>(pf);
-        ffn_half<2, (kBEarly < 32)>(part, xb, rg, pv, h, g);
+        ffn_half<2, (kBEarly < 32), DROP>(part, xb, rg, pv, h, g, bbits >> 16, dr.scale);
         stamp8<PROF>(pf);  // 3: FFN
         if (next_has_skip) ring_issue<8, kR8, 0>(rg);  // the x half of this wave's two output tiles of the next block's skip linear
-        combine_reduce<8, true>(part, xo, xb, pv + PV_L2_B, pv + PV_LN2_W, pv + PV_LN2_B, lds, h, lane);
+        combine_reduce<8, true, true, DROP>(part, xo, xb, pv + PV_L2_B, pv + PV_LN2_W, pv + PV_LN2_B, lds, h, lane, bbits >> 8, dr.scale);
     }
     stamp8<PROF>(pf);  // 4: combine 2
 }
@@ -411,32 +512,9 @@ __device__ __forceinline__ void store_tap_tile(float* tap, int slot, int t, cons
     st4(tap + ((size_t)slot * 16 + r) * kD + 16 * t + 4 * g, v);
 }
 
-// per-lane constants of the tile (row-lane layout: lane (g, r) holds row r)
-struct Lane8 {
-    int lane, g, r, cl, tok;
-    long clip;
-    bool valid, is_lat;
-};
-// Cheap to derive, expensive to keep: held across the block loop these constants get spilled to scratch (the ring
-// leaves no slack), so the step loop re-derives them where it needs them from an opaque copy of the lane id.
-__device__ __forceinline__ Lane8 lane_info(const SampleArgs& a, int lane) {
-    asm volatile("" : "+v"(lane));
-    Lane8 L;
-    L.lane = lane;
-    L.g = lane >> 4;
-    L.r = lane & 15;
-    const int S = a.S, R = S * a.G;
-    L.cl = L.r / S;
-    L.tok = L.r - L.cl * S;
-    L.clip = (long)blockIdx.x * a.G + L.cl;
-    L.valid = (L.r < R) && (L.clip < (long)a.B);
-    L.is_lat = L.valid && L.tok == 0;
-    return L;
-}
-
 // The whole T-step loop of one role.  Both roles execute the same sequence of workgroup barriers.
-template <bool ROLEA, bool PROF>
-__device__ __forceinline__ void role_loop8(const SampleArgs& a, char* smem, int w8, const Lane8& L0) {
+template <bool ROLEA, bool PROF, bool DROP, class Args>
+__device__ __forceinline__ void role_loop8(const Args& a, char* smem, int w8, const Lane8& L0) {
     uint4* skipbf = reinterpret_cast<uint4*>(smem + kSkip8Off);
     const float* pvl = reinterpret_cast<const float*>(smem + kPv8Off);
     const f32x4* tokrows = reinterpret_cast<const f32x4*>(smem + kTokRows8Off);
@@ -470,8 +548,10 @@ __device__ __forceinline__ void role_loop8(const SampleArgs& a, char* smem, int 
         ring_fill(rg, wbase);
     }
     Prof8 pf{a.prof_out ? a.prof_out + (size_t)w8 * 96 : nullptr, 0, false};
+    SDrop8 dr = sdrop8_of<DROP>(a);
 #pragma unroll 1
     for (int step = 0; step < a.T; ++step) {
+        dr.step = (uint32_t)step;
         // ---- token assembly (denoiser.py:174,180-181): every wave builds the four packed operands, a B wave also
         // its own two tiles in fp32
         OPV xb[4];
@@ -531,8 +611,8 @@ __device__ __forceinline__ void role_loop8(const SampleArgs& a, char* smem, int 
                 for (int c = 0; c < 4; ++c) xb[c] = __builtin_bit_cast(OPV, *reinterpret_cast<const uint4*>(a8_slot(smem, 7, c, lane)));
             }
             stamp8<PROF>(pf);  // 0: block start (after the skip linear, if any)
-            encoder_block8<ROLEA, PROF>(xb, xo, rg, pvl + blk * kEncPv, kvalid, smem, h, lane, blk >= 4 && blk < kLayers - 1,
-                                        skipbf + (7 - blk) * 4 * 64, pf);
+            encoder_block8<ROLEA, PROF, DROP>(xb, xo, rg, pvl + blk * kEncPv, kvalid, smem, h, lane, blk >= 4 && blk < kLayers - 1,
+                                              skipbf + (7 - blk) * 4 * 64, pf, a, dr, blk);
             if (!ROLEA && blk < 4 && w8 == 4) {
 #pragma unroll
                 for (int p = 0; p < 4; ++p) skipbf[(blk * 4 + p) * 64 + lane] = __builtin_bit_cast(uint4, xb[p]);
@@ -613,8 +693,9 @@ __device__ __forceinline__ void role_loop8(const SampleArgs& a, char* smem, int 
     }
 }
 
-template <bool PROF>
-__global__ __launch_bounds__(512) void OP_KERNEL(SampleArgs a) {
+// DROP = true (train-mode sampling, a.drop_thr > 0) takes the whole SampleArgs, the eval instantiations the SampleKernelArgs slice
+template <bool PROF, bool DROP, class Args>
+__global__ __launch_bounds__(512) void OP_KERNEL(Args a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* pvl = reinterpret_cast<float*>(smem + kPv8Off);
     f32x4* tokrows = reinterpret_cast<f32x4*>(smem + kTokRows8Off);
@@ -648,8 +729,8 @@ __global__ __launch_bounds__(512) void OP_KERNEL(SampleArgs a) {
     }
     if (w8 == 4 && L.lane < 32 && !a.time_tok_clip) st4(ttl + 4 * L.lane, ld4(a.time_tok + 4 * L.lane));
     __syncthreads();
-    if (w8 < 4) role_loop8<true, PROF>(a, smem, w8, L);
-    else role_loop8<false, PROF>(a, smem, w8, L);
+    if (w8 < 4) role_loop8<true, PROF, DROP>(a, smem, w8, L);
+    else role_loop8<false, PROF, DROP>(a, smem, w8, L);
     if (L.is_lat && w8 == 0 && a.latents_out) {
 #pragma unroll
         for (int t = 0; t < kTiles; ++t) st4(a.latents_out + (size_t)L.clip * kD + 16 * t + 4 * L.g, latl[t * 64 + L.lane]);
@@ -658,19 +739,26 @@ __global__ __launch_bounds__(512) void OP_KERNEL(SampleArgs a) {
 
 }  // namespace
 
-hipError_t OP_LAUNCH(const SampleArgs& a, hipStream_t stream) {
+hipError_t OP_LAUNCH(const SampleArgs& a_in, hipStream_t stream) {
+    SampleArgs a = a_in;
+    if (a.drop_thr > 0 && !(a.drop_epoch = train_epoch_ptr())) return hipErrorOutOfMemory;
     const int tiles = (a.B + a.G - 1) / a.G;
     static DeviceOnce once;
     int dev_;
     if (!once.done(&dev_)) {
-        for (const void* k : {reinterpret_cast<const void*>(&OP_KERNEL<false>), reinterpret_cast<const void*>(&OP_KERNEL<true>)}) {
+        for (const void* k : {reinterpret_cast<const void*>(&OP_KERNEL<false, false, SampleKernelArgs>), reinterpret_cast<const void*>(&OP_KERNEL<true, false, SampleKernelArgs>),
+                              reinterpret_cast<const void*>(&OP_KERNEL<false, true, SampleArgs>), reinterpret_cast<const void*>(&OP_KERNEL<true, true, SampleArgs>)}) {
             hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kSample8LdsBytes);
             if (e != hipSuccess) return e;
         }
         once.set(dev_);
     }
-    if (a.prof_out) hipLaunchKernelGGL(OP_KERNEL<true>, dim3(tiles), dim3(512), kSample8LdsBytes, stream, a);
-    else hipLaunchKernelGGL(OP_KERNEL<false>, dim3(tiles), dim3(512), kSample8LdsBytes, stream, a);
+    const SampleKernelArgs ka = a;
+    if (a.drop_thr > 0) {
+        if (a.prof_out) hipLaunchKernelGGL((OP_KERNEL<true, true, SampleArgs>), dim3(tiles), dim3(512), kSample8LdsBytes, stream, a);
+        else hipLaunchKernelGGL((OP_KERNEL<false, true, SampleArgs>), dim3(tiles), dim3(512), kSample8LdsBytes, stream, a);
+    } else if (a.prof_out) hipLaunchKernelGGL((OP_KERNEL<true, false, SampleKernelArgs>), dim3(tiles), dim3(512), kSample8LdsBytes, stream, ka);
+    else hipLaunchKernelGGL((OP_KERNEL<false, false, SampleKernelArgs>), dim3(tiles), dim3(512), kSample8LdsBytes, stream, ka);
     return hipGetLastError();
 }
 

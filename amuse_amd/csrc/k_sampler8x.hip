@@ -470,7 +470,7 @@ struct Lane8 {
     long clip;
     bool valid, is_lat;
 };
-__device__ __forceinline__ Lane8 lane_info(const SampleArgs& a, int lane) {
+__device__ __forceinline__ Lane8 lane_info(const SampleKernelArgs& a, int lane) {
     asm volatile("" : "+v"(lane));
     Lane8 L;
     L.lane = lane;
@@ -487,7 +487,7 @@ __device__ __forceinline__ Lane8 lane_info(const SampleArgs& a, int lane) {
 
 // The whole T-step loop of one role.  Both roles execute the same sequence of workgroup barriers.
 template <bool ROLEA, bool PROF>
-__device__ __forceinline__ void role_loop8x(const SampleArgs& a, char* smem, int w8, const Lane8& L0) {
+__device__ __forceinline__ void role_loop8x(const SampleKernelArgs& a, char* smem, int w8, const Lane8& L0) {
     const float* pvl = reinterpret_cast<const float*>(smem + kPv8Off);
     const f32x4* tokrows = reinterpret_cast<const f32x4*>(smem + kTokRows8Off);
     f32x4* latl = reinterpret_cast<f32x4*>(smem + kLat8Off);
@@ -663,7 +663,7 @@ __device__ __forceinline__ void role_loop8x(const SampleArgs& a, char* smem, int
 }
 
 template <bool PROF>
-__global__ __launch_bounds__(512) void k_sample8x(SampleArgs a) {
+__global__ __launch_bounds__(512) void k_sample8x(SampleKernelArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* pvl = reinterpret_cast<float*>(smem + kPv8Off);
     f32x4* tokrows = reinterpret_cast<f32x4*>(smem + kTokRows8Off);
@@ -716,8 +716,8 @@ hipError_t launch_sample8x(const SampleArgs& a, hipStream_t stream) {
         }
         once.set(dev_);
     }
-    if (a.prof_out) hipLaunchKernelGGL(k_sample8x<true>, dim3(tiles), dim3(512), kSample8xLdsBytes, stream, a);
-    else hipLaunchKernelGGL(k_sample8x<false>, dim3(tiles), dim3(512), kSample8xLdsBytes, stream, a);
+    if (a.prof_out) hipLaunchKernelGGL(k_sample8x<true>, dim3(tiles), dim3(512), kSample8xLdsBytes, stream, static_cast<const SampleKernelArgs&>(a));
+    else hipLaunchKernelGGL(k_sample8x<false>, dim3(tiles), dim3(512), kSample8xLdsBytes, stream, static_cast<const SampleKernelArgs&>(a));
     return hipGetLastError();
 }
 

@@ -364,16 +364,27 @@ int drop_args(float p, uint32_t* thr, float* scale) {
 // ---- the dropout epoch: ONE device word per GPU that every mask-drawing kernel adds into the high half of its Philox counter's offset.  It stays 0 in eager
 // training (the host hands every call a fresh offset); a training step captured as a HIP graph replays with FROZEN host offsets, so the graph ends with
 // k_train_epoch_add and every replay draws fresh masks (amuse_train_epoch_advance; forward and backward of one step see the same value).
+// The sampling kernels' train-mode dropout (k_sampler*.hip) reads the same word: counter word 3 of their masks is 2 + epoch.
 uint32_t* g_train_epoch[64] = {};
+std::mutex g_train_epoch_mu;
 __global__ void k_train_epoch_set(uint32_t* e, uint32_t add, uint32_t set, int do_set) { *e = do_set ? set : *e + add; }
 }  // namespace
+// Created on first use (which must not be inside a stream capture): allocated under a lock (threads of one process may race here), zeroed and
+// the zeroing complete before any kernel of any stream can read it - hipMemset is ordered on the null stream only, which non-blocking
+// streams do not wait for - and published only after all of that succeeded (a failed attempt leaves nothing behind and can be retried).
 uint32_t* train_epoch_ptr() {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return nullptr;
     dev &= 63;
+    std::lock_guard<std::mutex> lock(g_train_epoch_mu);
     if (!g_train_epoch[dev]) {
-        if (hipMalloc((void**)&g_train_epoch[dev], 256) != hipSuccess) return nullptr;
-        if (hipMemset(g_train_epoch[dev], 0, 256) != hipSuccess) return nullptr;
+        uint32_t* p = nullptr;
+        if (hipMalloc((void**)&p, 256) != hipSuccess) return nullptr;
+        if (hipMemset(p, 0, 256) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+            (void)hipFree(p);
+            return nullptr;
+        }
+        g_train_epoch[dev] = p;
     }
     return g_train_epoch[dev];
 }

@@ -153,6 +153,12 @@ class HipEngine:
     def set_clips_per_group(self, g: int):
         _lib.check(self.lib.amuse_set_clips_per_group(self.ctx, int(g)))
 
+    def set_sample_dropout(self, p: float = 0.0, seed: int = 0):
+        """Train-mode sampling (amuse_hip.h amuse_set_sample_dropout): the Denoiser's encoder dropouts live with probability p in sample,
+        denoise_step, profile_sample and the sampling half of diffusion_backward (fp32 / bf16 / fp16); masks keyed by (seed, global clip, step,
+        the library's dropout epoch).  p = 0: eval mode (the default)."""
+        _lib.check(self.lib.amuse_set_sample_dropout(self.ctx, float(p), int(seed) & 0xFFFFFFFFFFFFFFFF))
+
     def set_decode_path(self, path: str = "auto"):
         """decode kernels of the bf16 / fp16 / fp32x modes: "auto" (from 64 clips up the fused per-clip kernel, in fp32x the no-split-K row
         kernel), "staged", "fused", "clip" (the fp32x mode's per-clip decoder; "fused" in the other modes) (amuse_hip.h amuse_set_decode_path)."""

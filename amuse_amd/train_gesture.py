@@ -298,7 +298,10 @@ class GestureTrainer:
                 side = self._side_stream
                 side.wait_stream(torch.cuda.current_stream(self.device))     # the weights of the last optimizer step, the conditions
                 with torch.cuda.stream(side), torch.no_grad():
-                    gen = self.inner_sampler(con, emo, sty, motion.shape[0])
+                    if getattr(self.inner_sampler, "decode_on_trainer_stream", False):
+                        gen = self.inner_sampler.sample_latents(con, emo, sty, motion.shape[0])   # (decoded after the join: the layer kernels' scratch)
+                    else:
+                        gen = self.inner_sampler(con, emo, sty, motion.shape[0])
         # The Denoiser's chain (the no-gradient encode that feeds it, its forward pass and - autograd runs a node's backward pass on its forward pass's stream - its
         # backward pass) shares nothing with the prior's encode -> decode chain but the inputs: 160-row layers, ~1.4 ms of launches that each leave most of the chip
         # idle.  On the GPU it is issued on a stream of its own (scratch lane 1 of the library, train_ops.register_lane) beside the prior's 9,600-row kernels.
@@ -332,6 +335,9 @@ class GestureTrainer:
         if side is not None:                          # join: the losses read `gen`, and the optimizer step must not overtake the sampler's reads of the weights
             torch.cuda.current_stream(self.device).wait_stream(side)
             gen.record_stream(torch.cuda.current_stream(self.device))
+            if getattr(self.inner_sampler, "decode_on_trainer_stream", False):
+                with torch.no_grad():
+                    gen = self.inner_sampler.decode(gen)
         elif self.inner_sampler is not None:          # inverse diffusion (no gradient): the HIP sampler + decode
             with torch.no_grad():
                 gen = self.inner_sampler(con, emo, sty, motion.shape[0])
@@ -368,8 +374,12 @@ class GestureTrainer:
         Returns False - and leaves the trainer eager - where the step is not capturable (CPU, another optimizer, a train-mode inner sampler)."""
         from . import _lib as _libmod
         from . import train_ops
-        if (self.device.type != "cuda" or not isinstance(self.lpdm_opt, train_ops.FlatAdamW) or getattr(self.inner_sampler, "serial", False) or not train_ops.enabled()
-                or getattr(self.inner_sampler, "refresh", 1) != 1):
+        why = ("not a GPU run" if self.device.type != "cuda" else "the optimizer is not the flat AdamW" if not isinstance(self.lpdm_opt, train_ops.FlatAdamW)
+               else "the inner sampler runs serially on the trainer's modules (--inner-sampler train)" if getattr(self.inner_sampler, "serial", False)
+               else "the fused layer kernels are off (AMUSE_TRAIN_FUSED=0)" if not train_ops.enabled()
+               else "the inner sampler refreshes its weights every n > 1 calls" if getattr(self.inner_sampler, "refresh", 1) != 1 else None)
+        if why is not None:
+            print(f"[LPDM-T] training step not captured as a HIP graph: {why}", flush=True)
             return False
         for m in self.model.values():
             m.train()
@@ -529,10 +539,14 @@ class GestureTrainer:
 
 class HipInnerSampler:
     """ldm.diffusion_backward (DDIM-50, ldm.py:117-153) + prior.decode of its result on the HIP kernels, on the trainer's
-    CURRENT weights.  refresh = n: amuse_update_weights every n-th call (1 = every iteration, the reference's semantics)."""
+    CURRENT weights.  refresh = n: amuse_update_weights every n-th call (1 = every iteration, the reference's semantics).
+    dropout = p > 0 (`--inner-sampler train-hip`, AMUSE_TRAIN_INNER=train-hip): the reference's train-mode semantics on the same kernel - the Denoiser's
+    encoder dropouts live in all steps (amuse_set_sample_dropout: masks keyed by the global clip index and the library's dropout epoch, so eager calls
+    draw fresh masks through the clip counter and replays of a captured step through the epoch), and the decode is prior.decode on the trainer's own
+    modules in train mode (the library's dropout-live layer kernels), on the trainer's stream after the join (decode_on_trainer_stream)."""
 
     def __init__(self, trainer_models: Dict[str, nn.Module], device, precision: str = "bf16", refresh: int = 1, seed: int = 2024,
-                 ldm_cfg: Optional[dict] = None, flat: Optional[tuple] = None, rank: int = 0, world: int = 1):
+                 ldm_cfg: Optional[dict] = None, flat: Optional[tuple] = None, rank: int = 0, world: int = 1, dropout: float = 0.0):
         from .engine import HipEngine
         self.models, self.precision, self.refresh, self.seed = trainer_models, precision, max(1, refresh), seed
         self.flat = flat                        # (prior, denoiser) flat fp32 images that ARE the parameters (GestureTrainer.flat_param)
@@ -545,6 +559,10 @@ class HipInnerSampler:
         self.engine.set_decode_path("fused")
         self.what = {"bf16": 2, "fp32x": 8, "fp16": 16}.get(precision, 1)   # AMUSE_UPD_* mask of the streams this sampler runs
         self.on_device = True      # re-pack on the GPU straight from the trainer's flat parameter buffer (False: the host path of amuse_update_weights; tests)
+        self.dropout = float(dropout)
+        self.decode_on_trainer_stream = self.dropout > 0
+        if self.dropout > 0:
+            self.engine.set_sample_dropout(self.dropout, seed=seed + 1)
 
     def _den_state(self):
         return {k: v.detach().cpu().numpy() for k, v in self.models["ldm"].denoiser.state_dict().items()}
@@ -553,6 +571,14 @@ class HipInnerSampler:
         return {k: v.detach().cpu().numpy() for k, v in self.models["prior"].state_dict().items()}
 
     def __call__(self, con, emo, sty, bsz):
+        return self.decode(self.sample_latents(con, emo, sty, bsz))
+
+    def decode(self, lat):
+        if self.dropout > 0:      # train mode: the trainer's MotionPrior.decode, dropout live through the layer kernels
+            return self.models["prior"].decode(lat[None], [SEQ_LEN] * lat.shape[0])
+        return self.engine.vae_decode(lat, None, self.precision, return_feats=True)["feats"]
+
+    def sample_latents(self, con, emo, sty, bsz):
         if self.calls % self.refresh == 0 and self.calls > 0:
             t0 = time.perf_counter()
             if self.on_device:
@@ -572,12 +598,13 @@ class HipInnerSampler:
         if getattr(self, "graph_safe", False):
             # inside a captured training step (GestureTrainer.enable_graph) the host-side clip counter would be frozen: the initial latents come from torch's
             # generator on the device, whose state the graph advances per replay
-            lat = self.engine.sample(con, emo, sty, self.precision, seed=self.seed, x_init=torch.randn(bsz, 128, device=self.engine.device))
-            return self.engine.vae_decode(lat, None, self.precision, return_feats=True)["feats"]
+            # (with dropout live the clip index still keys the masks: rank r takes clips [r bsz, (r + 1) bsz), the epoch word advances per replay)
+            return self.engine.sample(con, emo, sty, self.precision, seed=self.seed, x_init=torch.randn(bsz, 128, device=self.engine.device),
+                                      clip_index0=self.rank * bsz if self.dropout > 0 else 0)
         # initial latents are keyed by a global clip index: rank r draws clips [counter + r * bsz, counter + (r + 1) * bsz)
         lat = self.engine.sample(con, emo, sty, self.precision, seed=self.seed, clip_index0=self.clip_counter + self.rank * bsz)
         self.clip_counter += bsz * self.world
-        return self.engine.vae_decode(lat, None, self.precision, return_feats=True)["feats"]
+        return lat
 
 
 def numpy_denoiser_state(ldm) -> dict:
@@ -678,8 +705,11 @@ def build_trainer(device, rank: int = 0, world: int = 1, process_group=None, see
     tr = GestureTrainer(prior, ldm, device, lr=lr, loss_cfg=loss_cfg, inner_sampler=None, process_group=process_group,
                         world=world, kind=None if kind == "full" else kind, grads_mode=grads_mode, sampler_stream=sampler_stream, optimizer=optimizer, denoiser_stream=denoiser_stream)
     inner = inner or os.environ.get("AMUSE_TRAIN_INNER", "eval")
-    if inner not in ("eval", "train"):
-        raise ValueError(f"inner sampler {inner!r}: 'eval' (the persistent HIP sampler kernel, default) or 'train' (the reference's train-mode semantics, dropout live)")
+    if inner not in ("eval", "train", "train-hip"):
+        raise ValueError(f"inner sampler {inner!r}: 'eval' (the persistent HIP sampler kernel, default), 'train' (the reference's train-mode semantics, dropout "
+                         "live, through the modules) or 'train-hip' (the same semantics on the persistent HIP sampler kernel)")
+    if inner == "train-hip" and torch.device(device).type != "cuda":
+        raise RuntimeError("inner sampler 'train-hip' runs the dropout-live HIP sampler kernel: there is no CPU path (use inner='train' on the CPU)")
     if inner == "train":      # TrainModeInnerSampler: the modules themselves (any device); on the GPU the initial latents are the HIP sampler's draws
         eng = None
         if torch.device(device).type == "cuda":
@@ -691,7 +721,8 @@ def build_trainer(device, rank: int = 0, world: int = 1, process_group=None, see
             raise RuntimeError("the in-loop sampler of train_gesture runs on the HIP kernels: no CPU path (pass use_hip_sampler=False "
                                "to train without the no-gradient gen_feature term)")
         tr.inner_sampler = HipInnerSampler(tr.model, device, refresh=sampler_refresh, ldm_cfg=ldm_cfg,
-                                           flat=(tr.flat_param[:tr.n_prior], tr.flat_param[tr.n_prior:]), rank=rank, world=world)
+                                           flat=(tr.flat_param[:tr.n_prior], tr.flat_param[tr.n_prior:]), rank=rank, world=world,
+                                           dropout=dropout if inner == "train-hip" else 0.0)
     return tr
 
 
@@ -772,7 +803,10 @@ def bench_main(args):
                                       "condition / memory projections and the Denoiser's 160-row layers; attention, LayerNorm / dropout / GELU / bias gradients, AdamW hand-written too; "
                                       "the library links and loads no vendor BLAS (torch's own ops remain only in the loss arithmetic)",
                        "inner_sampler": ("train: the reference's train-mode loop, dropout live (TrainModeInnerSampler)" if getattr(tr.inner_sampler, "serial", False)
-                                         else "eval: the persistent HIP sampler kernel (dropout off - the reference's loop runs in train mode; opt in with AMUSE_TRAIN_INNER=train)")},
+                                         else "train-hip: the persistent HIP sampler kernel with the Denoiser's dropouts live + the train-mode prior.decode "
+                                              "(the reference's semantics)" if getattr(tr.inner_sampler, "dropout", 0) > 0
+                                         else "eval: the persistent HIP sampler kernel (dropout off - the reference's loop runs in train mode; opt in with "
+                                              "AMUSE_TRAIN_INNER=train-hip, or =train for the module loop)")},
             "samples_per_s": round(its * bsz * world, 1),
             "allreduce_ms": round(float(np.median(ar)), 3) if ar else None,
             "hip_weight_repack_ms": round(float(np.median(sync)), 3) if sync else None,
@@ -801,9 +835,10 @@ def main(argv=None):
     ap.add_argument("--lr", type=float, default=1e-4, help="TRAIN_PARAM.latent_diffusion.lr_base (AdamW, trainer.py:181-184)")
     ap.add_argument("--kind", default=None, choices=["full", "emotion", "identity", "baseline"],
                     help="ablation variant (default: derived from the --cache id like trainer.py:396-401; synthetic data: full)")
-    ap.add_argument("--inner-sampler", default=None, choices=["eval", "train"],
+    ap.add_argument("--inner-sampler", default=None, choices=["eval", "train", "train-hip"],
                     help="the no-gradient DDIM-50 + decode of every iteration: eval (default) = the persistent HIP sampler kernel, dropout off; train = the "
-                         "reference's semantics (ldm.py:117-153 under model.train(): every dropout live) through the trainer's own modules, ~10 x slower")
+                         "reference's semantics (ldm.py:117-153 under model.train(): every dropout live) through the trainer's own modules, ~10 x slower; "
+                         "train-hip = the same semantics on the persistent HIP sampler kernel (dropout-live instantiation) + the train-mode decode")
     ap.add_argument("--no-graph", action="store_true", help="keep the iteration eager (default on the GPU: captured as two HIP graphs after three eager iterations)")
     ap.add_argument("--ldm-cfg", default=None, help="JSON file: configs/<arch>.json merged with diff_o.yaml (losses, schedulers); default: the shipped values")
     args = ap.parse_args(argv)
@@ -845,10 +880,14 @@ def main(argv=None):
             print("[LPDM-T] inner sampler: none (CPU run: the no-gradient gen_feature term is off)", flush=True)
         elif getattr(tr.inner_sampler, "serial", False):
             print("[LPDM-T] inner sampler: train - the reference's semantics (ldm.py:117-153 and prior.decode under model.train(): every dropout live), on the trainer's own modules", flush=True)
+        elif getattr(tr.inner_sampler, "dropout", 0) > 0:
+            print(f"[LPDM-T] inner sampler: train-hip - the reference's semantics (every dropout live, p = {tr.inner_sampler.dropout:g}) on the persistent HIP sampler "
+                  "kernel, then prior.decode on the trainer's modules in train mode", flush=True)
         else:
             print("[LPDM-T] inner sampler: eval - DDIM-50 + decode on the persistent HIP sampler kernel with dropout OFF.  DEVIATION from the reference, whose loop runs under "
                   "model.train() with every dropout live (scripts/trainer.py:357-358,413-415): the gen_feature loss term sees un-dropped samples.  "
-                  "--inner-sampler train (or AMUSE_TRAIN_INNER=train) selects the reference's semantics, ~10 x slower.", flush=True)
+                  "--inner-sampler train-hip (or AMUSE_TRAIN_INNER=train-hip) selects the reference's semantics on the HIP kernel, --inner-sampler train "
+                  "through the modules (~10 x slower).", flush=True)
     if args.cache:
         from .dataload import LatentDiffusionCache, make_loader
         loader = make_loader(LatentDiffusionCache.open(args.cache), args.batch, rank=rank, world=world, seed=args.seed)

@@ -36,8 +36,9 @@ extern "C" {
  *   environment  AMUSE_SHARE_GPU=1     amuse_amd/main.py: every --gpus rank stays on --device (two-process tests on a one-GPU box)
  *   environment  AMUSE_BENCH_SHARE_GPU=1   bench.py: --gpus N ranks on one GPU over gloo (the two-rank bench tests on a one-GPU box)
  *   environment  AMUSE_RUN_STAMP, AMUSE_MANIFEST_DIR   launcher -> rank hand-over inside amuse_amd/main.py (not set by users)
- *   environment  AMUSE_TRAIN_FUSED=0, AMUSE_TRAIN_VALIDATE=1, AMUSE_TRAIN_INNER=train   train_gesture: eager layers / torch's distribution checks / the reference's
- *                                      train-mode inner sampler (amuse_amd/train_ops.py, train_gesture.py)
+ *   environment  AMUSE_TRAIN_FUSED=0, AMUSE_TRAIN_VALIDATE=1   train_gesture: eager layers / torch's distribution checks (amuse_amd/train_ops.py)
+ *   environment  AMUSE_TRAIN_INNER=eval|train|train-hip   train_gesture's in-loop sampler: the persistent kernel in eval mode (default) / the reference's
+ *                                      train-mode module loop / the persistent kernel with the dropouts live (amuse_set_sample_dropout) + the train-mode decode
  * The ~30 environment switches and 51 -DAMUSE_* macros of rounds 1-5 (A/B residue) were retired in round 6: tools/probes/retired_switches/. */
 #define AMUSE_ABI_VERSION 5   /* 5: amuse_plan / amuse_debug_last_plan (the launch plan); the process-wide environment overrides of kernel choices are gone;
                                  4: amuse_train_* (training-step glue kernels);
@@ -264,6 +265,24 @@ int amuse_profile_sample(amuse_ctx* ctx, const float* con, const float* emo, con
  * Results are bitwise reproducible across launches / shards that use the same value and start at multiples of it
  * (a clip's slot inside its tile decides the rounding of its attention sums); amuse_amd/shard.py applies that rule. */
 int amuse_set_clips_per_group(amuse_ctx* ctx, int g);
+
+/* Train-mode sampling: the Denoiser's encoder dropouts live in amuse_sample, amuse_denoise_step, amuse_profile_sample and the sampling half of
+ * amuse_diffusion_backward (AMUSE_ARCH_ENC; AMUSE_PREC_F32 / _BF16 / _F16), as in the reference's training loop, which samples with the networks in
+ * train() mode (scripts/trainer.py).  p = 0 (the default) = eval mode, the kernels of before.  p NaN, < 0 or >= 1: AMUSE_EINVAL.  With p > 0 a sample or
+ * step call in AMUSE_PREC_F32X or on another arch returns AMUSE_ESTATE and launches nothing.  Decode, encode and amuse_diffusion_forward stay in eval
+ * semantics.
+ * Mask contract (tests/test_gpu_sample_dropout.py restates it).  Dropout sites of encoder layer l = 0..8 in execution order (input blocks 0-3, middle,
+ * output blocks 0-3), as TransformerEncoderLayer.forward_post (utils/cross_attention.py):
+ *   site s = 0  softmax probabilities before . V        element e = (h S + q) S + k   (h = head 0..3, q / k = query / key token, S = 3..5 tokens)
+ *   site s = 1  dropout1 on out_proj's output (+ bias)  e = tok 128 + f
+ *   site s = 2  the FFN's dropout(gelu(linear1))        e = tok 512 + f
+ *   site s = 3  dropout2 on linear2's output (+ bias)   e = tok 128 + f
+ * None on the positional encoding, the time / condition projections, the skip linears or the final LayerNorm (the reference has none there).
+ * Element e uses draw e % 4 of Philox4x32-10 with key = seed (lo, hi) and counter = (clip, step, ((l 4 + s) << 16) | (e / 4), 2 + epoch): clip = the
+ * global clip index (clip_index0 + b; b for amuse_denoise_step), step = the loop index i (0 for amuse_denoise_step), epoch = the training dropout
+ * epoch word (amuse_train_epoch_advance / _set: a captured step draws fresh masks per replay).  Word 3 starts at 2: no collision with the noise
+ * streams 0 and 1.  Keep <=> (draw >> 8) >= thr, thr = (uint32)(p 2^24); kept values are multiplied by 1 / (1 - p) (the amuse_train_* convention). */
+int amuse_set_sample_dropout(amuse_ctx* ctx, float p, uint64_t seed);
 
 /* Which kernels amuse_vae_decode (and amuse_diffusion_backward), amuse_vae_encode and the pose-space Denoiser's step use.  Every mode but fp32 has more
  * than one kernel family for MotionPrior.decode (vae.py:216-278); they compute the same function and differ in summation order only (fp32x: 1.5e-6 on

@@ -27,7 +27,7 @@ EXPORTS = [
     "amuse_debug_gemm",
     "amuse_debug_tile", "amuse_debug_f16_split", "amuse_debug_set_decode_tap",
     "amuse_create_arch", "amuse_denoiser_param_count", "amuse_arch", "amuse_state_dim", "amuse_denoise_step_pose", "amuse_feats_to_smplx",
-    "amuse_debug_set_ablation", "amuse_set_sample_dropout",
+    "amuse_debug_set_ablation", "amuse_set_sample_dropout", "amuse_set_decode_dropout",
     "amuse_train_ws_floats", "amuse_train_set_lane", "amuse_train_ln_fwd", "amuse_train_ln_bwd", "amuse_train_bias_gelu_drop_fwd", "amuse_train_bias_gelu_drop_bwd", "amuse_train_colsum",
     "amuse_train_layer_fwd", "amuse_train_layer_bwd", "amuse_train_linear_fwd", "amuse_train_linear_bwd", "amuse_train_adamw", "amuse_train_adamw_dev", "amuse_train_epoch_advance", "amuse_train_epoch_set", "amuse_train_attn_fwd", "amuse_train_attn_bwd",
 ]
@@ -115,6 +115,8 @@ def load() -> C.CDLL:
     lib.amuse_set_decode_path.argtypes = [vp, C.c_int]
     lib.amuse_set_sample_dropout.argtypes = [vp, C.c_float, u64]
     lib.amuse_set_sample_dropout.restype = C.c_int
+    lib.amuse_set_decode_dropout.argtypes = [vp, C.c_float, u64, u64]
+    lib.amuse_set_decode_dropout.restype = C.c_int
     lib.amuse_profile_sample.argtypes = [vp, fp, fp, fp, C.c_int, C.c_int, C.c_int, fp, vp]
     lib.amuse_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, ip, ip, ip, ip]
     lib.amuse_debug_last_plan.argtypes = [vp, ip, ip, ip, ip]

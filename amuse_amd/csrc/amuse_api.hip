@@ -23,7 +23,7 @@ __attribute__((visibility("hidden"))) int amuse_fail_msg(int code, const char* m
 namespace {
 constexpr int kVaeChunk = 512;
 constexpr int kEncRows = kFrames + 2;  // encoder sequence: 2 distribution tokens + 300 frames
-constexpr size_t kVaeFloatsPerClip = (size_t)kEncRows * kD * (1 + 3 + 1 + 4) + kLayers * kD;  // x, qkv, o, skip, ca | stats
+constexpr size_t kVaeFloatsPerClip = (size_t)kEncRows * kD * (1 + 3 + 1 + 4) + 4 * kLayers * kD;  // x, qkv, o, skip, ca (train-mode decode: its four per-head partials) | stats
 
 constexpr int kUpdBit[4] = {AMUSE_UPD_F32, AMUSE_UPD_BF16, AMUSE_UPD_F32X, AMUSE_UPD_F16};   // per PREC_* index
 
@@ -711,6 +711,16 @@ int amuse_set_sample_dropout(amuse_ctx* c, float p, uint64_t seed) {
     return 0;
 }
 
+int amuse_set_decode_dropout(amuse_ctx* c, float p, uint64_t seed, uint64_t clip_index0) {
+    if (!(p >= 0.f) || p >= 1.f) return fail(AMUSE_EINVAL, "dropout probability %g outside [0, 1)", (double)p);
+    if (!c) return fail(AMUSE_EINVAL, "ctx is NULL");
+    c->dec_drop_thr = (uint32_t)(p * 16777216.0f);   // k_train.hip drop_args
+    c->dec_drop_scale = 1.0f / (1.0f - p);
+    c->dec_drop_seed = seed;
+    c->dec_drop_clip0 = clip_index0;
+    return 0;
+}
+
 int amuse_set_decode_path(amuse_ctx* c, int path) {
     if (!c) return fail(AMUSE_EINVAL, "ctx is NULL");
     if (path != AMUSE_DECODE_AUTO && path != AMUSE_DECODE_STAGED && path != AMUSE_DECODE_FUSED && path != AMUSE_DECODE_CLIP)
@@ -912,18 +922,31 @@ hipError_t c1_consumed(amuse_ctx* c, int i, hipStream_t st) {
 }
 }  // namespace
 
-int amuse_vae_decode(amuse_ctx* c, const float* z, const int* lengths, int B, int precision, int quat_mode,
-                     float* feats_out, float* poses_out, float* trans_out, void* stream) {
+// train-mode decode (amuse_set_decode_dropout p > 0) is refused where no kernel draws the masks, so that dropout is never silently dropped
+static int decode_dropout_refused(const amuse_ctx* c, int precision) {
+    if (c->dec_drop_thr == 0) return 0;
+    if (!c->has_prior) return fail(AMUSE_ESTATE, "this context was created without MotionPrior weights");
+    if (precision == AMUSE_PREC_F32X)
+        return fail(AMUSE_ESTATE, "train-mode decode (amuse_set_decode_dropout p > 0) has no fp32x kernel: use fp32, bf16 or fp16");
+    return 0;
+}
+
+// amuse_vae_decode; clip0 = global index of clip 0 (the dropout masks of train-mode decode; unused in eval)
+static int vae_decode(amuse_ctx* c, const float* z, const int* lengths, int B, int precision, int quat_mode,
+                      float* feats_out, float* poses_out, float* trans_out, void* stream, uint64_t clip0) {
     if (!c) return fail(AMUSE_EINVAL, "ctx is NULL");
     if (!c->has_prior) return fail(AMUSE_ESTATE, "this context was created without MotionPrior weights");
     if (!z) return fail(AMUSE_EINVAL, "z is NULL");
     if (B < 1) return fail(AMUSE_EINVAL, "B must be >= 1, got %d", B);
     if (precision < AMUSE_PREC_F32 || precision > AMUSE_PREC_F16) return fail(AMUSE_EINVAL, "bad precision %d", precision);
     if (quat_mode != AMUSE_QUAT_P3D && quat_mode != AMUSE_QUAT_LEGACY) return fail(AMUSE_EINVAL, "bad quat_mode %d", quat_mode);
+    if (int e = decode_dropout_refused(c, precision)) return e;
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream;
     if (int e = stage_lengths(c, lengths, B, st)) return e;
-    const int path = decode_path_of(c, precision, B);
+    // train-mode decode runs on the staged family at every clip count, whatever the pin says: the fused kernels and block 0's hoisted constant are eval-only
+    const bool drop = c->dec_drop_thr > 0;
+    const int path = drop ? (c->last_plan[1] = AMUSE_DECODE_STAGED) : decode_path_of(c, precision, B);
     if (is_op16(precision) && path != AMUSE_DECODE_STAGED) {
         // bf16 / fp16 throughput modes from kFusedMinClips clips up: one persistent workgroup per clip (k_vae_fused.hip)
         const int chunk = B < kVaeFusedChunk ? B : kVaeFusedChunk;
@@ -994,9 +1017,30 @@ int amuse_vae_decode(amuse_ctx* c, const float* z, const int* lengths, int B, in
         ra.poses_out = poses_out ? poses_out + (size_t)b0 * kFrames * kJoints * 3 : nullptr;
         ra.trans_out = trans_out ? trans_out + (size_t)b0 * kFrames * 3 : nullptr;
         ra.B = nb; ra.quat_mode = quat_mode; ra.tiles = 19;
-        HIP_TRY(launch_vae_ca(z + (size_t)b0 * kD, c->vae_wv_t, c->vae_bv, c->vae_wo_t, c->vae_bo, ca, nb, st));
         VaeAttnArgs aa{};
         aa.q = ra.q; aa.k = ra.k; aa.v = ra.v; aa.lengths = ra.lengths; aa.o = attn_o; aa.B = nb; aa.q_tiles = 19;
+        if (drop) {
+            // the six dropout sites of every block live: per-head cross-attention partials, the dropout instantiations of the row and attention kernels;
+            // clip b of this chunk is global clip clip0 + b0 + b
+            HIP_TRY(launch_vae_ca(z + (size_t)b0 * kD, c->vae_wv_t, c->vae_bv, c->vae_wo_t, nullptr, ca, nb, st));   // (no bias: the per-head form)
+            VaeDropArgs da{};
+            da.drop_thr = c->dec_drop_thr; da.drop_scale = c->dec_drop_scale; da.drop_seed = c->dec_drop_seed;
+            da.drop_clip0 = (uint32_t)(clip0 + (uint64_t)b0);
+            VaeRowsDropArgs rd{};
+            static_cast<VaeRowsArgs&>(rd) = ra;
+            rd.drop = da; rd.ca_bias = c->vae_bo;
+            VaeAttnDropArgs ad{};
+            static_cast<VaeAttnArgs&>(ad) = aa;
+            ad.drop = da;
+            for (int stage = 0; stage < kVaeStages; ++stage) {
+                rd.stage = stage;
+                ad.layer = stage;
+                HIP_TRY(launch_vae_rows(rd, precision, VAE_MODE_DEC_DROP, st));
+                if (stage < kLayers) HIP_TRY(launch_vae_attn(ad, precision, VAE_MODE_DEC_DROP, st));
+            }
+            continue;
+        }
+        HIP_TRY(launch_vae_ca(z + (size_t)b0 * kD, c->vae_wv_t, c->vae_bv, c->vae_wo_t, c->vae_bo, ca, nb, st));
         // fp32x: the row stages without split-K (k_vae_rows8.hip; FUSED) or the split-K row kernel k_vae_rows<f16x2> (STAGED), chosen from the clips of the CALL (not of the
         // chunk: a job's last chunk must not change kernels) or as amuse_set_decode_path pins it, so that a job-level choice (amuse_plan) keeps fp32x shards bitwise too
         const bool rows8 = precision == PREC_F16X2 && path != AMUSE_DECODE_STAGED;
@@ -1059,6 +1103,11 @@ int amuse_vae_decode(amuse_ctx* c, const float* z, const int* lengths, int B, in
         }
     }
     return 0;
+}
+
+int amuse_vae_decode(amuse_ctx* c, const float* z, const int* lengths, int B, int precision, int quat_mode,
+                     float* feats_out, float* poses_out, float* trans_out, void* stream) {
+    return vae_decode(c, z, lengths, B, precision, quat_mode, feats_out, poses_out, trans_out, stream, c ? c->dec_drop_clip0 : 0);
 }
 
 int amuse_vae_encode(amuse_ctx* c, const float* feats, const int* lengths, int B, int precision, const float* eps,
@@ -1147,6 +1196,8 @@ int amuse_diffusion_backward(amuse_ctx* c, const float* con, const float* emo, c
     if (!c) return fail(AMUSE_EINVAL, "ctx is NULL");
     if (!poses_out || !trans_out) return fail(AMUSE_EINVAL, "poses_out / trans_out is NULL");
     if (B < 1) return fail(AMUSE_EINVAL, "B must be >= 1, got %d", B);
+    if (!(c->arch & 2))   // (a latent-space context decodes: refuse a train-mode decode that cannot run before anything is launched)
+        if (int e = decode_dropout_refused(c, precision)) return e;
     float* lat = latents_out;
     if (!lat) {
         HIP_TRY(hipSetDevice(c->device));
@@ -1157,7 +1208,8 @@ int amuse_diffusion_backward(amuse_ctx* c, const float* con, const float* emo, c
         return e;
     // diffusion_only: the sampled state IS the feature sequence - no decode (infer_ldm.py:165), only the conversion of :168-173
     if (c->arch & 2) return amuse_feats_to_smplx(c, lat, B, quat_mode, poses_out, trans_out, stream);
-    return amuse_vae_decode(c, lat, nullptr, B, precision, quat_mode, nullptr, poses_out, trans_out, stream);
+    // (train-mode decode: the masks follow the sampler's clips - this call's clip_index0, not the setter's)
+    return vae_decode(c, lat, nullptr, B, precision, quat_mode, nullptr, poses_out, trans_out, stream, clip_index0);
 }
 
 int amuse_counter_normal(amuse_ctx* c, uint64_t seed, uint64_t clip_index0, int B, int step, int rng_stream,

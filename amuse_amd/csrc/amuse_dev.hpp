@@ -558,6 +558,15 @@ __device__ __forceinline__ f32x4 sdrop_apply4(f32x4 v, uint32_t bits, float scal
                  (bits & 8u) ? v[3] * scale : 0.f};
 }
 
+// ---- train-mode decode dropout (amuse_hip.h amuse_set_decode_dropout): keep bits of elements 4 e4 .. 4 e4 + 3 of dropout site ls = 8 layer + site of
+// MotionPrior.decode; element e uses draw e % 4 of Philox4x32-10(key = seed, counter = (clip, 0x80000000 | ls, e / 4, 2 + epoch)), keep <=> draw >> 8 >= thr.
+// Bit 31 of word 1 keeps these streams clear of the sampler's (there word 1 is the step).  Bit m of the result = element 4 e4 + m kept.
+__device__ __forceinline__ uint32_t ddrop_bits4(uint64_t seed, uint32_t clip, uint32_t ls, uint32_t e4, uint32_t epoch2, uint32_t thr) {
+    uint32_t c[4] = {clip, 0x80000000u | ls, e4, epoch2};
+    philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+    return ((c[0] >> 8) >= thr ? 1u : 0u) | ((c[1] >> 8) >= thr ? 2u : 0u) | ((c[2] >> 8) >= thr ? 4u : 0u) | ((c[3] >> 8) >= thr ? 8u : 0u);
+}
+
 // ------------------------------------------------------------------------------------------------
 // Split-K combine as reduce-scatter + (LayerNorm) + all-gather.  exchange_sum makes every wave read all
 // partials and then repeat the same residual + LayerNorm on the full [16 x 128] tile - 4x redundant VALU and

@@ -335,6 +335,10 @@ struct amuse_ctx {
     uint32_t drop_thr = 0;
     float drop_scale = 1.f;
     uint64_t drop_seed = 0;
+    // train-mode decode (amuse_set_decode_dropout): dec_drop_thr = p 2^24, 0 = eval; dec_drop_clip0 = global index of clip 0 of an amuse_vae_decode call
+    uint32_t dec_drop_thr = 0;
+    float dec_drop_scale = 1.f;
+    uint64_t dec_drop_seed = 0, dec_drop_clip0 = 0;
     // denoiser
     uint4* den_w[3] = {nullptr, nullptr, nullptr};   // 4-wave kernel streams: fp32 | bf16 | split-fp16 (fp32x)
     uint32_t den_wave_units[3] = {0, 0, 0};

@@ -182,8 +182,23 @@ struct VaeRowsArgs {
     uint64_t seed, clip0;
     int step;
 };
-// mode: which network the stages run (k_vae.hip M_*)
-constexpr int VAE_MODE_DEC = 0, VAE_MODE_ENC = 1, VAE_MODE_DEN_E = 2, VAE_MODE_DEN_D = 3;
+// Train-mode decode (amuse_set_decode_dropout): what the dropout instantiations of the M_DEC kernels take BEHIND the eval arguments (the eval kernels keep
+// taking the unchanged VaeRowsArgs / VaeAttnArgs slice, so their code does not move).  The launchers set drop_epoch themselves (train_epoch_ptr).
+struct VaeDropArgs {
+    uint32_t drop_thr;           // p 2^24 (keep <=> draw >> 8 >= drop_thr); 0 = eval
+    float drop_scale;            // 1 / (1 - p)
+    uint64_t drop_seed;          // Philox key of the masks
+    const uint32_t* drop_epoch;  // the training dropout epoch word (counter word 3 = 2 + epoch)
+    uint32_t drop_clip0;         // global index of the launch's clip 0 (truncated to 32 bits, as in the sampler)
+};
+// rows: `ca` is [B][9][4][128], the per-head partial vectors of the cross-attention (launch_vae_ca with bo = NULL), not the eval constant
+struct VaeRowsDropArgs : VaeRowsArgs {
+    VaeDropArgs drop;
+    const float* ca_bias;        // [9][128] multihead_attn.out_proj.bias (the eval constant has it folded in)
+};
+// mode: which network the stages run (k_vae.hip M_*).  VAE_MODE_DEC_DROP = MotionPrior.decode with the dropout sites of every block live (fp32, bf16, fp16): the
+// argument IS a VaeRowsDropArgs (launch_vae_rows) / a VaeAttnDropArgs (launch_vae_attn) handed over by its base, with drop.drop_thr > 0
+constexpr int VAE_MODE_DEC = 0, VAE_MODE_ENC = 1, VAE_MODE_DEN_E = 2, VAE_MODE_DEN_D = 3, VAE_MODE_DEC_DROP = 4;
 hipError_t launch_vae_rows(const VaeRowsArgs& a, int precision, int mode, hipStream_t stream);
 // fp32x row stages without split-K (k_vae_rows8.hip): decode (every stage) and encode (stages 1..9; mode = VAE_MODE_DEC / _ENC below)
 hipError_t launch_vae_rows8x(const VaeRowsArgs& a, hipStream_t stream, int mode = 0);
@@ -196,6 +211,8 @@ struct VaeAttnArgs {
     int q_tiles;                                      // query tiles to produce: 19, or 1 (last encoder block)
     int S;                                            // VAE_MODE_DEN_E: rows per clip (302..304)
 };
+// VAE_MODE_DEC_DROP: the decoder's self-attention with the probabilities dropped in front of P . V (site 0); one kernel per operand format at every clip count
+struct VaeAttnDropArgs : VaeAttnArgs { int layer; VaeDropArgs drop; };
 hipError_t launch_vae_attn(const VaeAttnArgs& a, int precision, int mode, hipStream_t stream);
 // ---------------------------------------------------------------- fused decode (k_vae_fused.hip): one workgroup per clip
 constexpr int kVaeFusedStageUnits = 16;   // the weight stream is consumed in 16 KiB stages (LDS-DMA ring of three)
@@ -303,6 +320,8 @@ hipError_t launch_vae_latent(const float* stats, const float* eps, float* mu, fl
                              hipStream_t stream);
 
 // ca[b][blk][:] = out_proj(v_proj(z[b]))   (cross_attention.py:331-336 with a 1-token memory)
+// bo = NULL (train-mode decode): ca is [B][9][4][128] and gets ca[b][blk][h][:] = W_o[:, 32 h : 32 h + 32] v_h, the four per-head partial vectors (no bias) that
+// the row kernel combines with its row's four keep bits of the cross-attention probabilities
 hipError_t launch_vae_ca(const float* z, const float* wv_t /*[9][128][128]*/, const float* bv /*[9][128]*/,
                          const float* wo_t, const float* bo, float* ca, int B, hipStream_t stream);
 

@@ -108,6 +108,30 @@ __global__ __launch_bounds__(128) void k_vae_ca(const float* __restrict__ z, con
     ca[((size_t)b * kLayers + blk) * kD + j] = o + bo[blk * kD + j];
 }
 
+// train-mode decode (amuse_set_decode_dropout): the cross-attention's probabilities (softmax over one key == 1) are dropped per (query, head), so the
+// layer's output is no per-clip constant: query q gets b_o + sum_h m[h, q] / (1 - p) * (W_o[:, 32 h : 32 h + 32] v_h).  This kernel emits the four
+// per-head vectors cah[b][blk][h][:] (no bias); k_vae_rows combines them with its row's four keep bits.  grid = (9, B), block = 128.
+__global__ __launch_bounds__(128) void k_vae_ca_heads(const float* __restrict__ z, const float* __restrict__ wv_t,
+                                                      const float* __restrict__ bv, const float* __restrict__ wo_t,
+                                                      float* __restrict__ cah) {
+    __shared__ float zs[kD];
+    __shared__ float vs[kD];
+    const int j = threadIdx.x, blk = blockIdx.x, b = blockIdx.y;
+    zs[j] = z[(size_t)b * kD + j];
+    __syncthreads();
+    float acc = 0.f;
+    const float* wv = wv_t + (size_t)blk * kD * kD;
+    for (int k = 0; k < kD; ++k) acc = fmaf(zs[k], wv[k * kD + j], acc);
+    vs[j] = acc + bv[blk * kD + j];
+    __syncthreads();
+    const float* wo = wo_t + (size_t)blk * kD * kD;
+    for (int h = 0; h < kHeads; ++h) {
+        float o = 0.f;
+        for (int k = 32 * h; k < 32 * h + 32; ++k) o = fmaf(vs[k], wo[k * kD + j], o);
+        cah[(((size_t)b * kLayers + blk) * kHeads + h) * kD + j] = o;
+    }
+}
+
 // SMPL-X axis-angle + translation -> the prior's 333 motion features (infer_ldm.py:459-464):
 // axis_angle_to_matrix (= axis_angle_to_quaternion -> quaternion_to_matrix, rotation_conversions.py:425-478, 41-71)
 // then matrix_to_rotation_6d = the first two matrix rows (rotation_conversions.py:536-551).  One thread per (row, joint).
@@ -197,7 +221,8 @@ hipError_t launch_feats_to_smplx(const float* feats, size_t nrows, int quat_mode
 
 hipError_t launch_vae_ca(const float* z, const float* wv_t, const float* bv, const float* wo_t, const float* bo,
                          float* ca, int B, hipStream_t stream) {
-    hipLaunchKernelGGL(k_vae_ca, dim3(kLayers, B), dim3(128), 0, stream, z, wv_t, bv, wo_t, bo, ca);
+    if (!bo) hipLaunchKernelGGL(k_vae_ca_heads, dim3(kLayers, B), dim3(128), 0, stream, z, wv_t, bv, wo_t, ca);   // train-mode decode: per-head partials
+    else hipLaunchKernelGGL(k_vae_ca, dim3(kLayers, B), dim3(128), 0, stream, z, wv_t, bv, wo_t, bo, ca);
     return hipGetLastError();
 }
 

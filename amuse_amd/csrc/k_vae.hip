@@ -43,8 +43,16 @@ constexpr int M_DEC = 0, M_ENC = 1, M_DEN_E = 2, M_DEN_D = 3;
 constexpr bool mode_den(int m) { return m == M_DEN_E || m == M_DEN_D; }
 constexpr bool mode_enc_layers(int m) { return m == M_ENC || m == M_DEN_E; }   // two norms per block, no cross-attention
 
-template <int PREC, int MODE>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_vae_rows(VaeRowsArgs a) {
+// DROP (train-mode decode, amuse_set_decode_dropout; M_DEC only, ArgsT = VaeRowsDropArgs): the five dropout sites of forward_post that live in the row stages,
+// masks drawn in registers at the point of use (amuse_dev.hpp ddrop_bits4; site s of block blk is stream 8 blk + s):
+//   1 dropout1 on out_proj + bias, 3 dropout2 on the cross-attention output, 5 dropout3 on linear2 + bias: element frame 128 + feature;
+//   2 the cross-attention's probabilities (softmax over ONE key = 1, so 0 or 1 / (1 - p) per (head, frame)): element head 300 + frame - `ca` then holds the four
+//     per-head partial vectors (k_vae_ca_heads) and the row combines them with its four keep bits;
+//   4 the FFN's dropout(gelu(linear1)): element frame 512 + hidden feature.
+// Site 0 (the self-attention probabilities) is k_vae_attn's.  The eval instantiations take the unchanged VaeRowsArgs, so their code does not move.
+template <int PREC, int MODE, bool DROP = false, typename ArgsT = VaeRowsArgs>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_vae_rows(ArgsT a) {
+    static_assert(!DROP || MODE == M_DEC, "dropout exists for MotionPrior.decode only");
     constexpr bool ENC = MODE == M_ENC;
     constexpr bool DEN = mode_den(MODE);
     constexpr bool EMB = ENC || DEN;               // stage 0 embeds 333 input features
@@ -76,6 +84,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     bool skipped = false;
     constexpr bool FAST = is_op16(PREC);
     f32x4 x[kTiles];
+    [[maybe_unused]] uint64_t dseed = 0;
+    [[maybe_unused]] uint32_t dclip = 0, depoch2 = 0, dthr = 0;
+    [[maybe_unused]] float dscale = 1.f;
+    if constexpr (DROP) {
+        dseed = a.drop.drop_seed; dclip = a.drop.drop_clip0 + (uint32_t)b; depoch2 = 2u + *a.drop.drop_epoch;
+        dthr = a.drop.drop_thr; dscale = a.drop.drop_scale;
+    }
+    // keep bits of this wave's two combine tiles (features 16 (2 wave + i) + 4 g + m of row `frame`) at a 128-wide site: bits 0..3 tile 0, 4..7 tile 1
+    [[maybe_unused]] auto row_bits = [&](uint32_t ls) -> uint32_t {
+        const uint32_t e4 = (uint32_t)frame * 32u + 8u * (uint32_t)wave + (uint32_t)g;
+        return ddrop_bits4(dseed, dclip, ls, e4, depoch2, dthr) | (ddrop_bits4(dseed, dclip, ls, e4 + 4u, depoch2, dthr) << 4);
+    };
 
     constexpr int kEmbK = 22;  // 333 input features padded to 22 k-tiles (zero weights / zero operands beyond 333)
     constexpr int P_E = EMB ? gemm_units(PREC, 2, kEmbK) % kVR : 0;  // in_proj phase of stage 0
@@ -147,6 +167,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
         for (int t = 0; t < kTiles; ++t) part[t] = splat4(0.f);
         gemm_ring<PREC, kTiles, 2, false, kVR, P_O>(part, o, rg);
+        if constexpr (DROP)
+            combine_rs<true, FAST, 0, 1, 0, true>(part, x, true, pv + PV_OUT_B, pv + PV_LN1_W, pv + PV_LN1_B, comb, wave, lane, nullptr,
+                                                  row_bits(8u * blk + 1u), dscale);
+        else
         combine_rs<true, FAST>(part, x, true, pv + PV_OUT_B, pv + PV_LN1_W, pv + PV_LN1_B, comb, wave, lane);
         if constexpr (MODE == M_DEN_D) {
             // cross-attention of the tile's rows onto the clip's 2..4 memory tokens (cross_attention.py:337-343): q of head
@@ -202,6 +226,25 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             for (int t = 0; t < kTiles; ++t) part[t] = splat4(0.f);
             gemm_ring<PREC, kTiles, 2, false, kVR, P_CO>(part, a2, rg);
             combine_rs<true, FAST>(part, x, true, pv + PVX_CO_B, pv + PV_LN2_W, pv + PV_LN2_B, comb, wave, lane);
+        } else if constexpr (MODE == M_DEC && DROP) {
+            // cross-attention onto the single latent token with its probabilities dropped (site 2): b_o + sum_h keep[h][frame] / (1 - p) . cah[h], then
+            // dropout2 (site 3) on that vector; residual + norm2.  Every wave holds the whole row, so every wave draws the row's bits.
+            const float* cah = a.ca + ((size_t)b * kLayers + blk) * kHeads * kD;
+            const float* cb = a.ca_bias + blk * kD;
+            float mh[kHeads];
+#pragma unroll
+            for (int h = 0; h < kHeads; ++h) {
+                const uint32_t e = (uint32_t)h * kFrames + (uint32_t)frame;
+                mh[h] = ((ddrop_bits4(dseed, dclip, 8u * blk + 2u, e >> 2, depoch2, dthr) >> (e & 3u)) & 1u) ? dscale : 0.f;
+            }
+#pragma unroll
+            for (int t = 0; t < kTiles; ++t) {
+                f32x4 y = ld4(cb + 16 * t + 4 * g);
+#pragma unroll
+                for (int h = 0; h < kHeads; ++h) y += ld4(cah + h * kD + 16 * t + 4 * g) * mh[h];
+                x[t] = x[t] + sdrop_apply4(y, ddrop_bits4(dseed, dclip, 8u * blk + 3u, (uint32_t)frame * 32u + 4u * t + g, depoch2, dthr), dscale);
+            }
+            layer_norm_rows<is_op16(PREC)>(x, pv + PV_LN2_W, pv + PV_LN2_B, g);
         } else if constexpr (MODE == M_DEC) {
             // cross-attention onto the single latent token == per-clip constant; residual + norm2
             const float* ca = a.ca + ((size_t)b * kLayers + blk) * kD;
@@ -224,10 +267,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
                 for (int m = 0; m < 4; ++m) hid[t][m] = gelu_erf(hid[t][m]);
             }
+            if constexpr (DROP)   // site 4: hidden features 16 (8 wave + t) + 4 g + m of row `frame`
+                hid[t] = sdrop_apply4(hid[t], ddrop_bits4(dseed, dclip, 8u * blk + 4u, (uint32_t)frame * 128u + 4u * (kTiles * wave + t) + g, depoch2, dthr), dscale);
         }
 #pragma unroll
         for (int t = 0; t < kTiles; ++t) part[t] = splat4(0.f);
         gemm_ring<PREC, kTiles, kTiles, false, kVR, P_F2>(part, hid, rg);
+        if constexpr (DROP)
+            combine_rs<true, FAST, 0, 1, 0, true>(part, x, true, pv + PV_L2_B, pv + PV_LN3_W, pv + PV_LN3_B, comb, wave, lane, nullptr,
+                                                  row_bits(8u * blk + 5u), dscale);
+        else
         combine_rs<true, FAST>(part, x, true, pv + PV_L2_B, pv + (ENCL ? PV_LN2_W : PV_LN3_W), pv + (ENCL ? PV_LN2_B : PV_LN3_B),
                                comb, wave, lane);
         if (MODE != M_DEN_D && blk < 4 && wave == 0 && rvalid) {  // xs.append(x)
@@ -373,8 +422,12 @@ constexpr int kKS = 36;              // padded LDS row stride (floats) of the K_
 constexpr int kKeyRows = 320;        // 300 keys padded to 20 tiles (zero rows, masked)
 constexpr int kAttnLdsBytes = 2 * kKeyRows * kKS * 4;
 
-template <int PREC, int MODE>
-__global__ __launch_bounds__(256) void k_vae_attn(VaeAttnArgs a) {
+// DROP (train-mode decode; M_DEC, fp32, ArgsT = VaeAttnDropArgs): dropout site 0.  The reference drops the probabilities AFTER the softmax has normalised them, so the
+// running maximum and the row sum come from the unmasked scores; only the probability tile that feeds the O MFMA is masked (element (h 300 + q) 300 + key of
+// stream 8 layer; key padding first), and the kept ones' 1 / (1 - p) multiplies the normalised output once.
+template <int PREC, int MODE, bool DROP = false, typename ArgsT = VaeAttnArgs>
+__global__ __launch_bounds__(256) void k_vae_attn(ArgsT a) {
+    static_assert(!DROP || (MODE == M_DEC && PREC == PREC_F32), "dropout exists for the fp32 decoder attention only");
     constexpr bool ENC = MODE == M_ENC;
     const int S = MODE == M_DEN_E ? a.S : (ENC ? kFrames + 2 : kFrames);  // encode: keys 0,1 = distribution tokens, always valid (vae.py:176-181)
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -453,6 +506,16 @@ __global__ __launch_bounds__(256) void k_vae_attn(VaeAttnArgs a) {
             o[0] *= alpha;
             o[1] *= alpha;
             m_run = m_new;
+            if constexpr (DROP) {
+                const uint32_t e0 = ((uint32_t)h * kFrames + (uint32_t)fq) * kFrames + 32u * jp + 4u * g;   // (a multiple of 4)
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+                    const uint32_t bits = ddrop_bits4(a.drop.drop_seed, a.drop.drop_clip0 + (uint32_t)b, 8u * a.layer, (e0 + 16u * u) >> 2,
+                                                      2u + *a.drop.drop_epoch, a.drop.drop_thr);
+#pragma unroll
+                    for (int m = 0; m < 4; ++m) p[u][m] = ((bits >> m) & 1u) ? p[u][m] : 0.f;
+                }
+            }
             // O^T[d][i] += sum_key V[key][d] P[i][key]; A operand lane (g, d): V[32 jp + 16 u + 4 g + m][16 td + d]
             const float* vr = Vs + (32 * jp + 4 * g) * kKS + r;
             if constexpr (PREC == PREC_F32) {
@@ -495,8 +558,13 @@ __global__ __launch_bounds__(256) void k_vae_attn(VaeAttnArgs a) {
         }
         if (qvalid) {
             float* dst = a.o + ((size_t)b * S + fq) * kD + 32 * h + 4 * g;
+            if constexpr (DROP) {
+                st4(dst, (o[0] / l_run) * a.drop.drop_scale);
+                st4(dst + 16, (o[1] / l_run) * a.drop.drop_scale);
+            } else {
             st4(dst, o[0] / l_run);
             st4(dst + 16, o[1] / l_run);
+            }
         }
     }
 }
@@ -512,9 +580,15 @@ constexpr int kPairs = kKeyRows / 32;                        // 10
 constexpr int kAttnBf16LdsBytes = kKeyRows * 64 + kPairs * 2 * 16 * 64;  // 20 KiB + 20 KiB
 constexpr int kAttnSplitMaxClips = 48;   // up to this many clips per launch a (clip, head) pair is five workgroups (below); measured (profiles/r03_attn_split_threshold.txt): pays up to ~48 clips in bf16 and fp32x, not at 63
 
-template <int P16, int NQ>   // P16 = PREC_BF16 / PREC_F16: the operand format of q, k, v, p and the output
+// dropout site 0 of one (clip, head, layer): what attn_qtiles_bf16<.., DROP = true> needs to draw its masks (as in k_vae_attn<.., DROP> above)
+struct AttnDrop {
+    uint64_t seed;
+    uint32_t clip, ls, epoch2, thr, hS;   // hS = head * 300
+    float scale;
+};
+template <int P16, int NQ, bool DROP = false>   // P16 = PREC_BF16 / PREC_F16: the operand format of q, k, v, p and the output
 __device__ __forceinline__ void attn_qtiles_bf16(const uint4* Kb, const uint4* Vt, const unsigned short* qg,
-                                                 unsigned short* og, int qt0, int len, int g, int r, const int S) {
+                                                 unsigned short* og, int qt0, int len, int g, int r, const int S, const AttnDrop* dr = nullptr) {
     constexpr float kLog2e = 1.44269504088896340736f;
     typedef Op16<P16> Op;
     typedef typename Op::vec OPV;
@@ -577,6 +651,15 @@ __device__ __forceinline__ void attn_qtiles_bf16(const uint4* Kb, const uint4* V
                 }
             ps = allreduce_g_sum(ps);
             l_run[n] = l_run[n] * alpha + ps;
+            if constexpr (DROP) {   // the row sum above is the unmasked one: the reference drops normalised probabilities
+                const uint32_t e0 = (dr->hS + (uint32_t)((qt0 + 4 * n) * 16 + r)) * kFrames + 32u * jp + 4u * g;   // (a multiple of 4)
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+                    const uint32_t bits = ddrop_bits4(dr->seed, dr->clip, dr->ls, (e0 + 16u * u) >> 2, dr->epoch2, dr->thr);
+#pragma unroll
+                    for (int m = 0; m < 4; ++m) p[u][m] = ((bits >> m) & 1u) ? p[u][m] : 0.f;
+                }
+            }
             const OPV pb = Op::pack(p[0], p[1]);
             o[n][0] = Op::mfma(v0, pb, o[n][0]);  // O^T[d][i] += sum_key V[key][d] P[i][key]
             o[n][1] = Op::mfma(v1, pb, o[n][1]);
@@ -592,14 +675,22 @@ __device__ __forceinline__ void attn_qtiles_bf16(const uint4* Kb, const uint4* V
         const int fq = (qt0 + 4 * n) * 16 + r;
         if (fq < S) {
             unsigned short* dst = og + (size_t)fq * kD + 4 * g;
+            if constexpr (DROP) {
+                *reinterpret_cast<uint2*>(dst) = f32_to_x16x4<P16>((o[n][0] / l_run[n]) * dr->scale);
+                *reinterpret_cast<uint2*>(dst + 16) = f32_to_x16x4<P16>((o[n][1] / l_run[n]) * dr->scale);
+            } else {
             *reinterpret_cast<uint2*>(dst) = f32_to_x16x4<P16>(o[n][0] / l_run[n]);
             *reinterpret_cast<uint2*>(dst + 16) = f32_to_x16x4<P16>(o[n][1] / l_run[n]);
+            }
         }
     }
 }
 
-template <int P16, int MODE>
-__global__ __launch_bounds__(256) void k_vae_attn_bf16(VaeAttnArgs a) {
+// DROP (train-mode decode; M_DEC, ArgsT = VaeAttnDropArgs): dropout site 0 in attn_qtiles_bf16.  Both launch shapes stay (five workgroups per (clip, head) for small
+// batches): which workgroup computes a query tile changes neither its arithmetic nor its masks, so a clip's bits do not depend on the batch.
+template <int P16, int MODE, bool DROP = false, typename ArgsT = VaeAttnArgs>
+__global__ __launch_bounds__(256) void k_vae_attn_bf16(ArgsT a) {
+    static_assert(!DROP || MODE == M_DEC, "dropout exists for the decoder attention only");
     constexpr bool ENC = MODE == M_ENC;
     const int S = MODE == M_DEN_E ? a.S : (ENC ? kFrames + 2 : kFrames);
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -635,6 +726,19 @@ __global__ __launch_bounds__(256) void k_vae_attn_bf16(VaeAttnArgs a) {
     }
     __syncthreads();
     unsigned short* og = reinterpret_cast<unsigned short*>(a.o) + (size_t)b * S * kD + 32 * h;
+    if constexpr (DROP) {
+        const AttnDrop dr{a.drop.drop_seed, a.drop.drop_clip0 + (uint32_t)b, 8u * (uint32_t)a.layer, 2u + *a.drop.drop_epoch, a.drop.drop_thr,
+                          (uint32_t)h * kFrames, a.drop.drop_scale};
+        if (gridDim.y > 1) {
+            const int qt = 4 * blockIdx.y + wave;
+            if (qt < kRowTiles) attn_qtiles_bf16<P16, 1, true>(Kb, Vt, qg, og, qt, len, g, r, S, &dr);
+            return;
+        }
+        attn_qtiles_bf16<P16, 2, true>(Kb, Vt, qg, og, wave, len, g, r, S, &dr);
+        attn_qtiles_bf16<P16, 2, true>(Kb, Vt, qg, og, wave + 8, len, g, r, S, &dr);
+        if (wave + 16 < kRowTiles) attn_qtiles_bf16<P16, 1, true>(Kb, Vt, qg, og, wave + 16, len, g, r, S, &dr);
+        return;
+    }
     // 19 query tiles: wave w owns tiles w, w+4, w+8, w+12 (two pairs) and w+16 (waves 0..2)
     if (a.q_tiles == 1) {  // last encoder block: only the distribution rows (tile 0) are consumed downstream
         if (wave == 0 && blockIdx.y == 0) attn_qtiles_bf16<P16, 1>(Kb, Vt, qg, og, 0, len, g, r, S);
@@ -882,10 +986,59 @@ hipError_t attn_mode(const VaeAttnArgs& a, int precision, hipStream_t stream, bo
     }
     return hipSuccess;
 }
+
+template <int PREC>
+hipError_t rows_drop_one(const VaeRowsDropArgs& a, hipStream_t stream, bool setup) {
+    if (setup) return set_lds(&k_vae_rows<PREC, M_DEC, true, VaeRowsDropArgs>, kRowsLdsBytes);
+    hipLaunchKernelGGL((k_vae_rows<PREC, M_DEC, true, VaeRowsDropArgs>), dim3(a.B * a.tiles), dim3(256), kRowsLdsBytes, stream, a);
+    return hipSuccess;
+}
+
+// train-mode decode (amuse_set_decode_dropout; VAE_MODE_DEC_DROP): the dropout instantiations of the M_DEC row and attention kernels (fp32, bf16, fp16)
+hipError_t launch_vae_rows_drop(const VaeRowsDropArgs& a_in, int precision, hipStream_t stream) {
+    if (precision != PREC_F32 && precision != PREC_BF16 && precision != PREC_F16) return hipErrorInvalidValue;
+    VaeRowsDropArgs a = a_in;
+    if (a.drop.drop_thr == 0 || !(a.drop.drop_epoch = train_epoch_ptr())) return a.drop.drop_thr == 0 ? hipErrorInvalidValue : hipErrorOutOfMemory;
+    static DeviceOnce once;
+    int dev_;
+    if (!once.done(&dev_)) {
+        hipError_t e = rows_drop_one<PREC_F32>(a, stream, true);
+        if (e == hipSuccess) e = rows_drop_one<PREC_BF16>(a, stream, true);
+        if (e == hipSuccess) e = rows_drop_one<PREC_F16>(a, stream, true);
+        if (e != hipSuccess) return e;
+        once.set(dev_);
+    }
+    hipError_t e = precision == PREC_F32 ? rows_drop_one<PREC_F32>(a, stream, false)
+                 : precision == PREC_F16 ? rows_drop_one<PREC_F16>(a, stream, false)
+                                         : rows_drop_one<PREC_BF16>(a, stream, false);
+    return e != hipSuccess ? e : hipGetLastError();
+}
+
+hipError_t launch_vae_attn_drop(const VaeAttnDropArgs& a_in, int precision, hipStream_t stream) {
+    if (precision != PREC_F32 && precision != PREC_BF16 && precision != PREC_F16) return hipErrorInvalidValue;
+    VaeAttnDropArgs a = a_in;
+    if (a.drop.drop_thr == 0 || !(a.drop.drop_epoch = train_epoch_ptr())) return a.drop.drop_thr == 0 ? hipErrorInvalidValue : hipErrorOutOfMemory;
+    static DeviceOnce once;
+    int dev_;
+    if (!once.done(&dev_)) {
+        hipError_t e = set_lds(&k_vae_attn<PREC_F32, M_DEC, true, VaeAttnDropArgs>, kAttnLdsBytes);
+        if (e == hipSuccess) e = set_lds(&k_vae_attn_bf16<PREC_BF16, M_DEC, true, VaeAttnDropArgs>, kAttnBf16LdsBytes);
+        if (e == hipSuccess) e = set_lds(&k_vae_attn_bf16<PREC_F16, M_DEC, true, VaeAttnDropArgs>, kAttnBf16LdsBytes);
+        if (e != hipSuccess) return e;
+        once.set(dev_);
+    }
+    const dim3 grid(a.B * kHeads), block(256);
+    const dim3 grid16(a.B * kHeads, a.B <= kAttnSplitMaxClips ? 5 : 1);   // (the eval launch's rule; the kernel and a tile's bits are the same in both shapes)
+    if (precision == PREC_F32) hipLaunchKernelGGL((k_vae_attn<PREC_F32, M_DEC, true, VaeAttnDropArgs>), grid, block, kAttnLdsBytes, stream, a);
+    else if (precision == PREC_F16) hipLaunchKernelGGL((k_vae_attn_bf16<PREC_F16, M_DEC, true, VaeAttnDropArgs>), grid16, block, kAttnBf16LdsBytes, stream, a);
+    else hipLaunchKernelGGL((k_vae_attn_bf16<PREC_BF16, M_DEC, true, VaeAttnDropArgs>), grid16, block, kAttnBf16LdsBytes, stream, a);
+    return hipGetLastError();
+}
 }  // namespace
 
-// mode: VAE_MODE_* (amuse_kernels.hpp) = M_DEC / M_ENC / M_DEN_E / M_DEN_D above
+// mode: VAE_MODE_* (amuse_kernels.hpp) = M_DEC / M_ENC / M_DEN_E / M_DEN_D above, or VAE_MODE_DEC_DROP (a is a VaeRowsDropArgs)
 hipError_t launch_vae_rows(const VaeRowsArgs& a, int precision, int mode, hipStream_t stream) {
+    if (mode == VAE_MODE_DEC_DROP) return launch_vae_rows_drop(static_cast<const VaeRowsDropArgs&>(a), precision, stream);
     static DeviceOnce once;
     int dev_;
     if (!once.done(&dev_)) {
@@ -900,6 +1053,7 @@ hipError_t launch_vae_rows(const VaeRowsArgs& a, int precision, int mode, hipStr
 }
 
 hipError_t launch_vae_attn(const VaeAttnArgs& a, int precision, int mode, hipStream_t stream) {
+    if (mode == VAE_MODE_DEC_DROP) return launch_vae_attn_drop(static_cast<const VaeAttnDropArgs&>(a), precision, stream);
     static DeviceOnce once;
     int dev_;
     if (!once.done(&dev_)) {

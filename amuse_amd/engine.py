@@ -159,6 +159,12 @@ class HipEngine:
         the library's dropout epoch).  p = 0: eval mode (the default)."""
         _lib.check(self.lib.amuse_set_sample_dropout(self.ctx, float(p), int(seed) & 0xFFFFFFFFFFFFFFFF))
 
+    def set_decode_dropout(self, p: float = 0.0, seed: int = 0, clip_index0: int = 0):
+        """Train-mode decode (amuse_hip.h amuse_set_decode_dropout): the six dropouts of every MotionPrior.decode block live with probability p in
+        vae_decode and the decode half of diffusion_backward (fp32 / bf16 / fp16, on the staged kernels at every clip count); masks keyed by (seed,
+        global clip, the library's dropout epoch).  Clip b of a vae_decode call is global clip clip_index0 + b.  p = 0: eval mode (the default)."""
+        _lib.check(self.lib.amuse_set_decode_dropout(self.ctx, float(p), int(seed) & 0xFFFFFFFFFFFFFFFF, int(clip_index0) & 0xFFFFFFFFFFFFFFFF))
+
     def set_decode_path(self, path: str = "auto"):
         """decode kernels of the bf16 / fp16 / fp32x modes: "auto" (from 64 clips up the fused per-clip kernel, in fp32x the no-split-K row
         kernel), "staged", "fused", "clip" (the fp32x mode's per-clip decoder; "fused" in the other modes) (amuse_hip.h amuse_set_decode_path)."""

@@ -2,6 +2,7 @@
 packing of its call sites (scripts/trainer.py:524-526).  Rendering (Blender / ffmpeg) is out of scope."""
 from __future__ import annotations
 
+import os
 import random
 import string
 from pathlib import Path
@@ -75,6 +76,11 @@ def write_sample(feats: torch.Tensor, out_dir: Path, subject: str = "scott", rng
         d.mkdir(parents=True, exist_ok=True)
         tag = "".join(rng.choice(string.ascii_uppercase + string.ascii_lowercase + string.digits) for _ in range(6))
         p = d / f"{subject}_seq_{i}_{tag}_motion_smplx.npz"
-        np.savez(p, **smplx_npz_fields(feat.detach().cpu().numpy(), subject2gender(subject), betas))
+        # written beside the target and moved over it: a reader that still holds an older file of the same name open (two runs inside one second share the
+        # time-stamped directory and the seeded tags) keeps reading that file, never a half-written or replaced one
+        tmp = p.with_name(p.name + ".part")
+        with open(tmp, "wb") as fh:
+            np.savez(fh, **smplx_npz_fields(feat.detach().cpu().numpy(), subject2gender(subject), betas))
+        os.replace(tmp, p)
         paths.append(p)
     return paths

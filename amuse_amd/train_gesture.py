@@ -543,10 +543,14 @@ class HipInnerSampler:
     dropout = p > 0 (`--inner-sampler train-hip`, AMUSE_TRAIN_INNER=train-hip): the reference's train-mode semantics on the same kernel - the Denoiser's
     encoder dropouts live in all steps (amuse_set_sample_dropout: masks keyed by the global clip index and the library's dropout epoch, so eager calls
     draw fresh masks through the clip counter and replays of a captured step through the epoch), and the decode is prior.decode on the trainer's own
-    modules in train mode (the library's dropout-live layer kernels), on the trainer's stream after the join (decode_on_trainer_stream)."""
+    modules in train mode (the library's dropout-live layer kernels), on the trainer's stream after the join (decode_on_trainer_stream).
+    hip_decode (`--inner-sampler train-hip-decode`, with dropout > 0): the decode stays in the library too - amuse_set_decode_dropout turns on the dropout
+    instantiations of the staged decode kernels, masks keyed like the sampler's (seed + 2, the sample's clip base, the dropout epoch) - and on the sampler's
+    side stream, off the trainer's critical stream."""
 
     def __init__(self, trainer_models: Dict[str, nn.Module], device, precision: str = "bf16", refresh: int = 1, seed: int = 2024,
-                 ldm_cfg: Optional[dict] = None, flat: Optional[tuple] = None, rank: int = 0, world: int = 1, dropout: float = 0.0):
+                 ldm_cfg: Optional[dict] = None, flat: Optional[tuple] = None, rank: int = 0, world: int = 1, dropout: float = 0.0,
+                 hip_decode: bool = False):
         from .engine import HipEngine
         self.models, self.precision, self.refresh, self.seed = trainer_models, precision, max(1, refresh), seed
         self.flat = flat                        # (prior, denoiser) flat fp32 images that ARE the parameters (GestureTrainer.flat_param)
@@ -560,7 +564,9 @@ class HipInnerSampler:
         self.what = {"bf16": 2, "fp32x": 8, "fp16": 16}.get(precision, 1)   # AMUSE_UPD_* mask of the streams this sampler runs
         self.on_device = True      # re-pack on the GPU straight from the trainer's flat parameter buffer (False: the host path of amuse_update_weights; tests)
         self.dropout = float(dropout)
-        self.decode_on_trainer_stream = self.dropout > 0
+        self.hip_decode = bool(hip_decode) and self.dropout > 0
+        self.decode_on_trainer_stream = self.dropout > 0 and not self.hip_decode
+        self._clip0 = 0            # clip base of the last sample: the decode's masks follow the sampler's clips
         if self.dropout > 0:
             self.engine.set_sample_dropout(self.dropout, seed=seed + 1)
 
@@ -574,6 +580,9 @@ class HipInnerSampler:
         return self.decode(self.sample_latents(con, emo, sty, bsz))
 
     def decode(self, lat):
+        if self.hip_decode:       # train mode inside the library's decode kernels (a host-side switch: safe inside a captured step)
+            self.engine.set_decode_dropout(self.dropout, seed=self.seed + 2, clip_index0=self._clip0)
+            return self.engine.vae_decode(lat, None, self.precision, return_feats=True)["feats"]
         if self.dropout > 0:      # train mode: the trainer's MotionPrior.decode, dropout live through the layer kernels
             return self.models["prior"].decode(lat[None], [SEQ_LEN] * lat.shape[0])
         return self.engine.vae_decode(lat, None, self.precision, return_feats=True)["feats"]
@@ -599,10 +608,12 @@ class HipInnerSampler:
             # inside a captured training step (GestureTrainer.enable_graph) the host-side clip counter would be frozen: the initial latents come from torch's
             # generator on the device, whose state the graph advances per replay
             # (with dropout live the clip index still keys the masks: rank r takes clips [r bsz, (r + 1) bsz), the epoch word advances per replay)
+            self._clip0 = self.rank * bsz if self.dropout > 0 else 0
             return self.engine.sample(con, emo, sty, self.precision, seed=self.seed, x_init=torch.randn(bsz, 128, device=self.engine.device),
-                                      clip_index0=self.rank * bsz if self.dropout > 0 else 0)
+                                      clip_index0=self._clip0)
         # initial latents are keyed by a global clip index: rank r draws clips [counter + r * bsz, counter + (r + 1) * bsz)
-        lat = self.engine.sample(con, emo, sty, self.precision, seed=self.seed, clip_index0=self.clip_counter + self.rank * bsz)
+        self._clip0 = self.clip_counter + self.rank * bsz
+        lat = self.engine.sample(con, emo, sty, self.precision, seed=self.seed, clip_index0=self._clip0)
         self.clip_counter += bsz * self.world
         return lat
 
@@ -705,11 +716,14 @@ def build_trainer(device, rank: int = 0, world: int = 1, process_group=None, see
     tr = GestureTrainer(prior, ldm, device, lr=lr, loss_cfg=loss_cfg, inner_sampler=None, process_group=process_group,
                         world=world, kind=None if kind == "full" else kind, grads_mode=grads_mode, sampler_stream=sampler_stream, optimizer=optimizer, denoiser_stream=denoiser_stream)
     inner = inner or os.environ.get("AMUSE_TRAIN_INNER", "eval")
-    if inner not in ("eval", "train", "train-hip"):
+    if inner not in ("eval", "train", "train-hip", "train-hip-decode"):
         raise ValueError(f"inner sampler {inner!r}: 'eval' (the persistent HIP sampler kernel, default), 'train' (the reference's train-mode semantics, dropout "
-                         "live, through the modules) or 'train-hip' (the same semantics on the persistent HIP sampler kernel)")
+                         "live, through the modules), 'train-hip' (the same semantics on the persistent HIP sampler kernel) or 'train-hip-decode' (train-hip with "
+                         "the train-mode decode in the HIP decode kernels too)")
     if inner == "train-hip" and torch.device(device).type != "cuda":
         raise RuntimeError("inner sampler 'train-hip' runs the dropout-live HIP sampler kernel: there is no CPU path (use inner='train' on the CPU)")
+    if inner == "train-hip-decode" and torch.device(device).type != "cuda":
+        raise RuntimeError("inner sampler 'train-hip-decode' runs the dropout-live HIP sampler and decode kernels: there is no CPU path (use inner='train' on the CPU)")
     if inner == "train":      # TrainModeInnerSampler: the modules themselves (any device); on the GPU the initial latents are the HIP sampler's draws
         eng = None
         if torch.device(device).type == "cuda":
@@ -722,7 +736,7 @@ def build_trainer(device, rank: int = 0, world: int = 1, process_group=None, see
                                "to train without the no-gradient gen_feature term)")
         tr.inner_sampler = HipInnerSampler(tr.model, device, refresh=sampler_refresh, ldm_cfg=ldm_cfg,
                                            flat=(tr.flat_param[:tr.n_prior], tr.flat_param[tr.n_prior:]), rank=rank, world=world,
-                                           dropout=dropout if inner == "train-hip" else 0.0)
+                                           dropout=dropout if inner in ("train-hip", "train-hip-decode") else 0.0, hip_decode=inner == "train-hip-decode")
     return tr
 
 
@@ -803,6 +817,8 @@ def bench_main(args):
                                       "condition / memory projections and the Denoiser's 160-row layers; attention, LayerNorm / dropout / GELU / bias gradients, AdamW hand-written too; "
                                       "the library links and loads no vendor BLAS (torch's own ops remain only in the loss arithmetic)",
                        "inner_sampler": ("train: the reference's train-mode loop, dropout live (TrainModeInnerSampler)" if getattr(tr.inner_sampler, "serial", False)
+                                         else "train-hip-decode: the persistent HIP sampler kernel with the Denoiser's dropouts live + the train-mode decode in the HIP "
+                                              "decode kernels, both on the sampler's stream (the reference's semantics)" if getattr(tr.inner_sampler, "hip_decode", False)
                                          else "train-hip: the persistent HIP sampler kernel with the Denoiser's dropouts live + the train-mode prior.decode "
                                               "(the reference's semantics)" if getattr(tr.inner_sampler, "dropout", 0) > 0
                                          else "eval: the persistent HIP sampler kernel (dropout off - the reference's loop runs in train mode; opt in with "
@@ -835,10 +851,11 @@ def main(argv=None):
     ap.add_argument("--lr", type=float, default=1e-4, help="TRAIN_PARAM.latent_diffusion.lr_base (AdamW, trainer.py:181-184)")
     ap.add_argument("--kind", default=None, choices=["full", "emotion", "identity", "baseline"],
                     help="ablation variant (default: derived from the --cache id like trainer.py:396-401; synthetic data: full)")
-    ap.add_argument("--inner-sampler", default=None, choices=["eval", "train", "train-hip"],
+    ap.add_argument("--inner-sampler", default=None, choices=["eval", "train", "train-hip", "train-hip-decode"],
                     help="the no-gradient DDIM-50 + decode of every iteration: eval (default) = the persistent HIP sampler kernel, dropout off; train = the "
                          "reference's semantics (ldm.py:117-153 under model.train(): every dropout live) through the trainer's own modules, ~10 x slower; "
-                         "train-hip = the same semantics on the persistent HIP sampler kernel (dropout-live instantiation) + the train-mode decode")
+                         "train-hip = the same semantics on the persistent HIP sampler kernel (dropout-live instantiation) + the train-mode decode on the "
+                         "trainer's modules; train-hip-decode = train-hip with the decode in the HIP decode kernels too (amuse_set_decode_dropout), on the sampler's stream")
     ap.add_argument("--no-graph", action="store_true", help="keep the iteration eager (default on the GPU: captured as two HIP graphs after three eager iterations)")
     ap.add_argument("--ldm-cfg", default=None, help="JSON file: configs/<arch>.json merged with diff_o.yaml (losses, schedulers); default: the shipped values")
     args = ap.parse_args(argv)
@@ -880,6 +897,9 @@ def main(argv=None):
             print("[LPDM-T] inner sampler: none (CPU run: the no-gradient gen_feature term is off)", flush=True)
         elif getattr(tr.inner_sampler, "serial", False):
             print("[LPDM-T] inner sampler: train - the reference's semantics (ldm.py:117-153 and prior.decode under model.train(): every dropout live), on the trainer's own modules", flush=True)
+        elif getattr(tr.inner_sampler, "hip_decode", False):
+            print(f"[LPDM-T] inner sampler: train-hip-decode - the reference's semantics (every dropout live, p = {tr.inner_sampler.dropout:g}) on the persistent HIP sampler "
+                  "kernel and the dropout instantiations of the HIP decode kernels, both on the sampler's stream", flush=True)
         elif getattr(tr.inner_sampler, "dropout", 0) > 0:
             print(f"[LPDM-T] inner sampler: train-hip - the reference's semantics (every dropout live, p = {tr.inner_sampler.dropout:g}) on the persistent HIP sampler "
                   "kernel, then prior.decode on the trainer's modules in train mode", flush=True)

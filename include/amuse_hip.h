@@ -37,8 +37,9 @@ extern "C" {
  *   environment  AMUSE_BENCH_SHARE_GPU=1   bench.py: --gpus N ranks on one GPU over gloo (the two-rank bench tests on a one-GPU box)
  *   environment  AMUSE_RUN_STAMP, AMUSE_MANIFEST_DIR   launcher -> rank hand-over inside amuse_amd/main.py (not set by users)
  *   environment  AMUSE_TRAIN_FUSED=0, AMUSE_TRAIN_VALIDATE=1   train_gesture: eager layers / torch's distribution checks (amuse_amd/train_ops.py)
- *   environment  AMUSE_TRAIN_INNER=eval|train|train-hip   train_gesture's in-loop sampler: the persistent kernel in eval mode (default) / the reference's
- *                                      train-mode module loop / the persistent kernel with the dropouts live (amuse_set_sample_dropout) + the train-mode decode
+ *   environment  AMUSE_TRAIN_INNER=eval|train|train-hip|train-hip-decode   train_gesture's in-loop sampler: the persistent kernel in eval mode (default) / the
+ *                                      reference's train-mode module loop / the persistent kernel with the dropouts live (amuse_set_sample_dropout) + the train-mode
+ *                                      decode on the trainer's torch modules / the same sampler + the train-mode decode in the HIP decode kernels (amuse_set_decode_dropout)
  * The ~30 environment switches and 51 -DAMUSE_* macros of rounds 1-5 (A/B residue) were retired in round 6: tools/probes/retired_switches/. */
 #define AMUSE_ABI_VERSION 5   /* 5: amuse_plan / amuse_debug_last_plan (the launch plan); the process-wide environment overrides of kernel choices are gone;
                                  4: amuse_train_* (training-step glue kernels);
@@ -269,8 +270,8 @@ int amuse_set_clips_per_group(amuse_ctx* ctx, int g);
 /* Train-mode sampling: the Denoiser's encoder dropouts live in amuse_sample, amuse_denoise_step, amuse_profile_sample and the sampling half of
  * amuse_diffusion_backward (AMUSE_ARCH_ENC; AMUSE_PREC_F32 / _BF16 / _F16), as in the reference's training loop, which samples with the networks in
  * train() mode (scripts/trainer.py).  p = 0 (the default) = eval mode, the kernels of before.  p NaN, < 0 or >= 1: AMUSE_EINVAL.  With p > 0 a sample or
- * step call in AMUSE_PREC_F32X or on another arch returns AMUSE_ESTATE and launches nothing.  Decode, encode and amuse_diffusion_forward stay in eval
- * semantics.
+ * step call in AMUSE_PREC_F32X or on another arch returns AMUSE_ESTATE and launches nothing.  The decode has a switch of its own
+ * (amuse_set_decode_dropout below); encode and amuse_diffusion_forward stay in eval semantics.
  * Mask contract (tests/test_gpu_sample_dropout.py restates it).  Dropout sites of encoder layer l = 0..8 in execution order (input blocks 0-3, middle,
  * output blocks 0-3), as TransformerEncoderLayer.forward_post (utils/cross_attention.py):
  *   site s = 0  softmax probabilities before . V        element e = (h S + q) S + k   (h = head 0..3, q / k = query / key token, S = 3..5 tokens)
@@ -283,6 +284,31 @@ int amuse_set_clips_per_group(amuse_ctx* ctx, int g);
  * epoch word (amuse_train_epoch_advance / _set: a captured step draws fresh masks per replay).  Word 3 starts at 2: no collision with the noise
  * streams 0 and 1.  Keep <=> (draw >> 8) >= thr, thr = (uint32)(p 2^24); kept values are multiplied by 1 / (1 - p) (the amuse_train_* convention). */
 int amuse_set_sample_dropout(amuse_ctx* ctx, float p, uint64_t seed);
+
+/* Train-mode decode: the dropouts of MotionPrior.decode live in amuse_vae_decode and in the decode half of amuse_diffusion_backward, as in the reference's
+ * training loop, which decodes its in-loop samples with the prior in train() mode (scripts/trainer.py).  A switch of its own: amuse_set_sample_dropout is not
+ * touched by it, nor are amuse_vae_encode, amuse_diffusion_forward, amuse_denoise_step*, amuse_sample.  p = 0 (the default) = eval mode, the kernels and the plan
+ * of before.  p NaN, < 0 or >= 1, or a NULL ctx: AMUSE_EINVAL.  With p > 0:
+ *   - AMUSE_PREC_F32, _BF16, _F16: the decode runs on the staged kernel family (csrc/k_vae.hip; STAGED below) at every clip count, whatever amuse_set_decode_path
+ *     says, and amuse_debug_last_plan reports AMUSE_DECODE_STAGED; the fused per-clip kernels stay eval-only.  A clip's result does not depend on the batch it is in.
+ *   - AMUSE_PREC_F32X, or a context without a prior: AMUSE_ESTATE, nothing launched (amuse_diffusion_backward: not even the sampler).
+ * Clip b of an amuse_vae_decode call has global clip index clip_index0 + b with THIS function's clip_index0; inside amuse_diffusion_backward that call's own
+ * clip_index0 argument is used instead, so the decode's masks follow the sampler's clips.  The index is truncated to 32 bits, as in the sampler.
+ * Mask contract (tests/test_decode_dropout_cpu.py restates it; tests/golden/decode_dropout.npz holds the reference module's output under these masks).
+ * TransformerDecoderLayer.forward_post (utils/cross_attention.py) has six dropout sites (torch's nn.MultiheadAttention drops its softmax probabilities); layer
+ * l = 0..8 in execution order (input blocks 0-3, middle, output blocks 0-3), S = 300 rows whatever the clip's length, h = head 0..3, q / k = query / key frame:
+ *   site s = 0  self-attention probabilities before . V           element e = (h S + q) S + k   (after the softmax has normalised: the row sum is the unmasked one)
+ *   site s = 1  dropout1 on the self-attention out_proj (+ bias)  e = q 128 + f
+ *   site s = 2  cross-attention probabilities onto the ONE memory token (softmax over one key = 1, so 0 or 1 / (1 - p) per head and query)   e = h S + q
+ *   site s = 3  dropout2 on the cross-attention out_proj (+ bias) e = q 128 + f
+ *   site s = 4  the FFN's dropout(gelu(linear1))                  e = q 512 + f
+ *   site s = 5  dropout3 on linear2 (+ bias)                      e = q 128 + f
+ * None on the positional encoding, the skip linears, decoder.norm or final_layer (the reference has none there).
+ * Element e uses draw e % 4 of Philox4x32-10 with key = seed (lo, hi) and counter = (clip, 0x80000000 | (8 l + s), e / 4, 2 + epoch): epoch = the training
+ * dropout epoch word (amuse_train_epoch_advance / _set: a captured decode draws fresh masks per replay).  Bit 31 of word 1 keeps these streams clear of the
+ * sampler's under an equal seed (there word 1 is the step, at most AMUSE_MAX_STEPS); word 3 starts at 2: no collision with the noise streams 0 and 1.
+ * Keep <=> (draw >> 8) >= thr, thr = (uint32)(p 2^24); kept values are multiplied by 1 / (1 - p) in fp32 (the amuse_train_* convention). */
+int amuse_set_decode_dropout(amuse_ctx* ctx, float p, uint64_t seed, uint64_t clip_index0);
 
 /* Which kernels amuse_vae_decode (and amuse_diffusion_backward), amuse_vae_encode and the pose-space Denoiser's step use.  Every mode but fp32 has more
  * than one kernel family for MotionPrior.decode (vae.py:216-278); they compute the same function and differ in summation order only (fp32x: 1.5e-6 on

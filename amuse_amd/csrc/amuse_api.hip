@@ -1,6 +1,6 @@
 // C ABI of libamuse_hip.so (include/amuse_hip.h): context, weight packing into MFMA-fragment
 // streams, workspace, and the launch sequences.  Host code only - kernels live in k_*.hip.
-#include "amuse_host.hpp"
+#include "amuse_pack.hpp"
 #include "amuse_variants.hpp"
 
 namespace {
@@ -25,261 +25,88 @@ constexpr int kVaeChunk = 512;
 constexpr int kEncRows = kFrames + 2;  // encoder sequence: 2 distribution tokens + 300 frames
 constexpr size_t kVaeFloatsPerClip = (size_t)kEncRows * kD * (1 + 3 + 1 + 4) + 4 * kLayers * kD;  // x, qkv, o, skip, ca (train-mode decode: its four per-head partials) | stats
 
-constexpr int kUpdBit[4] = {AMUSE_UPD_F32, AMUSE_UPD_BF16, AMUSE_UPD_F32X, AMUSE_UPD_F16};   // per PREC_* index
-
+// The builders: which parameters, precision, front / back matrices and AMUSE_UPD_* class go into which stream.  The layouts themselves - the order inside
+// a stream and the kernel that consumes it - are stated once each in amuse_pack.hpp.
 int build_denoiser(amuse_ctx* c, const float* den, int what = AMUSE_UPD_ALL) {
     static const ParamIndex DI = denoiser_index();
     const Params D{DI, den};
-    // ---- weight stream of the 4-wave kernel (k_sampler.hip: the fp32 parity mode; every other mode samples on an 8-wave kernel): [wave][per-step units]
-    for (const int prec : {PREC_F32}) {
-        if (!(what & kUpdBit[prec])) continue;   // amuse_update_weights: only the requested precisions are re-packed
+    if (what & AMUSE_UPD_F32) {   // the 4-wave kernel (k_sampler.hip: the fp32 parity mode; every other mode samples on an 8-wave kernel), pack_ring4_stream
         std::vector<uint4> all;
-        size_t per_wave = 0;
-        for (int w = 0; w < 4; ++w) {
-            std::vector<uint4> s;
+        const auto pass = [&](std::vector<uint4>& s, int w) {
             for (int b = 0; b < 9; ++b) {
                 const std::string p = blk_name("encoder", b);
                 if (b >= 5) {
-                    pack_skiplin(s, prec, D, "encoder", b - 5, w);
-                    s.insert(s.end(), (size_t)skip_pad_units(prec) * 64, uint4{0, 0, 0, 0});  // ring alignment
+                    pack_skiplin(s, PREC_F32, D, "encoder", b - 5, w);
+                    pad_units(s, skip_pad_units(PREC_F32));  // ring alignment
                 }
-                pack_qkv(s, prec, D.get(p + ".self_attn.in_proj_weight"), w, true);
-                pack_outproj_ffn_quarters(s, prec, D, p, w);
+                pack_qkv(s, PREC_F32, D.get(p + ".self_attn.in_proj_weight"), w, true);
+                pack_outproj_ffn_quarters(s, PREC_F32, D, p, w);
             }
-            if (w == 0) per_wave = s.size();
-            else if (s.size() != per_wave) return fail(AMUSE_ESTATE, "internal: uneven denoiser wave streams");
-            all.insert(all.end(), s.begin(), s.end());
-            all.insert(all.end(), s.begin(), s.begin() + (size_t)kRing * 64);  // ring wrap: tail = head
-        }
-        c->den_wave_units[prec] = (uint32_t)(per_wave / 64);
-        if (upload(&c->den_w[prec], all.data(), all.size() * sizeof(uint4))) return AMUSE_EHIP;
+        };
+        if (int e = pack_ring4_stream(all, &c->den_wave_units, pass)) return e;
+        if (upload(c, &c->den_w, all.data(), all.size() * sizeof(uint4), PREC_F32, AMUSE_UPD_F32)) return AMUSE_EHIP;
     }
-    for (const int p16 : {PREC_BF16, PREC_F16}) {   // 8-wave throughput kernel (bf16 / fp16 operands): wave w8 = 4 s + h; A waves (s = 0) carry head h + FFN quarters 0,1, B waves quarters 2,3
-        if (!(what & kUpdBit[p16])) continue;
+    // the 8-wave kernels (pack_sample8_streams): bf16 and fp16 share layout and unit counts, fp32x has its own A-wave order
+    struct { int prec; uint4** slot; uint32_t* units; } const w8[3] = {
+        {PREC_BF16, &c->den_w8, c->den_w8_units}, {PREC_F16, &c->den_w8h, c->den_w8_units}, {PREC_F16X2, &c->den_w8x, c->den_w8x_units}};
+    for (const auto& t : w8) {
+        if (!(what & kUpdBit[t.prec])) continue;   // amuse_update_weights: only the requested precisions are re-packed
         std::vector<uint4> all;
-        for (int w8 = 0; w8 < 8; ++w8) {
-            const int h = w8 & 3, sgrp = w8 >> 2;
-            std::vector<uint4> s;
-            // per block, in issue order (k_sampler8.hip).  A: out_proj | in_proj q,k | v (ahead of an output block: skip
-            // linear, skip-input half | q,k | v | out_proj), then FFN quarters 0,1 as F1a F1b F2a F2b.  B: [skip linear,
-            // x half], then FFN quarters 2,3.
-            for (int b = 0; b < 9; ++b) {
-                const std::string p = blk_name("encoder", b);
-                auto f1 = [&](int q) { const int h0 = 8 * h + 2 * q; pack_gemm(s, p16, D.get(p + ".linear1.weight"), 512, 128, {h0, h0 + 1}, range(0, 8)); };
-                auto f2 = [&](int q) { const int h0 = 8 * h + 2 * q; pack_gemm(s, p16, D.get(p + ".linear2.weight"), 128, 512, range(0, 8), {h0, h0 + 1}); };
-                const int qa = 2 * sgrp, qb = 2 * sgrp + 1;
-                const float* wskip = b >= 5 ? D.get("encoder.linear_blocks." + std::to_string(b - 5) + ".weight") : nullptr;
-                if (sgrp == 0) {
-                    // a block's group of 32: 8 leading units, then q, k | v.  The leading 8 are out_proj - or, ahead of an
-                    // output block, the skip-input half (k-tiles 8..15 of cat(x, skip)) of the skip linear for output
-                    // tiles 2h, 2h+1, with out_proj following as a group of its own
-                    const auto outproj = [&] { pack_gemm(s, p16, D.get(p + ".self_attn.out_proj.weight"), 128, 128, range(0, 8), {2 * h, 2 * h + 1}); };
-                    if (b >= 5) pack_gemm(s, p16, wskip, 128, 256, {2 * h, 2 * h + 1}, range(8, 16));
-                    else outproj();
-                    pack_qkv(s, p16, D.get(p + ".self_attn.in_proj_weight"), h, true);
-                    if (b >= 5) outproj();
-                } else if (b >= 5) {
-                    // the x half (k-tiles 0..7) of the same two output tiles
-                    pack_gemm(s, p16, wskip, 128, 256, {2 * h, 2 * h + 1}, range(0, 8));
-                }
-                f1(qa); f1(qb); f2(qa); f2(qb);
-            }
-            uint32_t& units = c->den_w8_units[sgrp];
-            if (h == 0) units = (uint32_t)(s.size() / 64);
-            else if (s.size() / 64 != units) return fail(AMUSE_ESTATE, "internal: uneven 8-wave denoiser streams");
-            all.insert(all.end(), s.begin(), s.end());
-            if (sgrp == 0) all.insert(all.end(), s.begin(), s.begin() + (size_t)kRing8 * 64);  // ring wrap: tail = head
-        }
-        if (upload(p16 == PREC_BF16 ? &c->den_w8 : &c->den_w8h, all.data(), all.size() * sizeof(uint4))) return AMUSE_EHIP;
-    }
-    if (what & AMUSE_UPD_F32X) {   // 8-wave fp32x kernel: the same roles, split-fp16 units (two per 16 x 32 weight tile: hi, lo)
-        std::vector<uint4> all;
-        for (int w8 = 0; w8 < 8; ++w8) {
-            const int h = w8 & 3, sgrp = w8 >> 2;
-            std::vector<uint4> s;
-            // per block, in issue order (k_sampler8x.hip).  A: lead (v - or, ahead of an output block, the skip-input half of the
-            // skip linear for output tiles 2h, 2h+1) | q,k for k-pairs 0,1 | [v, output blocks] | q,k for k-pairs 2,3 | out_proj
-            // | F1a F1b F2a F2b (FFN quarters 0,1).  B: [skip linear, x half], F1a F1b F2a F2b (quarters 2,3).
-            for (int b = 0; b < 9; ++b) {
-                const std::string p = blk_name("encoder", b);
-                auto f1 = [&](int q) { const int h0 = 8 * h + 2 * q; pack_gemm(s, PREC_F16X2, D.get(p + ".linear1.weight"), 512, 128, {h0, h0 + 1}, range(0, 8)); };
-                auto f2 = [&](int q) { const int h0 = 8 * h + 2 * q; pack_gemm(s, PREC_F16X2, D.get(p + ".linear2.weight"), 128, 512, range(0, 8), {h0, h0 + 1}); };
-                const int qa = 2 * sgrp, qb = 2 * sgrp + 1;
-                const float* wskip = b >= 5 ? D.get("encoder.linear_blocks." + std::to_string(b - 5) + ".weight") : nullptr;
-                if (sgrp == 0) {
-                    const float* in_w = D.get(p + ".self_attn.in_proj_weight");
-                    const std::vector<int> qk_tiles = {2 * h, 2 * h + 1, 8 + 2 * h, 8 + 2 * h + 1};
-                    const auto outproj = [&] { pack_gemm(s, PREC_F16X2, D.get(p + ".self_attn.out_proj.weight"), 128, 128, range(0, 8), {2 * h, 2 * h + 1}); };
-                    const auto vproj = [&] { pack_gemm(s, PREC_F16X2, in_w, 384, 128, {16 + 2 * h, 16 + 2 * h + 1}, range(0, 8)); };
-                    if (b >= 5) pack_gemm(s, PREC_F16X2, wskip, 128, 256, {2 * h, 2 * h + 1}, range(8, 16));
-                    else vproj();
-                    pack_gemm(s, PREC_F16X2, in_w, 384, 128, qk_tiles, range(0, 4));
-                    if (b >= 5) vproj();
-                    pack_gemm(s, PREC_F16X2, in_w, 384, 128, qk_tiles, range(4, 8));
-                    outproj();
-                } else if (b >= 5) {
-                    pack_gemm(s, PREC_F16X2, wskip, 128, 256, {2 * h, 2 * h + 1}, range(0, 8));
-                }
-                f1(qa); f1(qb); f2(qa); f2(qb);
-            }
-            uint32_t& units = c->den_w8x_units[sgrp];
-            if (h == 0) units = (uint32_t)(s.size() / 64);
-            else if (s.size() / 64 != units) return fail(AMUSE_ESTATE, "internal: uneven 8-wave fp32x denoiser streams");
-            all.insert(all.end(), s.begin(), s.end());
-            if (sgrp == 0) all.insert(all.end(), s.begin(), s.begin() + (size_t)kRing8 * 64);  // ring wrap: tail = head
-        }
-        all.insert(all.end(), (size_t)kRing8 * 64, uint4{0, 0, 0, 0});   // the last B wave's initial ring fill reads past its slice
-        if (upload(&c->den_w8x, all.data(), all.size() * sizeof(uint4))) return AMUSE_EHIP;
+        if (int e = pack_sample8_streams(all, t.units, t.prec, D)) return e;
+        if (upload(c, t.slot, all.data(), all.size() * sizeof(uint4), t.prec, kUpdBit[t.prec])) return AMUSE_EHIP;
     }
     {
         auto pv = build_pvec(D, "encoder", false);
-        if (upload(&c->den_pvec, pv.data(), pv.size() * 4)) return AMUSE_EHIP;
-        if (upload(&c->den_pe, D.get("query_pos.pe"), 500 * 128 * 4)) return AMUSE_EHIP;
+        if (upload(c, &c->den_pvec, pv.data(), pv.size() * 4)) return AMUSE_EHIP;
+        if (upload(c, &c->den_pe, D.get("query_pos.pe"), 500 * 128 * 4)) return AMUSE_EHIP;
         float fr[128];
         for (int k = 0; k < 128; ++k) fr[k] = expf(-logf(10000.f) * (float)k / 128.f);
-        if (upload(&c->den_freqs, fr, sizeof(fr))) return AMUSE_EHIP;
-        auto w1t = transpose(D.get("time_embedding.linear_1.weight"), 128, 256);
-        auto w2t = transpose(D.get("time_embedding.linear_2.weight"), 128, 128);
-        if (upload(&c->te_w1t, w1t.data(), w1t.size() * 4) || upload(&c->te_w2t, w2t.data(), w2t.size() * 4) ||
-            upload(&c->te_b1, D.get("time_embedding.linear_1.bias"), 512) ||
-            upload(&c->te_b2, D.get("time_embedding.linear_2.bias"), 512))
-            return AMUSE_EHIP;
-        const char* names[3] = {"con", "emo", "sty"};
-        for (int n = 0; n < 3; ++n) {
-            auto wt = transpose(D.get(std::string("emb_proj_") + names[n] + ".1.weight"), 128, 256);
-            if (upload(&c->cond_wt[n], wt.data(), wt.size() * 4) ||
-                upload(&c->cond_b[n], D.get(std::string("emb_proj_") + names[n] + ".1.bias"), 512))
-                return AMUSE_EHIP;
-        }
+        if (upload(c, &c->den_freqs, fr, sizeof(fr), PREC_F32, kImgConst)) return AMUSE_EHIP;
     }
-    return 0;
+    return upload_embeddings(c, D);
 }
 
 int build_prior(amuse_ctx* c, const float* pri, int what = AMUSE_UPD_ALL) {
     static const ParamIndex PI = prior_index();
     if (!g_capture) c->vae_c1_valid[0] = c->vae_c1_valid[1] = c->vae_c1_valid[2] = c->vae_c1_valid[3] = false;   // block 0's hoisted constant belongs to the old decoder weights
     const Params Pp{PI, pri};
-    // ---- VAE decoder weight streams: [stage][wave][units]
+    const float *w_emb = Pp.get("skel_embedding.weight"), *w_final = Pp.get("final_layer.weight");
+    const bool enc = what & AMUSE_UPD_ENCODER;
+    const int X = PREC_F16X2, UX = AMUSE_UPD_F32X;
+    // ---- decoder.  Staged streams (pack_staged_stream): the blocks' stages, final_layer behind stage 9
     for (int prec = 0; prec < 4; ++prec) {
         if (!(what & kUpdBit[prec])) continue;
         std::vector<uint4> all;
-        for (int st = 0; st < kVaeStages; ++st) {
-            c->vae_stage_base[prec][st] = (uint32_t)(all.size() / 64);
-            size_t per_wave = 0;
-            for (int w = 0; w < 4; ++w) {
-                std::vector<uint4> s;
-                if (st >= 1) {
-                    const int b = st - 1;
-                    pack_outproj_ffn(s, prec, Pp, blk_name("decoder", b), w);
-                    if (b >= 4 && b <= 7) pack_skiplin(s, prec, Pp, "decoder", b - 4, w);
-                }
-                if (st < 9) pack_qkv(s, prec, Pp.get(blk_name("decoder", st) + ".self_attn.in_proj_weight"), w, false);
-                else pack_gemm(s, prec, Pp.get("final_layer.weight"), kFeats, 128, range(6 * w, 6 * w + 6), range(0, 8));
-                if (w == 0) per_wave = s.size();
-                else if (s.size() != per_wave) return fail(AMUSE_ESTATE, "internal: uneven vae wave streams");
-                all.insert(all.end(), s.begin(), s.end());
-            }
-            c->vae_stage_units[prec][st] = (uint32_t)(per_wave / 64);
-        }
-        all.insert(all.end(), (size_t)kVaeRing * 64, uint4{0, 0, 0, 0});  // the last wave's ring reads past its slice
-        if (upload(&c->vae_w[prec], all.data(), all.size() * sizeof(uint4))) return AMUSE_EHIP;
+        const auto content = [&](std::vector<uint4>& s, int st, int w) {
+            pack_skipnet_stage(s, prec, Pp, "decoder", st, w);
+            if (st == 9) pack_out_matrix_wave(s, prec, w_final, w);
+        };
+        if (int e = pack_staged_stream(all, c->vae_stage_base[prec], c->vae_stage_units[prec], content)) return e;
+        if (upload(c, &c->vae_w[prec], all.data(), all.size() * sizeof(uint4), prec, kUpdBit[prec])) return AMUSE_EHIP;
     }
-    if (what & AMUSE_UPD_F32X) {   // fp32x row stages, eight tiles per workgroup (k_vae_rows8.hip): per stage ONE stream in consumption order, 16-unit
-        // (8 hi | lo pairs) LDS stages: every stage is one k-pair x 8 output tiles, or - linear1 - 4 k-pairs x 2 output tiles
+    if (what & UX) {   // fp32x row stages without split-K: every stage
         std::vector<uint4> s;
-        for (int st = 0; st < kVaeStages; ++st) {
-            c->vae_w8x_base[st] = (uint32_t)(s.size() / 64);
-            if (st >= 1) {
-                const int b = st - 1;
-                const std::string p = blk_name("decoder", b);
-                pack_gemm(s, PREC_F16X2, Pp.get(p + ".self_attn.out_proj.weight"), 128, 128, range(0, 8), range(0, 8));
-                for (int ch = 0; ch < 16; ++ch) {
-                    pack_gemm(s, PREC_F16X2, Pp.get(p + ".linear1.weight"), 512, 128, {2 * ch, 2 * ch + 1}, range(0, 8));
-                    pack_gemm(s, PREC_F16X2, Pp.get(p + ".linear2.weight"), 128, 512, range(0, 8), {2 * ch, 2 * ch + 1});
-                }
-                if (b >= 4 && b <= 7) {   // the skip linear ahead of output block b + 1: the x half, then the popped-skip half
-                    const float* wskip = Pp.get("decoder.linear_blocks." + std::to_string(b - 4) + ".weight");
-                    pack_gemm(s, PREC_F16X2, wskip, 128, 256, range(0, 8), range(0, 8));
-                    pack_gemm(s, PREC_F16X2, wskip, 128, 256, range(0, 8), range(8, 16));
-                }
-            }
-            if (st < 9) {
-                const float* in_w = Pp.get(blk_name("decoder", st) + ".self_attn.in_proj_weight");
-                for (int grp = 0; grp < 3; ++grp) pack_gemm(s, PREC_F16X2, in_w, 384, 128, range(8 * grp, 8 * grp + 8), range(0, 8));
-            } else {
-                for (int q = 0; q < 4; ++q) pack_gemm(s, PREC_F16X2, Pp.get("final_layer.weight"), kFeats, 128, range(6 * q, 6 * q + 6), range(0, 8));
-            }
-            if (s.size() % ((size_t)16 * 64) != 0) return fail(AMUSE_ESTATE, "internal: rows8 stream is not whole stages");
-        }
-        s.insert(s.end(), (size_t)2 * 16 * 64, uint4{0, 0, 0, 0});   // the fetch runs two stages ahead
-        if (upload(&c->vae_w8x, s.data(), s.size() * sizeof(uint4))) return AMUSE_EHIP;
+        if (int e = pack_rows8_stream(s, c->vae_w8x_base, Pp, "decoder", 0, 9, w_final)) return e;
+        if (upload(c, &c->vae_w8x, s.data(), s.size() * sizeof(uint4), X, UX)) return AMUSE_EHIP;
     }
-    if (what & AMUSE_UPD_F32X) {   // fp32x fused decoder (k_vae_fusedx.hip): ONE stream of unit pairs for the clip's eight waves, in consumption order, 16-unit stages
+    if (what & UX) {   // fp32x per-clip decoder
         std::vector<uint4> s;
-        for (int b = 0; b < 9; ++b) {
-            const std::string p = blk_name("decoder", b);
-            if (b >= 5) {   // skip linear ahead of an output block: the x half (k-pairs 0..3), then the popped-skip half
-                const float* wskip = Pp.get("decoder.linear_blocks." + std::to_string(b - 5) + ".weight");
-                pack_gemm(s, PREC_F16X2, wskip, 128, 256, range(0, 8), range(0, 8));
-                pack_gemm(s, PREC_F16X2, wskip, 128, 256, range(0, 8), range(8, 16));
-            }
-            const float* in_w = Pp.get(p + ".self_attn.in_proj_weight");
-            for (int h = 0; h < 4; ++h) {   // per head: k | v tiles per k-pair (two stages), then q (one stage)
-                pack_gemm(s, PREC_F16X2, in_w, 384, 128, {8 + 2 * h, 8 + 2 * h + 1, 16 + 2 * h, 16 + 2 * h + 1}, range(0, 8));
-                pack_gemm(s, PREC_F16X2, in_w, 384, 128, {2 * h, 2 * h + 1}, range(0, 8));
-            }
-            pack_gemm(s, PREC_F16X2, Pp.get(p + ".self_attn.out_proj.weight"), 128, 128, range(0, 8), range(0, 8));
-            // FFN in 16 chunks of 32 hidden features, linear1 one chunk ahead: linear1(0), 15 x [linear1(ch + 1), linear2(ch)], linear2(15)
-            const auto f1 = [&](int ch) { pack_gemm(s, PREC_F16X2, Pp.get(p + ".linear1.weight"), 512, 128, {2 * ch, 2 * ch + 1}, range(0, 8)); };
-            const auto f2 = [&](int ch) { pack_gemm(s, PREC_F16X2, Pp.get(p + ".linear2.weight"), 128, 512, range(0, 8), {2 * ch, 2 * ch + 1}); };
-            f1(0);
-            for (int ch = 0; ch < 15; ++ch) { f1(ch + 1); f2(ch); }
-            f2(15);
-        }
-        for (int q = 0; q < 4; ++q) pack_gemm(s, PREC_F16X2, Pp.get("final_layer.weight"), kFeats, 128, range(6 * q, 6 * q + 6), range(0, 8));
-        if (s.size() % ((size_t)16 * 64) != 0) return fail(AMUSE_ESTATE, "internal: fused fp32x decode stream is not whole stages");
-        s.insert(s.end(), (size_t)2 * 16 * 64, uint4{0, 0, 0, 0});   // the fetch runs two stages ahead
-        if (upload(&c->vae_wfx, s.data(), s.size() * sizeof(uint4))) return AMUSE_EHIP;
+        if (int e = pack_fusedx_stream(s, Pp, "decoder", nullptr, w_final)) return e;
+        if (upload(c, &c->vae_wfx, s.data(), s.size() * sizeof(uint4), X, UX)) return AMUSE_EHIP;
     }
-    for (const int p16 : {PREC_BF16, PREC_F16}) {   // fused decode kernel (k_vae_fused.hip; bf16 / fp16 operands): ONE stream for the four waves, in consumption order, cut
+    for (const int p16 : {PREC_BF16, PREC_F16}) {   // 16-bit fused per-clip decoder
         if (!(what & kUpdBit[p16])) continue;
-        // into stages of kVaeFusedStageUnits units (every phase below is a whole number of stages)
         std::vector<uint4> s;
-        const auto pad = [&](int units) { s.insert(s.end(), (size_t)units * 64, uint4{0, 0, 0, 0}); };
-        for (int b = 0; b < 9; ++b) {
-            const std::string p = blk_name("decoder", b);
-            if (b >= 5) {   // skip linear ahead of an output block: the x half (k-tiles 0..7), then the popped-skip half
-                const float* wskip = Pp.get("decoder.linear_blocks." + std::to_string(b - 5) + ".weight");
-                pack_gemm(s, p16, wskip, 128, 256, range(0, 8), range(0, 8));
-                pack_gemm(s, p16, wskip, 128, 256, range(0, 8), range(8, 16));
-            }
-            const float* in_w = Pp.get(p + ".self_attn.in_proj_weight");
-            for (int h = 0; h < 4; ++h) {   // per head: stage A = k | v tiles per k-pair; stage B = q, out_proj's k-slice
-                pack_gemm(s, p16, in_w, 384, 128, {8 + 2 * h, 8 + 2 * h + 1, 16 + 2 * h, 16 + 2 * h + 1}, range(0, 8));
-                pack_gemm(s, p16, in_w, 384, 128, {2 * h, 2 * h + 1}, range(0, 8));
-                pack_gemm(s, p16, Pp.get(p + ".self_attn.out_proj.weight"), 128, 128, range(0, 8), {2 * h, 2 * h + 1});
-            }
-            // FFN in 16 chunks of 32 hidden features, software-pipelined: [linear1(0) | pad], 15 x [linear1(i + 1) | linear2(i)],
-            // [linear2(15) | pad]
-            const auto f1 = [&](int ch) { pack_gemm(s, p16, Pp.get(p + ".linear1.weight"), 512, 128, {2 * ch, 2 * ch + 1}, range(0, 8)); };
-            const auto f2 = [&](int ch) { pack_gemm(s, p16, Pp.get(p + ".linear2.weight"), 128, 512, range(0, 8), {2 * ch, 2 * ch + 1}); };
-            f1(0); pad(8);
-            for (int ch = 0; ch < 15; ++ch) { f1(ch + 1); f2(ch); }
-            f2(15); pad(8);
-        }
-        for (int half = 0; half < 2; ++half)   // final_layer ONCE: 24 output tiles in two halves of 48 units (k-pair outer) - the kernel's last stage holds it in LDS whole
-            pack_gemm(s, p16, Pp.get("final_layer.weight"), kFeats, 128, range(12 * half, 12 * half + 12), range(0, 8));
-        if (s.size() % ((size_t)kVaeFusedStageUnits * 64) != 0) return fail(AMUSE_ESTATE, "internal: fused decode stream is not whole stages");
-        pad(2 * kVaeFusedStageUnits);   // the fetch runs two stages ahead
-        if (upload(p16 == PREC_BF16 ? &c->vae_wf : &c->vae_wfh, s.data(), s.size() * sizeof(uint4))) return AMUSE_EHIP;
+        if (int e = pack_fused16_stream(s, p16, Pp, "decoder", nullptr, w_final)) return e;
+        if (upload(c, p16 == PREC_BF16 ? &c->vae_wf : &c->vae_wfh, s.data(), s.size() * sizeof(uint4), p16, kUpdBit[p16])) return AMUSE_EHIP;
     }
     {
         auto pv = build_pvec(Pp, "decoder", true);
-        if (upload(&c->vae_pvec, pv.data(), pv.size() * 4)) return AMUSE_EHIP;
+        if (upload(c, &c->vae_pvec, pv.data(), pv.size() * 4)) return AMUSE_EHIP;
         std::vector<float> fb(16 * kFeatTiles, 0.f);
         memcpy(fb.data(), Pp.get("final_layer.bias"), kFeats * 4);
-        if (upload(&c->vae_final_bias, fb.data(), fb.size() * 4)) return AMUSE_EHIP;
-        if (upload(&c->vae_pe, Pp.get("query_pos_decoder.pe"), 500 * 128 * 4)) return AMUSE_EHIP;
+        if (upload(c, &c->vae_final_bias, fb.data(), fb.size() * 4)) return AMUSE_EHIP;
+        if (upload(c, &c->vae_pe, Pp.get("query_pos_decoder.pe"), 500 * 128 * 4)) return AMUSE_EHIP;
         std::vector<float> wv_t(9 * 128 * 128), wo_t(9 * 128 * 128), bv(9 * 128), bo(9 * 128);
         for (int b = 0; b < 9; ++b) {
             const std::string p = blk_name("decoder", b) + ".multihead_attn";
@@ -290,95 +117,37 @@ int build_prior(amuse_ctx* c, const float* pri, int what = AMUSE_UPD_ALL) {
             memcpy(bv.data() + b * 128, Pp.get(p + ".in_proj_bias") + 256, 512);
             memcpy(bo.data() + b * 128, Pp.get(p + ".out_proj.bias"), 512);
         }
-        if (upload(&c->vae_wv_t, wv_t.data(), wv_t.size() * 4) || upload(&c->vae_wo_t, wo_t.data(), wo_t.size() * 4) ||
-            upload(&c->vae_bv, bv.data(), bv.size() * 4) || upload(&c->vae_bo, bo.data(), bo.size() * 4))
+        if (upload(c, &c->vae_wv_t, wv_t.data(), wv_t.size() * 4) || upload(c, &c->vae_wo_t, wo_t.data(), wo_t.size() * 4) ||
+            upload(c, &c->vae_bv, bv.data(), bv.size() * 4) || upload(c, &c->vae_bo, bo.data(), bo.size() * 4))
             return AMUSE_EHIP;
     }
-    // ---- VAE encoder weight streams: stage 0 = skel_embedding (K = 333 padded to 22 k-tiles, 2 output tiles per wave)
-    // + in_proj(0); stage i+1 = post-attention of block i (+ skip linear) + in_proj(i+1); stage 9 = post-attention of block 8
+    // ---- encoder (AMUSE_UPD_ENCODER).  Staged streams: skel_embedding in front of stage 0, nothing behind stage 9
     for (int prec = 0; prec < 4; ++prec) {
-        if (!(what & kUpdBit[prec]) || !(what & AMUSE_UPD_ENCODER)) continue;
+        if (!(what & kUpdBit[prec]) || !enc) continue;
         std::vector<uint4> all;
-        for (int st = 0; st < kVaeStages; ++st) {
-            c->vaee_stage_base[prec][st] = (uint32_t)(all.size() / 64);
-            size_t per_wave = 0;
-            for (int w = 0; w < 4; ++w) {
-                std::vector<uint4> s;
-                if (st == 0) pack_gemm(s, prec, Pp.get("skel_embedding.weight"), 128, kFeats, {2 * w, 2 * w + 1}, range(0, 22));
-                if (st >= 1) {
-                    const int b = st - 1;
-                    pack_outproj_ffn(s, prec, Pp, blk_name("encoder", b), w);
-                    if (b >= 4 && b <= 7) pack_skiplin(s, prec, Pp, "encoder", b - 4, w);
-                }
-                if (st < 9) pack_qkv(s, prec, Pp.get(blk_name("encoder", st) + ".self_attn.in_proj_weight"), w, false);
-                if (w == 0) per_wave = s.size();
-                else if (s.size() != per_wave) return fail(AMUSE_ESTATE, "internal: uneven vae encoder wave streams");
-                all.insert(all.end(), s.begin(), s.end());
-            }
-            c->vaee_stage_units[prec][st] = (uint32_t)(per_wave / 64);
-        }
-        all.insert(all.end(), (size_t)kVaeRing * 64, uint4{0, 0, 0, 0});
-        if (upload(&c->vaee_w[prec], all.data(), all.size() * sizeof(uint4))) return AMUSE_EHIP;
+        const auto content = [&](std::vector<uint4>& s, int st, int w) {
+            if (st == 0) pack_in_matrix_wave(s, prec, w_emb, w);
+            pack_skipnet_stage(s, prec, Pp, "encoder", st, w);
+        };
+        if (int e = pack_staged_stream(all, c->vaee_stage_base[prec], c->vaee_stage_units[prec], content)) return e;
+        if (upload(c, &c->vaee_w[prec], all.data(), all.size() * sizeof(uint4), prec, kUpdBit[prec] | AMUSE_UPD_ENCODER)) return AMUSE_EHIP;
     }
-    if ((what & AMUSE_UPD_F32X) && (what & AMUSE_UPD_ENCODER)) {   // encode's stages 1..9 for the fp32x row kernel without split-K (the decoder's stream layout above)
+    if ((what & UX) && enc) {   // fp32x row stages without split-K: stages 1..9 (the embedding stage stays with k_vae_rows<f16x2, M_ENC>)
         std::vector<uint4> s;
-        for (int st = 0; st < kVaeStages; ++st) {
-            c->vaee_w8x_base[st] = (uint32_t)(s.size() / 64);
-            if (st == 0) continue;   // (the embedding stage stays with k_vae_rows<f16x2, M_ENC>)
-            const int b = st - 1;
-            const std::string p = blk_name("encoder", b);
-            pack_gemm(s, PREC_F16X2, Pp.get(p + ".self_attn.out_proj.weight"), 128, 128, range(0, 8), range(0, 8));
-            for (int ch = 0; ch < 16; ++ch) {
-                pack_gemm(s, PREC_F16X2, Pp.get(p + ".linear1.weight"), 512, 128, {2 * ch, 2 * ch + 1}, range(0, 8));
-                pack_gemm(s, PREC_F16X2, Pp.get(p + ".linear2.weight"), 128, 512, range(0, 8), {2 * ch, 2 * ch + 1});
-            }
-            if (b >= 4 && b <= 7) {
-                const float* wskip = Pp.get("encoder.linear_blocks." + std::to_string(b - 4) + ".weight");
-                pack_gemm(s, PREC_F16X2, wskip, 128, 256, range(0, 8), range(0, 8));
-                pack_gemm(s, PREC_F16X2, wskip, 128, 256, range(0, 8), range(8, 16));
-            }
-            if (st < 9) {
-                const float* in_w = Pp.get(blk_name("encoder", st) + ".self_attn.in_proj_weight");
-                for (int grp = 0; grp < 3; ++grp) pack_gemm(s, PREC_F16X2, in_w, 384, 128, range(8 * grp, 8 * grp + 8), range(0, 8));
-            }
-            if (s.size() % ((size_t)16 * 64) != 0) return fail(AMUSE_ESTATE, "internal: rows8 encoder stream is not whole stages");
-        }
-        s.insert(s.end(), (size_t)2 * 16 * 64, uint4{0, 0, 0, 0});   // the fetch runs two stages ahead
-        if (upload(&c->vaee_w8x, s.data(), s.size() * sizeof(uint4))) return AMUSE_EHIP;
+        if (int e = pack_rows8_stream(s, c->vaee_w8x_base, Pp, "encoder", 1, 9, nullptr)) return e;
+        if (upload(c, &c->vaee_w8x, s.data(), s.size() * sizeof(uint4), X, UX | AMUSE_UPD_ENCODER)) return AMUSE_EHIP;
     }
-    if ((what & AMUSE_UPD_F32X) && (what & AMUSE_UPD_ENCODER)) {   // encode as one persistent workgroup per clip (k_vae_fusedx.hip k_den_fusedx<encode>): skel_embedding, then
-        // the nine encoder blocks in the fused fp32x decoder's order
+    if ((what & UX) && enc) {   // fp32x per-clip encoder (k_den_fusedx<encode>): skel_embedding in front, no output matrix
         std::vector<uint4> s;
-        pack_gemm(s, PREC_F16X2, Pp.get("skel_embedding.weight"), 128, kFeats, range(0, 8), range(0, 22));
-        for (int b = 0; b < 9; ++b) {
-            const std::string p = blk_name("encoder", b);
-            if (b >= 5) {
-                const float* wskip = Pp.get("encoder.linear_blocks." + std::to_string(b - 5) + ".weight");
-                pack_gemm(s, PREC_F16X2, wskip, 128, 256, range(0, 8), range(0, 8));
-                pack_gemm(s, PREC_F16X2, wskip, 128, 256, range(0, 8), range(8, 16));
-            }
-            const float* in_w = Pp.get(p + ".self_attn.in_proj_weight");
-            for (int h = 0; h < 4; ++h) {
-                pack_gemm(s, PREC_F16X2, in_w, 384, 128, {8 + 2 * h, 8 + 2 * h + 1, 16 + 2 * h, 16 + 2 * h + 1}, range(0, 8));
-                pack_gemm(s, PREC_F16X2, in_w, 384, 128, {2 * h, 2 * h + 1}, range(0, 8));
-            }
-            pack_gemm(s, PREC_F16X2, Pp.get(p + ".self_attn.out_proj.weight"), 128, 128, range(0, 8), range(0, 8));
-            const auto f1 = [&](int ch) { pack_gemm(s, PREC_F16X2, Pp.get(p + ".linear1.weight"), 512, 128, {2 * ch, 2 * ch + 1}, range(0, 8)); };
-            const auto f2 = [&](int ch) { pack_gemm(s, PREC_F16X2, Pp.get(p + ".linear2.weight"), 128, 512, range(0, 8), {2 * ch, 2 * ch + 1}); };
-            f1(0);
-            for (int ch = 0; ch < 15; ++ch) { f1(ch + 1); f2(ch); }
-            f2(15);
-        }
-        if (s.size() % ((size_t)16 * 64) != 0) return fail(AMUSE_ESTATE, "internal: fused fp32x encoder stream is not whole stages");
-        s.insert(s.end(), (size_t)2 * 16 * 64, uint4{0, 0, 0, 0});   // the fetch runs two stages ahead
-        if (upload(&c->vaee_wfx, s.data(), s.size() * sizeof(uint4))) return AMUSE_EHIP;
+        if (int e = pack_fusedx_stream(s, Pp, "encoder", w_emb, nullptr)) return e;
+        if (upload(c, &c->vaee_wfx, s.data(), s.size() * sizeof(uint4), X, UX | AMUSE_UPD_ENCODER)) return AMUSE_EHIP;
     }
     {
         auto pv = build_pvec(Pp, "encoder", false);
-        if (upload(&c->vaee_pvec, pv.data(), pv.size() * 4) ||
-            upload(&c->vaee_pe, Pp.get("query_pos_encoder.pe"), 500 * 128 * 4) ||
-            upload(&c->vaee_tok, Pp.get("global_motion_token"), 2 * 128 * 4) ||
-            upload(&c->vaee_emb_bias, Pp.get("skel_embedding.bias"), 128 * 4))
+        if (upload(c, &c->vaee_pvec, pv.data(), pv.size() * 4) ||
+            upload(c, &c->vaee_pe, Pp.get("query_pos_encoder.pe"), 500 * 128 * 4) ||
+            upload(c, &c->vaee_tok, Pp.get("global_motion_token"), 2 * 128 * 4) ||
+            upload(c, &c->vaee_emb_bias, Pp.get("skel_embedding.bias"), 128 * 4))
             return AMUSE_EHIP;
     }
     return 0;
@@ -426,7 +195,7 @@ int pick_group(amuse_ctx* c, int B, int S) {
 // kernel choice for one sampling launch: fp32 -> the 4-wave parity kernel (k_sampler.hip); fp32x / bf16 / fp16 -> the 8-wave kernels
 bool use_sample8(int precision) { return precision != PREC_F32; }
 void set_stream(const amuse_ctx* c, SampleArgs& a, int precision) {
-    if (precision < 3) { a.wstream = c->den_w[precision]; a.wave_units = c->den_wave_units[precision]; }
+    if (precision == PREC_F32) { a.wstream = c->den_w; a.wave_units = c->den_wave_units; }
     a.wave_units_a = c->den_w8_units[0]; a.wave_units_b = c->den_w8_units[1];
 }
 hipError_t dispatch_sample(amuse_ctx* c, SampleArgs& a, int precision, hipStream_t st) {
@@ -577,20 +346,12 @@ int amuse_update_weights(amuse_ctx* c, const float* denoiser_params, size_t n_de
 
 namespace {
 // The gather maps.  Every image the builders upload is a permutation of parameters plus zero padding (the one exception,
-// the timestep frequencies, does not depend on the parameters and is skipped), so three builder runs on probe parameters - byte k
+// the timestep frequencies, is uploaded as kImgConst and never captured), so three builder runs on probe parameters - byte k
 // of (index + 1), a value bf16 holds exactly - spell out, per image element, which parameter it carries.
 int build_repack_maps(amuse_ctx* c) {
-    struct Img { std::vector<int> map; bool prior; };
+    struct Img { std::vector<int> map; bool prior; int kind, cls; };   // kind / cls: as the builder classified the image (upload, amuse_host.hpp)
     std::map<void**, Img> imgs;
     std::vector<float> den(AMUSE_DENOISER_PARAMS), pri(AMUSE_PRIOR_PARAMS);
-    // element type of an image: 0 = fp32, 1 = bf16, 2 = split-fp16, 3 = fp16 (launch_repack's `kind`)
-    auto kind_of = [&](void** slot) {
-        if (slot == (void**)&c->den_w[PREC_F16X2] || slot == (void**)&c->den_w8x || slot == (void**)&c->vae_w[PREC_F16X2] ||
-            slot == (void**)&c->vaee_w[PREC_F16X2] || slot == (void**)&c->vae_w8x || slot == (void**)&c->vaee_w8x || slot == (void**)&c->vae_wfx || slot == (void**)&c->vaee_wfx) return 2;
-        if (slot == (void**)&c->den_w8h || slot == (void**)&c->vae_wfh || slot == (void**)&c->vae_w[PREC_F16] || slot == (void**)&c->vaee_w[PREC_F16]) return 3;
-        return (slot == (void**)&c->den_w[PREC_BF16] || slot == (void**)&c->den_w8 || slot == (void**)&c->vae_w[PREC_BF16] ||
-                slot == (void**)&c->vae_wf || slot == (void**)&c->vaee_w[PREC_BF16]) ? 1 : 0;
-    };
     for (int k = 0; k < 3; ++k) {
         for (size_t i = 0; i < den.size(); ++i) den[i] = (float)(((i + 1) >> (8 * k)) & 255);
         for (size_t i = 0; i < pri.size(); ++i) pri[i] = (float)(((i + 1) >> (8 * k)) & 255);
@@ -603,25 +364,25 @@ int build_repack_maps(amuse_ctx* c) {
             g_capture = nullptr;
             if (rc) return rc;
             for (auto& kv : cap.bufs) {
-                if (kv.first == (void**)&c->den_freqs) continue;
-                const int kind = kind_of(kv.first);
-                const size_t n = kv.second.size() / (kind ? 2 : 4);
+                const std::vector<unsigned char>& bytes = kv.second.bytes;
+                const int kind = kv.second.kind;
+                const size_t n = bytes.size() / (kind ? 2 : 4);
                 Img& im = imgs[kv.first];
-                if (k == 0) { im.map.assign(n, 0); im.prior = which == 1; }
+                if (k == 0) { im.map.assign(n, 0); im.prior = which == 1; im.kind = kind; im.cls = kv.second.cls; }
                 else if (im.map.size() != n) return fail(AMUSE_ESTATE, "internal: packed image changed size between probe runs");
                 for (size_t j = 0; j < n; ++j) {
                     float v;
                     if (kind == 1) {
                         uint16_t h;
-                        memcpy(&h, kv.second.data() + 2 * j, 2);
+                        memcpy(&h, bytes.data() + 2 * j, 2);
                         const uint32_t u = (uint32_t)h << 16;
                         memcpy(&v, &u, 4);
                     } else if (kind == 2 || kind == 3) {
                         uint16_t h;
-                        memcpy(&h, kv.second.data() + 2 * j, 2);
+                        memcpy(&h, bytes.data() + 2 * j, 2);
                         v = h2f(h);
                     } else {
-                        memcpy(&v, kv.second.data() + 4 * j, 4);
+                        memcpy(&v, bytes.data() + 4 * j, 4);
                     }
                     if (!(v >= 0.f && v <= 255.f && v == (float)(int)v)) return fail(AMUSE_ESTATE, "internal: a packed image is not a gather of the parameters");
                     im.map[j] |= (int)v << (8 * k);
@@ -634,20 +395,11 @@ int build_repack_maps(amuse_ctx* c) {
         const size_t limit = kv.second.prior ? AMUSE_PRIOR_PARAMS : AMUSE_DENOISER_PARAMS;
         for (int m : kv.second.map)
             if (m < 0 || (size_t)m > limit) return fail(AMUSE_ESTATE, "internal: gather index out of range");
-        int cls = 0;   // which AMUSE_UPD_* bits the image needs; 0 = small parameters, always replaced
-        if (slot == (void**)&c->den_w[PREC_F32] || slot == (void**)&c->vae_w[PREC_F32]) cls = AMUSE_UPD_F32;
-        else if (slot == (void**)&c->den_w[PREC_F16X2] || slot == (void**)&c->den_w8x || slot == (void**)&c->vae_w[PREC_F16X2] || slot == (void**)&c->vae_w8x || slot == (void**)&c->vae_wfx) cls = AMUSE_UPD_F32X;
-        else if (slot == (void**)&c->vaee_w[PREC_F16X2] || slot == (void**)&c->vaee_w8x || slot == (void**)&c->vaee_wfx) cls = AMUSE_UPD_F32X | AMUSE_UPD_ENCODER;
-        else if (slot == (void**)&c->den_w8h || slot == (void**)&c->vae_wfh || slot == (void**)&c->vae_w[PREC_F16]) cls = AMUSE_UPD_F16;
-        else if (slot == (void**)&c->vaee_w[PREC_F16]) cls = AMUSE_UPD_F16 | AMUSE_UPD_ENCODER;
-        else if (slot == (void**)&c->den_w[PREC_BF16] || slot == (void**)&c->den_w8 || slot == (void**)&c->vae_w[PREC_BF16] || slot == (void**)&c->vae_wf) cls = AMUSE_UPD_BF16;
-        else if (slot == (void**)&c->vaee_w[PREC_F32]) cls = AMUSE_UPD_F32 | AMUSE_UPD_ENCODER;
-        else if (slot == (void**)&c->vaee_w[PREC_BF16]) cls = AMUSE_UPD_BF16 | AMUSE_UPD_ENCODER;
         int* dmap = nullptr;
         HIP_TRY(hipMalloc((void**)&dmap, kv.second.map.size() * sizeof(int)));
         c->owned.push_back(dmap);
         HIP_TRY(hipMemcpy(dmap, kv.second.map.data(), kv.second.map.size() * sizeof(int), hipMemcpyHostToDevice));
-        c->repack.push_back({slot, dmap, kv.second.map.size(), kv.second.prior ? 1 : 0, kind_of(slot), cls});
+        c->repack.push_back({slot, dmap, kv.second.map.size(), kv.second.prior ? 1 : 0, kv.second.kind, kv.second.cls});
     }
     return 0;
 }
@@ -664,7 +416,7 @@ int amuse_update_weights_device(amuse_ctx* c, const float* denoiser_params_dev, 
     if (prior_params_dev) c->vae_c1_valid[0] = c->vae_c1_valid[1] = c->vae_c1_valid[2] = c->vae_c1_valid[3] = false;
     for (const auto& r : c->repack) {
         const float* src = r.prior ? prior_params_dev : denoiser_params_dev;
-        if (!src || !*r.slot) continue;                 // (an image the context never built, e.g. the 4-wave bf16 stream after an update)
+        if (!src) continue;                             // (only one of the two parameter arrays given)
         if ((r.cls & what) != r.cls) continue;          // every bit the image needs must be requested
         HIP_TRY(launch_repack(src, r.map, *r.slot, r.n, r.kind, (hipStream_t)stream));
     }
@@ -682,12 +434,9 @@ void amuse_destroy(amuse_ctx* c) {
     variant_destroy(c);
     for (void* p : c->owned)
         if (p) (void)hipFree(p);
-    void* ptrs[] = {c->den_w[0], c->den_w[1], c->den_w[2], c->den_w8, c->den_w8h, c->den_w8x, c->vae_wfh, c->den_pvec, c->den_pe, c->den_freqs, c->te_w1t, c->te_b1, c->te_w2t,
-                    c->te_b2, c->cond_wt[0], c->cond_wt[1], c->cond_wt[2], c->cond_b[0], c->cond_b[1], c->cond_b[2],
-                    c->vae_w[0], c->vae_w[1], c->vae_w[2], c->vae_w[3], c->vae_w8x, c->vae_wfx, c->vaee_w8x, c->vaee_wfx, c->vaee_w[2], c->vaee_w[3], c->vae_pvec, c->vae_final_bias, c->vae_pe, c->vae_wv_t, c->vae_bv,
-                    c->vae_wo_t, c->vae_bo, c->vaee_w[0], c->vaee_w[1], c->vaee_pvec, c->vaee_pe, c->vaee_tok,
-                    c->vaee_emb_bias, c->d_timesteps, c->d_coef, c->d_time_tok, c->d_ts1, c->d_tt1, c->d_coef1,
-                    c->cond_tok, c->lat_tmp, c->fwd_ws, c->vae_ws, c->d_lengths, c->vae_wf, c->vae_skip, c->vae_ca_ws, c->vae_c1[0], c->vae_c1[1], c->vae_c1[2], c->vae_c1[3]};
+    // (the weight images are in `owned`: upload() put them there)  schedule buffers and workspaces:
+    void* ptrs[] = {c->d_timesteps, c->d_coef, c->d_time_tok, c->d_ts1, c->d_tt1, c->d_coef1, c->cond_tok, c->lat_tmp, c->fwd_ws, c->vae_ws, c->d_lengths,
+                    c->vae_skip, c->vae_ca_ws, c->vae_c1[0], c->vae_c1[1], c->vae_c1[2], c->vae_c1[3]};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     for (hipEvent_t e : c->vae_c1_ev)

@@ -218,7 +218,7 @@ hipError_t launch_vae_attn(const VaeAttnArgs& a, int precision, int mode, hipStr
 constexpr int kVaeFusedStageUnits = 16;   // the weight stream is consumed in 16 KiB stages (LDS-DMA ring of three)
 constexpr int kVaeFusedLdsBytes = 40960 + 3 * 16384 + 2 * 8192 + 5120;   // K/V images of one head | weight ring | block params | ca
 struct VaeFusedArgs {
-    const uint4* wstream;      // bf16 stream in consumption order, whole stages (amuse_api.hip), shared by the 4 waves
+    const uint4* wstream;      // bf16 stream in consumption order, whole stages (amuse_pack.hpp pack_fused16_stream), shared by the 4 waves
     const float* pvec;         // decoder small params, PV_* layout
     const float* final_bias;   // [384]
     const float* pe;           // query_pos_decoder.pe [500][128]
@@ -239,7 +239,7 @@ hipError_t launch_vae_fused(const VaeFusedArgs& a, hipStream_t stream);
 hipError_t launch_vae_fusedh(const VaeFusedArgs& a, hipStream_t stream);   // fp16 operands (AMUSE_PREC_F16, k_vae_fusedh.hip)
 // fp32x form of the fused decoder (k_vae_fusedx.hip): split-fp16 operands, the staged fp32x path's arithmetic bit for bit; its scratch arrays are the staged path's
 struct VaeFusedXArgs {
-    const uint4* wstream;      // unit pairs (hi | lo) in consumption order, whole 16 KiB stages (amuse_api.hip)
+    const uint4* wstream;      // unit pairs (hi | lo) in consumption order, whole 16 KiB stages (amuse_pack.hpp pack_fusedx_stream)
     const float* pvec;         // decoder small params, PV_* layout
     const float* final_bias;   // [384]
     const float* pe;           // query_pos_decoder.pe [500][128]
@@ -260,7 +260,7 @@ hipError_t launch_vae_fusedx(const VaeFusedXArgs& a, hipStream_t stream);
 // of x_t, the condition tokens in front, nine encoder blocks (the decode kernel's two block halves with an encoder layer), encoder.norm, pose_proj, the mask, eps_hat and -
 // with coefficients - the scheduler update of x_t in the parity modes' arithmetic (k_vae.hip's last stage).  Scratch: the staged step's attn_o and skip arrays.
 struct DenFusedXArgs {
-    const uint4* wstream;      // unit pairs in consumption order, whole 16 KiB stages (amuse_variants.hip)
+    const uint4* wstream;      // unit pairs in consumption order, whole 16 KiB stages (amuse_pack.hpp pack_fusedx_stream)
     const float* pvec;         // the variant's small parameters, PV_* layout
     const float* emb_bias;     // pose_embd.bias [128]
     const float* final_bias;   // pose_proj.bias padded to [384]
@@ -286,7 +286,7 @@ struct DenFusedXArgs {
 hipError_t launch_den_fusedx(const DenFusedXArgs& a, hipStream_t stream);
 // ---------------------------------------------------------------- fused pose-space denoiser step (k_den_fused.hip): one workgroup per clip
 struct DenFusedArgs {
-    const uint4* wstream;      // 16-bit stream in consumption order, whole stages (amuse_variants.hip)
+    const uint4* wstream;      // 16-bit stream in consumption order, whole stages (amuse_pack.hpp pack_fused16_stream)
     const float* pvec;         // encoder small params, PV_* layout
     const float* final_bias;   // pose_proj.bias padded to [384]
     const float* emb_bias;     // pose_embd.bias [128]

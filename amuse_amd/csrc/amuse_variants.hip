@@ -1,6 +1,7 @@
 // Denoiser variants (reference models/latent_diffusion/denoiser.py:64-66,92-131,174-204): host side - state-dict index, weight
 // streams, hoisted tables, launch sequences.  Kernels: k_sampler_dec.hip (arch "trans_dec", latent sample: persistent T-step kernel),
 // k_vae.hip M_DEN_E / M_DEN_D (diffusion_only: one step = the staged rows / attention kernels at S = 304 / 300), k_misc.hip prologues.
+#include "amuse_pack.hpp"
 #include "amuse_variants.hpp"
 
 struct amuse_variant {
@@ -33,7 +34,6 @@ constexpr int kTkv = kLayers * 2 * kD;        // floats of one token's K / V ove
 constexpr int kPoseRowsMax = kFrames + 4;
 constexpr size_t kPoseWsPerClip = (size_t)kPoseRowsMax * kD * (1 + 3 + 1 + 4);
 constexpr int kPoseChunk = 256;
-constexpr int kUpdBitV[4] = {AMUSE_UPD_F32, AMUSE_UPD_BF16, AMUSE_UPD_F32X, AMUSE_UPD_F16};
 
 bool arch_dec(int arch) { return arch & 1; }
 bool arch_pose(int arch) { return arch & 2; }
@@ -243,150 +243,60 @@ int variant_build(amuse_ctx* c, const float* den, int what) {
     const int arch = c->arch;
     const Params D{index_of(arch), den};
     const bool dec = arch_dec(arch), pose = arch_pose(arch);
-    if (!pose) {   // arch DEC: the persistent kernel's per-wave streams, one pass over the nine layers per step
+    if (!pose) {   // arch DEC: the persistent kernel's per-wave ring streams (pack_ring4_stream), one pass over the nine layers per step
         for (int prec = 0; prec < 4; ++prec) {
-            if (!(what & kUpdBitV[prec])) continue;
+            if (!(what & kUpdBit[prec])) continue;
             std::vector<uint4> all;
-            size_t per_wave = 0;
-            for (int w = 0; w < 4; ++w) {
-                std::vector<uint4> s;
+            const auto pass = [&](std::vector<uint4>& s, int w) {
                 for (int l = 0; l < kLayers; ++l) pack_dec_layer(s, prec, D, l, w, true);
-                if (w == 0) per_wave = s.size();
-                else if (s.size() != per_wave) return fail(AMUSE_ESTATE, "internal: uneven trans_dec wave streams");
-                all.insert(all.end(), s.begin(), s.end());
-                all.insert(all.end(), s.begin(), s.begin() + (size_t)kRing * 64);   // ring wrap: tail = head
-            }
-            v->dec_units[prec] = (uint32_t)(per_wave / 64);
+            };
+            if (int e = pack_ring4_stream(all, &v->dec_units[prec], pass)) return e;
             if (v->dec_units[prec] % kRing) return fail(AMUSE_ESTATE, "internal: a trans_dec step is not whole ring revolutions");
-            if (upload(&v->dec_w[prec], all.data(), all.size() * sizeof(uint4))) return AMUSE_EHIP;
+            if (upload(c, &v->dec_w[prec], all.data(), all.size() * sizeof(uint4), prec, kUpdBit[prec])) return AMUSE_EHIP;
         }
     } else {
-        // staged streams (k_vae.hip): stage 0 = pose_embd (K = 333 padded to 22 k-tiles, 2 output tiles per wave) + in_proj(0);
-        // stage i + 1 = what follows block i's self-attention (+ skip linear, trans_enc) + in_proj(i + 1) | pose_proj (24 tiles, 6 per wave)
+        const float *w_emb = D.get("pose_embd.weight"), *w_proj = D.get("pose_proj.weight");
+        // staged streams (pack_staged_stream): pose_embd in front of stage 0, pose_proj behind stage 9; between them the encoder blocks' stages (trans_enc) or,
+        // stage i + 1, what follows decoder layer i's self-attention (pack_dec_layer) + in_proj(i + 1) (trans_dec)
         for (int prec = 0; prec < 4; ++prec) {
-            if (!(what & kUpdBitV[prec])) continue;
+            if (!(what & kUpdBit[prec])) continue;
             std::vector<uint4> all;
-            for (int st = 0; st < kVaeStages; ++st) {
-                v->stage_base[prec][st] = (uint32_t)(all.size() / 64);
-                size_t per_wave = 0;
-                for (int w = 0; w < 4; ++w) {
-                    std::vector<uint4> s;
-                    if (st == 0) pack_gemm(s, prec, D.get("pose_embd.weight"), 128, kFeats, {2 * w, 2 * w + 1}, range(0, 22));
-                    if (st >= 1) {
-                        const int b = st - 1;
-                        if (dec) {
-                            pack_dec_layer(s, prec, D, b, w, false);
-                        } else {
-                            pack_outproj_ffn(s, prec, D, blk_name("encoder", b), w);
-                            if (b >= 4 && b <= 7) pack_skiplin(s, prec, D, "encoder", b - 4, w);
-                        }
-                    }
-                    if (st < 9) pack_qkv(s, prec, D.get((dec ? dec_name(st) : blk_name("encoder", st)) + ".self_attn.in_proj_weight"), w, false);
-                    else pack_gemm(s, prec, D.get("pose_proj.weight"), kFeats, 128, range(6 * w, 6 * w + 6), range(0, 8));
-                    if (w == 0) per_wave = s.size();
-                    else if (s.size() != per_wave) return fail(AMUSE_ESTATE, "internal: uneven pose-denoiser wave streams");
-                    all.insert(all.end(), s.begin(), s.end());
+            const auto content = [&](std::vector<uint4>& s, int st, int w) {
+                if (st == 0) pack_in_matrix_wave(s, prec, w_emb, w);
+                if (!dec) pack_skipnet_stage(s, prec, D, "encoder", st, w);
+                else {
+                    if (st >= 1) pack_dec_layer(s, prec, D, st - 1, w, false);
+                    if (st < 9) pack_qkv(s, prec, D.get(dec_name(st) + ".self_attn.in_proj_weight"), w, false);
                 }
-                v->stage_units[prec][st] = (uint32_t)(per_wave / 64);
-            }
-            all.insert(all.end(), (size_t)kVaeRing * 64, uint4{0, 0, 0, 0});   // the last wave's ring reads past its slice
-            if (upload(&v->rows_w[prec], all.data(), all.size() * sizeof(uint4))) return AMUSE_EHIP;
+                if (st == 9) pack_out_matrix_wave(s, prec, w_proj, w);
+            };
+            if (int e = pack_staged_stream(all, v->stage_base[prec], v->stage_units[prec], content)) return e;
+            if (upload(c, &v->rows_w[prec], all.data(), all.size() * sizeof(uint4), prec, kUpdBit[prec])) return AMUSE_EHIP;
         }
-        if (!dec && (what & AMUSE_UPD_F32X)) {   // fp32x: stages 1..8 once more as ONE stream per stage in consumption order (k_vae_rows8.hip's layout, amuse_api.hip)
+        if (!dec && (what & AMUSE_UPD_F32X)) {   // fp32x row stages without split-K: stages 1..8 (pose_embd / pose_proj + update stay with k_vae_rows)
             std::vector<uint4> s;
-            for (int st = 0; st < kVaeStages; ++st) {
-                v->rows8_base[st] = (uint32_t)(s.size() / 64);
-                if (st == 0 || st == 9) continue;   // (pose_embd / pose_proj + update stay with k_vae_rows)
-                const int b = st - 1;
-                const std::string p = blk_name("encoder", b);
-                pack_gemm(s, PREC_F16X2, D.get(p + ".self_attn.out_proj.weight"), 128, 128, range(0, 8), range(0, 8));
-                for (int ch = 0; ch < 16; ++ch) {
-                    pack_gemm(s, PREC_F16X2, D.get(p + ".linear1.weight"), 512, 128, {2 * ch, 2 * ch + 1}, range(0, 8));
-                    pack_gemm(s, PREC_F16X2, D.get(p + ".linear2.weight"), 128, 512, range(0, 8), {2 * ch, 2 * ch + 1});
-                }
-                if (b >= 4 && b <= 7) {
-                    const float* wskip = D.get("encoder.linear_blocks." + std::to_string(b - 4) + ".weight");
-                    pack_gemm(s, PREC_F16X2, wskip, 128, 256, range(0, 8), range(0, 8));
-                    pack_gemm(s, PREC_F16X2, wskip, 128, 256, range(0, 8), range(8, 16));
-                }
-                const float* in_w = D.get(blk_name("encoder", st) + ".self_attn.in_proj_weight");
-                for (int grp = 0; grp < 3; ++grp) pack_gemm(s, PREC_F16X2, in_w, 384, 128, range(8 * grp, 8 * grp + 8), range(0, 8));
-                if (s.size() % ((size_t)16 * 64) != 0) return fail(AMUSE_ESTATE, "internal: rows8 pose-denoiser stream is not whole stages");
-            }
-            s.insert(s.end(), (size_t)2 * 16 * 64, uint4{0, 0, 0, 0});   // the fetch runs two stages ahead
-            if (upload(&v->rows8_w, s.data(), s.size() * sizeof(uint4))) return AMUSE_EHIP;
+            if (int e = pack_rows8_stream(s, v->rows8_base, D, "encoder", 1, 8, nullptr)) return e;
+            if (upload(c, &v->rows8_w, s.data(), s.size() * sizeof(uint4), PREC_F16X2, AMUSE_UPD_F32X)) return AMUSE_EHIP;
         }
-        if (!dec && (what & AMUSE_UPD_F32X)) {   // fp32x: the whole step as ONE stream of unit pairs for the per-clip kernel (k_vae_fusedx.hip k_den_fusedx): pose_embd (11 k-pairs x 8
-            // output tiles), nine encoder blocks in the fused fp32x decoder's order (amuse_api.hip: skip linear, per head k | v then q, out_proj, the FFN with linear1 one chunk
-            // ahead), pose_proj in four quarters of six output tiles
+        if (!dec && (what & AMUSE_UPD_F32X)) {   // fp32x: the whole step as one per-clip stream (k_den_fusedx): pose_embd in front, pose_proj behind
             std::vector<uint4> s;
-            pack_gemm(s, PREC_F16X2, D.get("pose_embd.weight"), 128, kFeats, range(0, 8), range(0, 22));
-            for (int b = 0; b < 9; ++b) {
-                const std::string p = blk_name("encoder", b);
-                if (b >= 5) {
-                    const float* wskip = D.get("encoder.linear_blocks." + std::to_string(b - 5) + ".weight");
-                    pack_gemm(s, PREC_F16X2, wskip, 128, 256, range(0, 8), range(0, 8));
-                    pack_gemm(s, PREC_F16X2, wskip, 128, 256, range(0, 8), range(8, 16));
-                }
-                const float* in_w = D.get(p + ".self_attn.in_proj_weight");
-                for (int h = 0; h < 4; ++h) {
-                    pack_gemm(s, PREC_F16X2, in_w, 384, 128, {8 + 2 * h, 8 + 2 * h + 1, 16 + 2 * h, 16 + 2 * h + 1}, range(0, 8));
-                    pack_gemm(s, PREC_F16X2, in_w, 384, 128, {2 * h, 2 * h + 1}, range(0, 8));
-                }
-                pack_gemm(s, PREC_F16X2, D.get(p + ".self_attn.out_proj.weight"), 128, 128, range(0, 8), range(0, 8));
-                const auto f1 = [&](int ch) { pack_gemm(s, PREC_F16X2, D.get(p + ".linear1.weight"), 512, 128, {2 * ch, 2 * ch + 1}, range(0, 8)); };
-                const auto f2 = [&](int ch) { pack_gemm(s, PREC_F16X2, D.get(p + ".linear2.weight"), 128, 512, range(0, 8), {2 * ch, 2 * ch + 1}); };
-                f1(0);
-                for (int ch = 0; ch < 15; ++ch) { f1(ch + 1); f2(ch); }
-                f2(15);
-            }
-            for (int q = 0; q < 4; ++q) pack_gemm(s, PREC_F16X2, D.get("pose_proj.weight"), kFeats, 128, range(6 * q, 6 * q + 6), range(0, 8));
-            if (s.size() % ((size_t)16 * 64) != 0) return fail(AMUSE_ESTATE, "internal: fused fp32x pose-denoiser stream is not whole stages");
-            s.insert(s.end(), (size_t)2 * 16 * 64, uint4{0, 0, 0, 0});   // the fetch runs two stages ahead
-            if (upload(&v->fusedx_w, s.data(), s.size() * sizeof(uint4))) return AMUSE_EHIP;
+            if (int e = pack_fusedx_stream(s, D, "encoder", w_emb, w_proj)) return e;
+            if (upload(c, &v->fusedx_w, s.data(), s.size() * sizeof(uint4), PREC_F16X2, AMUSE_UPD_F32X)) return AMUSE_EHIP;
         }
-        if (!dec) {
-            // fused step kernel (k_den_fused.hip; bf16 / fp16 operands): ONE stream for the eight waves, in consumption order, cut into
-            // stages of kVaeFusedStageUnits units - the fused decoder's layout (amuse_api.hip) with pose_embd in front and encoder blocks
+        if (!dec)   // 16-bit fused step kernel (k_den_fused.hip): the fused decoder's layout with pose_embd in front and encoder blocks
             for (const int p16 : {PREC_BF16, PREC_F16}) {
-                if (!(what & kUpdBitV[p16])) continue;
+                if (!(what & kUpdBit[p16])) continue;
                 std::vector<uint4> s;
-                const auto pad = [&](int units) { s.insert(s.end(), (size_t)units * 64, uint4{0, 0, 0, 0}); };
-                pack_gemm(s, p16, D.get("pose_embd.weight"), 128, kFeats, range(0, 8), range(0, 22));   // 11 k-pairs x 8 output tiles
-                pad(8);
-                for (int b = 0; b < 9; ++b) {
-                    const std::string p = blk_name("encoder", b);
-                    if (b >= 5) {   // skip linear ahead of an output block: the x half (k-tiles 0..7), then the popped-skip half
-                        const float* wskip = D.get("encoder.linear_blocks." + std::to_string(b - 5) + ".weight");
-                        pack_gemm(s, p16, wskip, 128, 256, range(0, 8), range(0, 8));
-                        pack_gemm(s, p16, wskip, 128, 256, range(0, 8), range(8, 16));
-                    }
-                    const float* in_w = D.get(p + ".self_attn.in_proj_weight");
-                    for (int h = 0; h < 4; ++h) {   // per head: stage A = k | v tiles per k-pair; stage B = q, out_proj's k-slice
-                        pack_gemm(s, p16, in_w, 384, 128, {8 + 2 * h, 8 + 2 * h + 1, 16 + 2 * h, 16 + 2 * h + 1}, range(0, 8));
-                        pack_gemm(s, p16, in_w, 384, 128, {2 * h, 2 * h + 1}, range(0, 8));
-                        pack_gemm(s, p16, D.get(p + ".self_attn.out_proj.weight"), 128, 128, range(0, 8), {2 * h, 2 * h + 1});
-                    }
-                    const auto f1 = [&](int ch) { pack_gemm(s, p16, D.get(p + ".linear1.weight"), 512, 128, {2 * ch, 2 * ch + 1}, range(0, 8)); };
-                    const auto f2 = [&](int ch) { pack_gemm(s, p16, D.get(p + ".linear2.weight"), 128, 512, range(0, 8), {2 * ch, 2 * ch + 1}); };
-                    f1(0); pad(8);
-                    for (int ch = 0; ch < 15; ++ch) { f1(ch + 1); f2(ch); }
-                    f2(15); pad(8);
-                }
-                for (int half = 0; half < 2; ++half)   // pose_proj ONCE (24 output tiles in two halves of 48 units): the kernel's last stage holds it in LDS whole
-                    pack_gemm(s, p16, D.get("pose_proj.weight"), kFeats, 128, range(12 * half, 12 * half + 12), range(0, 8));
-                if (s.size() % ((size_t)kVaeFusedStageUnits * 64) != 0) return fail(AMUSE_ESTATE, "internal: fused denoiser stream is not whole stages");
-                pad(2 * kVaeFusedStageUnits);   // the fetch runs two stages ahead
-                if (upload(&v->fused_w[p16 == PREC_F16], s.data(), s.size() * sizeof(uint4))) return AMUSE_EHIP;
+                if (int e = pack_fused16_stream(s, p16, D, "encoder", w_emb, w_proj)) return e;
+                if (upload(c, &v->fused_w[p16 == PREC_F16], s.data(), s.size() * sizeof(uint4), p16, kUpdBit[p16])) return AMUSE_EHIP;
             }
-        }
         std::vector<float> fb(16 * kFeatTiles, 0.f);
         memcpy(fb.data(), D.get("pose_proj.bias"), kFeats * 4);
-        if (upload(&v->final_bias, fb.data(), fb.size() * 4) || upload(&v->emb_bias, D.get("pose_embd.bias"), 128 * 4)) return AMUSE_EHIP;
+        if (upload(c, &v->final_bias, fb.data(), fb.size() * 4) || upload(c, &v->emb_bias, D.get("pose_embd.bias"), 128 * 4)) return AMUSE_EHIP;
     }
     {
         const std::vector<float> pv = dec ? build_pvec_dec(D) : build_pvec(D, "encoder", false);
-        if (upload(&v->pvec, pv.data(), pv.size() * 4)) return AMUSE_EHIP;
+        if (upload(c, &v->pvec, pv.data(), pv.size() * 4)) return AMUSE_EHIP;
     }
     if (dec) {
         std::vector<float> wkv((size_t)kLayers * 2 * kD * kD), bkv((size_t)kLayers * 2 * kD);
@@ -397,33 +307,21 @@ int variant_build(amuse_ctx* c, const float* den, int what) {
                 memcpy(wkv.data() + ((size_t)l * 2 + kvi) * kD * kD, t.data(), (size_t)kD * kD * 4);
                 memcpy(bkv.data() + ((size_t)l * 2 + kvi) * kD, D.get(p + ".in_proj_bias") + (1 + kvi) * kD, kD * 4);
             }
-        if (upload(&v->wkv_t, wkv.data(), wkv.size() * 4) || upload(&v->bkv, bkv.data(), bkv.size() * 4)) return AMUSE_EHIP;
+        if (upload(c, &v->wkv_t, wkv.data(), wkv.size() * 4) || upload(c, &v->bkv, bkv.data(), bkv.size() * 4)) return AMUSE_EHIP;
         if (!v->tkv_sched) HIP_TRY(hipMalloc((void**)&v->tkv_sched, (size_t)AMUSE_MAX_STEPS * kTkv * sizeof(float)));
     }
-    // what every arch shares with the shipped configuration: positions, timestep frequencies, time-embedding MLP, condition projections
-    if (upload(&c->den_pe, D.get("query_pos.pe"), 500 * 128 * 4) || upload(&v->m_pe, D.get("mem_pos.pe"), 500 * 128 * 4)) return AMUSE_EHIP;
+    // what every arch shares with the shipped configuration: positions, timestep frequencies, time-embedding MLP + condition projections
+    if (upload(c, &c->den_pe, D.get("query_pos.pe"), 500 * 128 * 4) || upload(c, &v->m_pe, D.get("mem_pos.pe"), 500 * 128 * 4)) return AMUSE_EHIP;
     float fr[128];
     for (int k = 0; k < 128; ++k) fr[k] = expf(-logf(10000.f) * (float)k / 128.f);
-    if (!c->den_freqs && upload(&c->den_freqs, fr, sizeof(fr))) return AMUSE_EHIP;   // (amuse_set_schedule may have installed the caller's values)
-    const auto w1t = transpose(D.get("time_embedding.linear_1.weight"), 128, 256);
-    const auto w2t = transpose(D.get("time_embedding.linear_2.weight"), 128, 128);
-    if (upload(&c->te_w1t, w1t.data(), w1t.size() * 4) || upload(&c->te_w2t, w2t.data(), w2t.size() * 4) ||
-        upload(&c->te_b1, D.get("time_embedding.linear_1.bias"), 512) || upload(&c->te_b2, D.get("time_embedding.linear_2.bias"), 512))
-        return AMUSE_EHIP;
-    const char* names[3] = {"con", "emo", "sty"};
-    for (int n = 0; n < 3; ++n) {
-        const auto wt = transpose(D.get(std::string("emb_proj_") + names[n] + ".1.weight"), 128, 256);
-        if (upload(&c->cond_wt[n], wt.data(), wt.size() * 4) || upload(&c->cond_b[n], D.get(std::string("emb_proj_") + names[n] + ".1.bias"), 512))
-            return AMUSE_EHIP;
-    }
-    return 0;
+    if (!c->den_freqs && upload(c, &c->den_freqs, fr, sizeof(fr), PREC_F32, kImgConst)) return AMUSE_EHIP;   // (amuse_set_schedule may have installed the caller's values)
+    return upload_embeddings(c, D);
 }
 
 void variant_destroy(amuse_ctx* c) {
     amuse_variant* v = c->var;
     if (!v) return;
-    void* ptrs[] = {v->dec_w[0], v->dec_w[1], v->dec_w[2], v->dec_w[3], v->rows_w[0], v->rows_w[1], v->rows_w[2], v->rows_w[3], v->rows8_w, v->fusedx_w, v->pvec, v->m_pe,
-                    v->wkv_t, v->bkv, v->emb_bias, v->final_bias, v->tkv_sched, v->ckv, v->tkv1, v->ws, v->tt, v->fused_w[0], v->fused_w[1], v->skip};
+    void* ptrs[] = {v->tkv_sched, v->ckv, v->tkv1, v->ws, v->tt, v->skip};   // tables and workspaces (the uploaded images belong to c->owned)
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     delete v;

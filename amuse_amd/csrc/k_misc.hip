@@ -244,7 +244,7 @@ __global__ __launch_bounds__(256) void k_repack(const float* __restrict__ params
         } else if (kind == 3) {   // fp16 image (AMUSE_PREC_F16)
             reinterpret_cast<unsigned short*>(dst)[j] = __builtin_bit_cast(unsigned short, (_Float16)v);
         } else if (kind == 2) {
-            // split-fp16 image: 1 KiB units (512 elements) alternate hi / lo pieces of the same weights (amuse_api.hip pack_gemm)
+            // split-fp16 image: 1 KiB units (512 elements) alternate hi / lo pieces of the same weights (amuse_pack.hpp pack_gemm)
             const _Float16 hi = (_Float16)v;
             const _Float16 out = ((j >> 9) & 1) ? (_Float16)(v - (float)hi) : hi;
             reinterpret_cast<unsigned short*>(dst)[j] = __builtin_bit_cast(unsigned short, out);

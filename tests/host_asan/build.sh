@@ -1,5 +1,5 @@
 #!/bin/bash
-# builds tests/host_asan/host_asan (the library's host code + stubbed runtime, -fsanitize=address,undefined): build.sh <out dir>
+# builds tests/host_asan/{host_asan,plan_sweep,pack_images} (the library's host code + stubbed runtime, -fsanitize=address,undefined): build.sh <out dir>
 set -e
 here="$(cd "$(dirname "$0")" && pwd)"
 out=${1:-/tmp/amuse_host_asan}
@@ -15,3 +15,6 @@ $HIPCC --offload-host-only -std=c++17 $SAN -c "$here/hip_stub.cpp" -x hip -o "$o
 # the launch-plan sweep (tests/test_plan_cpu.py) on the same objects
 /opt/rocm/lib/llvm/bin/clang++ -std=c++17 $SAN -c "$here/plan_sweep.cpp" -o "$out/plan_sweep.o"
 /opt/rocm/lib/llvm/bin/clang++ $SAN "$out/plan_sweep.o" "$out/hip_stub.o" "$out/amuse_api.o" "$out/amuse_variants.o" "$out/amuse_audio_api.o" -o "$out/plan_sweep"
+# the image log of the weight packers (tests/test_pack_images_cpu.py) on the same objects
+/opt/rocm/lib/llvm/bin/clang++ -std=c++17 $SAN -c "$here/pack_images.cpp" -o "$out/pack_images.o"
+/opt/rocm/lib/llvm/bin/clang++ $SAN "$out/pack_images.o" "$out/hip_stub.o" "$out/amuse_api.o" "$out/amuse_variants.o" "$out/amuse_audio_api.o" -o "$out/pack_images"

@@ -28,7 +28,7 @@ def test_library_exports_every_declared_symbol():
 
 
 def test_f16_split_of_the_fp32x_mode_matches_numpy():
-    """The host packer's hi / lo split (amuse_api.hip f2h / h2f, used for AMUSE_PREC_F32X's weight stream) against numpy's
+    """The host packer's hi / lo split (amuse_pack.hpp f2h / h2f, used for AMUSE_PREC_F32X's weight stream) against numpy's
     IEEE float16 conversion: normal range, subnormal results, ties, overflow, signed zeros - bit for bit - and the split
     keeps 22 significand bits."""
     import ctypes as C

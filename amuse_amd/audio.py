@@ -16,6 +16,8 @@ from .engine import _ptr, flatten_state_dict
 
 NORM_MEAN, NORM_STD = -9.173025, 5.062332   # configs/base_new.json TRAIN_PARAM.wav_dtw_mfcc.dataset_{mean,std}
 WHICH = {"con": 0, "emo": 1, "sty": 2}
+# include/amuse_hip.h amuse_audio_set_precision: "bf16" = the throughput arithmetic (default), "fp32x" = the parity mode (split-fp16 operands)
+AUDIO_PREC = {"bf16": _lib.PREC_BF16, "fp32x": _lib.PREC_F32X}
 
 
 def kaldi_tables() -> Tuple[np.ndarray, np.ndarray]:
@@ -40,7 +42,8 @@ class AudioEngine:
     """One amuse_audio_ctx on one GPU: the three AST encoders of AST_EVP (models/audio/AST_EVP.py:53-61)."""
 
     def __init__(self, con_sd: Dict[str, np.ndarray], emo_sd: Dict[str, np.ndarray], sty_sd: Dict[str, np.ndarray],
-                 device="cuda:0", norm_mean: float = NORM_MEAN, norm_std: float = NORM_STD, frame_based_feats: bool = True):
+                 device="cuda:0", norm_mean: float = NORM_MEAN, norm_std: float = NORM_STD, frame_based_feats: bool = True,
+                 precision: str = "bf16"):
         self.lib = _lib.load()
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -55,6 +58,21 @@ class AudioEngine:
                                                window.ctypes.data_as(fp), norm_mean, norm_std, int(bool(frame_based_feats)))
         if not self.ctx:
             raise _lib.AmuseHipError(f"amuse_audio_create failed: {self.lib.amuse_last_error().decode()}")
+        if precision != "bf16":
+            self.set_precision(precision)
+
+    def set_precision(self, precision: str) -> None:
+        """"bf16" | "fp32x" (amuse_audio_set_precision): governs encode / features / features_ragged / process_single_seq; fbank is fp32 in both.
+        The first switch to "fp32x" builds that mode's weight images (1.04 GB for the three encoders).  A refused value leaves the mode as it was."""
+        if precision not in AUDIO_PREC:
+            raise ValueError(f"audio precision must be one of {sorted(AUDIO_PREC)}, got {precision!r}")
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.amuse_audio_set_precision(self.ctx, AUDIO_PREC[precision]))
+
+    @property
+    def precision(self) -> str:
+        code = self.lib.amuse_audio_precision(self.ctx)
+        return {v: k for k, v in AUDIO_PREC.items()}[code]
 
     def close(self):
         if getattr(self, "ctx", None):

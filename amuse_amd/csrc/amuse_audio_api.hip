@@ -8,10 +8,14 @@
 
 #include "../../include/amuse_hip.h"
 #include "amuse_audio.hpp"
+#include "amuse_audio_x.hpp"
 
 using namespace amuse;
 
 int amuse_fail_msg(int code, const char* msg);   // amuse_api.hip: the library's thread-local error slot
+// The parity mode (AMUSE_PREC_F32X) lives in amuse_audio_x.hip and is reached through this WEAK reference only: where that unit is not linked (the host-only
+// build of tests/host_asan, whose stub defines the bf16 launchers alone) the address is null and amuse_audio_set_precision refuses the mode.
+extern "C" const amuse::AudioXOps* amuse_audio_x_ops(void) __attribute__((weak));
 
 namespace {
 
@@ -69,6 +73,11 @@ struct amuse_audio_ctx {
     int fbank_cap = 0;
     hipStream_t side[2] = {nullptr, nullptr};
     hipEvent_t ev_fork = nullptr, ev_join[2] = {nullptr, nullptr};
+    // amuse_audio_set_precision: the mode, the parity mode's state (weight images + workspaces, built on the first switch to AMUSE_PREC_F32X) and, until then,
+    // a host copy of the three parameter arrays to build it from (the device holds bf16 images only)
+    int precision = AMUSE_PREC_BF16;
+    void* xstate = nullptr;
+    std::vector<float> host_params[3];
 };
 
 namespace {
@@ -219,6 +228,18 @@ int run_encoder(const amuse_audio_ctx* c, const Workspace& w, const Encoder& E, 
     return 0;
 }
 
+// the two modes behind one pair of calls: workspace `slot` for nb clips / encoder `which` over nb clips on workspace `slot`
+int mode_ensure_ws(amuse_audio_ctx* c, int slot, int nb) {
+    if (c->precision == AMUSE_PREC_F32X) return amuse_audio_x_ops()->ensure_ws(c->xstate, slot, nb);
+    return ensure_ws(c->ws[slot], nb);
+}
+int mode_run_encoder(const amuse_audio_ctx* c, int slot, int which, const float* fbank, int nb, float* feat_out, float* hidden_out, int tap_block,
+                     hipStream_t st) {
+    if (c->precision == AMUSE_PREC_F32X)
+        return amuse_audio_x_ops()->run_encoder(c->xstate, slot, which, c->frame_based, fbank, nb, feat_out, hidden_out, tap_block, st);
+    return run_encoder(c, c->ws[slot], c->enc[which], fbank, nb, feat_out, hidden_out, tap_block, st);
+}
+
 }  // namespace
 
 extern "C" {
@@ -269,6 +290,8 @@ amuse_audio_ctx* amuse_audio_create(int device, const float* con_params, const f
         c->mel_range = reinterpret_cast<int*>(rng);
     }
     for (int e = 0; e < 3 && !rc; ++e) rc = build_encoder(c, c->enc[e], ps[e]);
+    if (!rc && amuse_audio_x_ops)   // (a link without the parity mode never needs them)
+        for (int e = 0; e < 3; ++e) c->host_params[e].assign(ps[e], ps[e] + n_each);
     if (rc) {
         amuse_audio_destroy(c);
         return nullptr;
@@ -281,6 +304,7 @@ void amuse_audio_destroy(amuse_audio_ctx* c) {
     (void)hipSetDevice(c->device);
     for (void* p : c->owned) (void)hipFree(p);
     for (Workspace& w : c->ws) free_ws(w);
+    if (c->xstate) amuse_audio_x_ops()->destroy(c->xstate);
     if (c->fbank) (void)hipFree(c->fbank);
     for (int i = 0; i < 2; ++i) {
         if (c->side[i]) (void)hipStreamDestroy(c->side[i]);
@@ -306,10 +330,10 @@ int amuse_audio_encode(amuse_audio_ctx* c, int which, const float* fbank, int B,
     if (hidden_out && (tap_block < 0 || tap_block >= kAstLayers)) return failf(AMUSE_EINVAL, "%stap_block %ld not in 0..11", "", tap_block);
     HIP_TRY(hipSetDevice(c->device));
     const int chunk = B < kChunk ? B : kChunk;
-    if (int e = ensure_ws(c->ws[0], chunk)) return e;
+    if (int e = mode_ensure_ws(c, 0, chunk)) return e;
     for (int b0 = 0; b0 < B; b0 += chunk) {
         const int nb = (B - b0) < chunk ? (B - b0) : chunk;
-        if (int e = run_encoder(c, c->ws[0], c->enc[which], fbank + (size_t)b0 * kAstFrames * kAstMel, nb, feat_out + (size_t)b0 * kAstFeat,
+        if (int e = mode_run_encoder(c, 0, which, fbank + (size_t)b0 * kAstFrames * kAstMel, nb, feat_out + (size_t)b0 * kAstFeat,
                                 hidden_out ? hidden_out + (size_t)b0 * kAstTokens * kAstDim : nullptr, tap_block, (hipStream_t)stream))
             return e;
     }
@@ -328,7 +352,7 @@ int amuse_audio_features(amuse_audio_ctx* c, const float* waves, int n_samples, 
     if (int e = ensure_side_streams(c)) return e;
     for (int e = 0; e < 3; ++e)
         if (outs[e])
-            if (int rc = ensure_ws(c->ws[e], chunk)) return rc;
+            if (int rc = mode_ensure_ws(c, e, chunk)) return rc;
     // per chunk: fbank on `st`, then a fork-join over two side streams (stream-ordered with `st` through events, so the
     // call stays asynchronous and capturable): encoder e on stream e with workspace e
     for (int b0 = 0; b0 < B; b0 += chunk) {
@@ -338,16 +362,33 @@ int amuse_audio_features(amuse_audio_ctx* c, const float* waves, int n_samples, 
         for (int e = 1; e < 3; ++e) {
             if (!outs[e]) continue;
             HIP_TRY(hipStreamWaitEvent(c->side[e - 1], c->ev_fork, 0));
-            if (int rc = run_encoder(c, c->ws[e], c->enc[e], c->fbank, nb, outs[e] + (size_t)b0 * kAstFeat, nullptr, 0, c->side[e - 1])) return rc;
+            if (int rc = mode_run_encoder(c, e, e, c->fbank, nb, outs[e] + (size_t)b0 * kAstFeat, nullptr, 0, c->side[e - 1])) return rc;
             HIP_TRY(hipEventRecord(c->ev_join[e - 1], c->side[e - 1]));
         }
         if (outs[0])
-            if (int rc = run_encoder(c, c->ws[0], c->enc[0], c->fbank, nb, outs[0] + (size_t)b0 * kAstFeat, nullptr, 0, st)) return rc;
+            if (int rc = mode_run_encoder(c, 0, 0, c->fbank, nb, outs[0] + (size_t)b0 * kAstFeat, nullptr, 0, st)) return rc;
         for (int e = 1; e < 3; ++e)
             if (outs[e]) HIP_TRY(hipStreamWaitEvent(st, c->ev_join[e - 1], 0));   // (also: the next chunk's fbank overwrites c->fbank)
     }
     return 0;
 }
+
+int amuse_audio_set_precision(amuse_audio_ctx* c, int precision) {
+    if (!c) return failf(AMUSE_EINVAL, "NULL argument%s");
+    if (precision != AMUSE_PREC_BF16 && precision != AMUSE_PREC_F32X)
+        return failf(AMUSE_EINVAL, "%saudio precision %ld is neither AMUSE_PREC_BF16 nor AMUSE_PREC_F32X", "", precision);
+    if (precision == AMUSE_PREC_F32X && !c->xstate) {
+        if (!amuse_audio_x_ops)
+            return failf(AMUSE_ESTATE, "the audio front-end's AMUSE_PREC_F32X mode (amuse_audio_x) is not linked into this build%s");
+        HIP_TRY(hipSetDevice(c->device));
+        const float* const ps[3] = {c->host_params[0].data(), c->host_params[1].data(), c->host_params[2].data()};
+        if (int e = amuse_audio_x_ops()->create(&c->xstate, ps)) return e;
+        for (std::vector<float>& v : c->host_params) std::vector<float>().swap(v);   // the images are built once: the host copy is done
+    }
+    c->precision = precision;
+    return 0;
+}
+int amuse_audio_precision(const amuse_audio_ctx* c) { return c ? c->precision : AMUSE_EINVAL; }
 
 // GEMM in isolation (tools/gpu_gemm_bench.py, tests): C = A . W^T + bias with epilogue 0 (bf16 out) or 3 (fp32 out);
 // A dev bf16 TILE-MAJOR [M padded to 128][K] (amuse_debug_tile), W dev bf16 in the kernel's packed fragment order

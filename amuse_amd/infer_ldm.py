@@ -130,15 +130,17 @@ class PretrainedLPDM_v1:
             print("[LATDIFF] (2/3) <===== Chosen AST model: ", best, " , loading state dict... =====>")
             sds = ckpt.load_ast_checkpoint(best)
             self.set_audio_encoders(sds["con"], sds["emo"], sds["sty"], wd.get("dataset_mean", -9.173025),
-                                    wd.get("dataset_std", 5.062332), wd.get("frame_based_feats", True))
+                                    wd.get("dataset_std", 5.062332), wd.get("frame_based_feats", True),
+                                    precision=wd.get("audio_precision", "bf16"))   # (this path's own key; amuse_amd.main --audio-precision sets it)
         elif self.audio_encoder is None:
             raise FileNotFoundError(f"[LATDIFF] AST checkpoint directory {ast_dir} not found (TRAIN_PARAM.{tag}.pretrained_ast); "
                                     f"construct PretrainedLPDM_v1(audio_encoder=...) to run from precomputed embeddings")
         return ldm_epoch
 
-    def set_audio_encoders(self, con_sd, emo_sd, sty_sd, norm_mean=-9.173025, norm_std=5.062332, frame_based_feats=True):
-        """Build the HIP audio front-end from three ASTModel state dicts (AST_EVP.{con,emo,sty}_enc)."""
-        self.audio_engine = AudioEngine(con_sd, emo_sd, sty_sd, self.device, norm_mean, norm_std, frame_based_feats)
+    def set_audio_encoders(self, con_sd, emo_sd, sty_sd, norm_mean=-9.173025, norm_std=5.062332, frame_based_feats=True, precision="bf16"):
+        """Build the HIP audio front-end from three ASTModel state dicts (AST_EVP.{con,emo,sty}_enc).  precision: "bf16" (throughput arithmetic) or
+        "fp32x" (the parity mode: embeddings within 1e-5 of the fp32 oracle's, AudioEngine.set_precision)."""
+        self.audio_engine = AudioEngine(con_sd, emo_sd, sty_sd, self.device, norm_mean, norm_std, frame_based_feats, precision=precision)
 
     @classmethod
     def from_state_dicts(cls, denoiser_sd: Dict[str, np.ndarray], prior_sd: Optional[Dict[str, np.ndarray]],

@@ -182,6 +182,10 @@ def main(argv=None):
                     help="fp32x (default): results match the reference's fp32 modules (eps_hat <= 1e-5) on the 16-bit MFMA; fp32: the same bars on "
                          "the fp32 MFMA, 2.6 x slower; fp16: the throughput mode (2 x fp32x, ~3e-3 on eps_hat; operands must stay below 65504: an "
                          "overflow surfaces as a non-finite output); bf16: the same speed with 8 x the rounding - only for activations beyond fp16 range")
+    ap.add_argument("--audio-precision", default="bf16", choices=["bf16", "fp32x"],
+                    help="arithmetic of the audio front-end (fbank + 3 x AST) of infer_gesture / edit_gesture.  bf16 (default): bf16 operands, embeddings ~5e-3 off the "
+                         "fp32 encoders; fp32x: split-fp16 operands, embeddings within 1e-5 - the mode in which a --precision fp32x run is in parity FROM THE WAVEFORM "
+                         "(1.04 GB more device memory for the weight images, several times the front-end's time)")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--gpus", type=int, default=1, help="one process per GPU on this node: train_gesture = data-parallel ranks (RCCL all-reduce); infer_gesture / "
                                                          "edit_gesture = the job list cut into contiguous ranges, each rank embeds, samples and writes its own (no collective; "
@@ -254,13 +258,18 @@ def main(argv=None):
             setattr(model, k, tp["test"][k]["use"])
         wd = tp["wav_dtw_mfcc"]
         model.set_audio_encoders(*(aw.make_ast_weights(0, n) for n in aw.ENCODERS), wd.get("dataset_mean", -9.173025),
-                                 wd.get("dataset_std", 5.062332), wd.get("frame_based_feats", True))
+                                 wd.get("dataset_std", 5.062332), wd.get("frame_based_feats", True), precision=args.audio_precision)
         ldm_epoch = 0
     else:
         config["_ldm_cfg_override"] = ldm_cfg
+        tp["wav_dtw_mfcc"]["audio_precision"] = args.audio_precision
         model = PretrainedLPDM_v1(None)
         ldm_epoch = model.setup(config, device, processed, None, False, baseline, verbose=False, diffonly=diffonly)
     model.precision = args.precision
+    print(f"[amuse_amd] sampler / decoder precision: {args.precision}; audio front-end precision: {args.audio_precision}"
+          + (" (split-fp16 AST encoders: with --precision fp32 / fp32x the run is in parity from the waveform)" if args.audio_precision == "fp32x"
+             else " (bf16 AST encoders: the embeddings carry bf16 rounding; --audio-precision fp32x is the mode in which a --precision fp32x run is in parity "
+                  "from the waveform)"))
     model.set_sampler(args.sampler, args.steps)
     eval_loader = torch.load(args.eval_data, weights_only=False) if args.eval_data else None
     tr = trainer(config, device, train_loader=eval_loader, model_path=model_path, tag="LPDM_infer", logger_cfg=None,

@@ -373,6 +373,33 @@ int amuse_audio_encode(amuse_audio_ctx* ctx, int which, const float* fbank, int 
 int amuse_audio_features(amuse_audio_ctx* ctx, const float* waves, int n_samples, int B, float* con_out,
                          float* emo_out, float* sty_out, void* stream);
 
+/* The arithmetic of amuse_audio_encode (its hidden_out tap included) and amuse_audio_features; amuse_audio_fbank is fp32 in
+ * either mode.  AMUSE_PREC_BF16 (the default): bf16 operands, fp32 accumulation - bit for bit what a context that never
+ * left the mode computes, also after a round trip through AMUSE_PREC_F32X.  AMUSE_PREC_F32X, the parity mode - the contract:
+ *   - every GEMM operand x is used as hi = rn16(x), lo = rn16(x - hi) in IEEE fp16, rn16 = round-to-nearest-even with
+ *     gradual underflow (the bits of amuse_debug_f16_split and of v_cvt_pk_f16_f32): the weights, the im2col patches, the
+ *     LayerNorm outputs, q (pre-scaled by head_dim ** -0.5 * log2 e before the split), k, v, the un-normalised softmax
+ *     probabilities, the attention output and the GELU output.  A product is Wl.xh + Wh.xl + Wh.xh on
+ *     v_mfma_f32_16x16x32_f16 with fp32 accumulation; the lo.lo term (2^-22 relative) is dropped;
+ *   - everything else is fp32: the residual stream; LayerNorm (two passes; eps 1e-6 in the blocks and the final norm, 1e-5
+ *     in the feature head); softmax in exp2 units with the running-maximum rule of the fp32x decode attention - a chunk
+ *     of 64 keys moves a row's maximum only when a score exceeds it by more than 6 log2 units, so p never exceeds 2^6, and
+ *     the division by the row sum removes the scale; the row sums of the split P (hi + lo, the values the P.V product
+ *     uses); pooling;
+ *   - GELU is the exact erf form (fp32 rounding class; the bf16 kernels' clamped polynomial is 1.9e-4 off);
+ *   - the 768 -> 256 feature head runs on plain fp32 FMAs from fp32 weights, k ascending: its input is NOT split;
+ *   - |x| >= 65504 saturates hi (>= 65520: infinity).  No operand of the shipped architecture gets there: LayerNorm
+ *     outputs, the pre-scaled q, k and v of LayerNorm-ed rows, p <= 64, convex combinations of v, GELU of those;
+ *   - a clip's bits do not depend on its batch position, on the 32-clip chunking or on the call (encode / features).
+ * The mode's weight images (4 B per parameter: 345 MB per encoder) are built on the FIRST switch to AMUSE_PREC_F32X from a
+ * host copy of the parameters that amuse_audio_create keeps until then, its activation workspace (two fp16 planes per
+ * operand matrix, 39 MB per clip and encoder) grows with the calls as the bf16 one does; amuse_audio_destroy frees both.
+ * amuse_audio_create uploads what it always did.  Not stream-ordered: call it between, not during, the context's calls.
+ * Returns AMUSE_EINVAL for a NULL ctx or any other precision, AMUSE_ESTATE (and changes nothing) from a build of the
+ * library without the mode's translation unit (amuse_audio_x.hip); amuse_audio_precision returns the mode. */
+int amuse_audio_set_precision(amuse_audio_ctx* ctx, int precision);
+int amuse_audio_precision(const amuse_audio_ctx* ctx);
+
 /* The front-end's GEMM kernel in isolation, for tests and tools/gpu_gemm_bench.py: out = A . W^T + bias.
  * The front-end keeps every GEMM operand TILE-MAJOR in HBM (16-row x 32-feature tiles of 64 lanes x 8 elements, a bf16
  * tile being one MFMA fragment; amuse_amd/csrc/amuse_audio.hpp): A dev bf16 tile-major [M rounded up to 128][K], W dev

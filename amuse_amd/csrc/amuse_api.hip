@@ -66,47 +66,22 @@ int build_denoiser(amuse_ctx* c, const float* den, int what = AMUSE_UPD_ALL) {
     return upload_embeddings(c, D);
 }
 
+// block 0's hoisted constants belong to the decoder weights they were computed from
+void invalidate_c1(amuse_ctx* c) { c->c1_bf16.valid = c->c1_f16.valid = c->c1_rows8.valid = c->c1_clip.valid = false; }
+
 int build_prior(amuse_ctx* c, const float* pri, int what = AMUSE_UPD_ALL) {
     static const ParamIndex PI = prior_index();
-    if (!g_capture) c->vae_c1_valid[0] = c->vae_c1_valid[1] = c->vae_c1_valid[2] = c->vae_c1_valid[3] = false;   // block 0's hoisted constant belongs to the old decoder weights
+    if (!g_capture) invalidate_c1(c);
     const Params Pp{PI, pri};
-    const float *w_emb = Pp.get("skel_embedding.weight"), *w_final = Pp.get("final_layer.weight");
-    const bool enc = what & AMUSE_UPD_ENCODER;
-    const int X = PREC_F16X2, UX = AMUSE_UPD_F32X;
-    // ---- decoder.  Staged streams (pack_staged_stream): the blocks' stages, final_layer behind stage 9
-    for (int prec = 0; prec < 4; ++prec) {
-        if (!(what & kUpdBit[prec])) continue;
-        std::vector<uint4> all;
-        const auto content = [&](std::vector<uint4>& s, int st, int w) {
-            pack_skipnet_stage(s, prec, Pp, "decoder", st, w);
-            if (st == 9) pack_out_matrix_wave(s, prec, w_final, w);
-        };
-        if (int e = pack_staged_stream(all, c->vae_stage_base[prec], c->vae_stage_units[prec], content)) return e;
-        if (upload(c, &c->vae_w[prec], all.data(), all.size() * sizeof(uint4), prec, kUpdBit[prec])) return AMUSE_EHIP;
-    }
-    if (what & UX) {   // fp32x row stages without split-K: every stage
-        std::vector<uint4> s;
-        if (int e = pack_rows8_stream(s, c->vae_w8x_base, Pp, "decoder", 0, 9, w_final)) return e;
-        if (upload(c, &c->vae_w8x, s.data(), s.size() * sizeof(uint4), X, UX)) return AMUSE_EHIP;
-    }
-    if (what & UX) {   // fp32x per-clip decoder
-        std::vector<uint4> s;
-        if (int e = pack_fusedx_stream(s, Pp, "decoder", nullptr, w_final)) return e;
-        if (upload(c, &c->vae_wfx, s.data(), s.size() * sizeof(uint4), X, UX)) return AMUSE_EHIP;
-    }
-    for (const int p16 : {PREC_BF16, PREC_F16}) {   // 16-bit fused per-clip decoder
-        if (!(what & kUpdBit[p16])) continue;
-        std::vector<uint4> s;
-        if (int e = pack_fused16_stream(s, p16, Pp, "decoder", nullptr, w_final)) return e;
-        if (upload(c, p16 == PREC_BF16 ? &c->vae_wf : &c->vae_wfh, s.data(), s.size() * sizeof(uint4), p16, kUpdBit[p16])) return AMUSE_EHIP;
-    }
+    // ---- decoder: final_layer behind stage 9; every stage on the row kernel without split-K
+    if (int e = build_rownet_streams(c, c->dec, Pp, {"decoder", nullptr, Pp.get("final_layer.weight"), 0, 9, true, 0}, what)) return e;
     {
         auto pv = build_pvec(Pp, "decoder", true);
-        if (upload(c, &c->vae_pvec, pv.data(), pv.size() * 4)) return AMUSE_EHIP;
+        if (upload(c, &c->dec.pvec, pv.data(), pv.size() * 4)) return AMUSE_EHIP;
         std::vector<float> fb(16 * kFeatTiles, 0.f);
         memcpy(fb.data(), Pp.get("final_layer.bias"), kFeats * 4);
-        if (upload(c, &c->vae_final_bias, fb.data(), fb.size() * 4)) return AMUSE_EHIP;
-        if (upload(c, &c->vae_pe, Pp.get("query_pos_decoder.pe"), 500 * 128 * 4)) return AMUSE_EHIP;
+        if (upload(c, &c->dec.final_bias, fb.data(), fb.size() * 4)) return AMUSE_EHIP;
+        if (upload(c, &c->dec.pe, Pp.get("query_pos_decoder.pe"), 500 * 128 * 4)) return AMUSE_EHIP;
         std::vector<float> wv_t(9 * 128 * 128), wo_t(9 * 128 * 128), bv(9 * 128), bo(9 * 128);
         for (int b = 0; b < 9; ++b) {
             const std::string p = blk_name("decoder", b) + ".multihead_attn";
@@ -121,33 +96,15 @@ int build_prior(amuse_ctx* c, const float* pri, int what = AMUSE_UPD_ALL) {
             upload(c, &c->vae_bv, bv.data(), bv.size() * 4) || upload(c, &c->vae_bo, bo.data(), bo.size() * 4))
             return AMUSE_EHIP;
     }
-    // ---- encoder (AMUSE_UPD_ENCODER).  Staged streams: skel_embedding in front of stage 0, nothing behind stage 9
-    for (int prec = 0; prec < 4; ++prec) {
-        if (!(what & kUpdBit[prec]) || !enc) continue;
-        std::vector<uint4> all;
-        const auto content = [&](std::vector<uint4>& s, int st, int w) {
-            if (st == 0) pack_in_matrix_wave(s, prec, w_emb, w);
-            pack_skipnet_stage(s, prec, Pp, "encoder", st, w);
-        };
-        if (int e = pack_staged_stream(all, c->vaee_stage_base[prec], c->vaee_stage_units[prec], content)) return e;
-        if (upload(c, &c->vaee_w[prec], all.data(), all.size() * sizeof(uint4), prec, kUpdBit[prec] | AMUSE_UPD_ENCODER)) return AMUSE_EHIP;
-    }
-    if ((what & UX) && enc) {   // fp32x row stages without split-K: stages 1..9 (the embedding stage stays with k_vae_rows<f16x2, M_ENC>)
-        std::vector<uint4> s;
-        if (int e = pack_rows8_stream(s, c->vaee_w8x_base, Pp, "encoder", 1, 9, nullptr)) return e;
-        if (upload(c, &c->vaee_w8x, s.data(), s.size() * sizeof(uint4), X, UX | AMUSE_UPD_ENCODER)) return AMUSE_EHIP;
-    }
-    if ((what & UX) && enc) {   // fp32x per-clip encoder (k_den_fusedx<encode>): skel_embedding in front, no output matrix
-        std::vector<uint4> s;
-        if (int e = pack_fusedx_stream(s, Pp, "encoder", w_emb, nullptr)) return e;
-        if (upload(c, &c->vaee_wfx, s.data(), s.size() * sizeof(uint4), X, UX | AMUSE_UPD_ENCODER)) return AMUSE_EHIP;
-    }
+    // ---- encoder (streams: AMUSE_UPD_ENCODER): skel_embedding in front of stage 0 - that stage stays with k_vae_rows<f16x2, M_ENC>, stages 1..9 on the row kernel
+    // without split-K - and nothing behind stage 9; no 16-bit per-clip kernel
+    if (int e = build_rownet_streams(c, c->enc, Pp, {"encoder", Pp.get("skel_embedding.weight"), nullptr, 1, 9, false, AMUSE_UPD_ENCODER}, what)) return e;
     {
         auto pv = build_pvec(Pp, "encoder", false);
-        if (upload(c, &c->vaee_pvec, pv.data(), pv.size() * 4) ||
-            upload(c, &c->vaee_pe, Pp.get("query_pos_encoder.pe"), 500 * 128 * 4) ||
+        if (upload(c, &c->enc.pvec, pv.data(), pv.size() * 4) ||
+            upload(c, &c->enc.pe, Pp.get("query_pos_encoder.pe"), 500 * 128 * 4) ||
             upload(c, &c->vaee_tok, Pp.get("global_motion_token"), 2 * 128 * 4) ||
-            upload(c, &c->vaee_emb_bias, Pp.get("skel_embedding.bias"), 128 * 4))
+            upload(c, &c->enc.emb_bias, Pp.get("skel_embedding.bias"), 128 * 4))
             return AMUSE_EHIP;
     }
     return 0;
@@ -218,38 +175,18 @@ hipError_t dispatch_sample(amuse_ctx* c, SampleArgs& a, int precision, hipStream
 constexpr int kVaeFusedChunk = 4096;
 int decode_path_of(amuse_ctx* c, int precision, int B) {
     int path = resolve_path(c->decode_path, plan_decode_path(precision, B), precision);
-    if (path == AMUSE_DECODE_CLIP && !c->vae_wfx) path = AMUSE_DECODE_FUSED;
+    if (path == AMUSE_DECODE_CLIP && !c->dec.fusedx) path = AMUSE_DECODE_FUSED;
     return c->last_plan[1] = path;
 }
 int encode_path_of(amuse_ctx* c, int precision, int B) {
     int path = precision == AMUSE_PREC_F32X ? resolve_path(c->decode_path, plan_encode_path(precision, B), precision) : AMUSE_DECODE_STAGED;
-    if (path == AMUSE_DECODE_CLIP && !c->vaee_wfx) path = AMUSE_DECODE_FUSED;
-    if (path == AMUSE_DECODE_FUSED && !c->vaee_w8x) path = AMUSE_DECODE_STAGED;
+    if (path == AMUSE_DECODE_CLIP && !c->enc.fusedx) path = AMUSE_DECODE_FUSED;
+    if (path == AMUSE_DECODE_FUSED && !c->enc.rows8) path = AMUSE_DECODE_STAGED;
     return c->last_plan[2] = path;
 }
 
-int stage_lengths(amuse_ctx* c, const int* lengths, int B, hipStream_t st) {
-    if (!lengths) return 0;
-    for (int b = 0; b < B; ++b)
-        if (lengths[b] < 1 || lengths[b] > kFrames) return fail(AMUSE_EINVAL, "lengths[%d] = %d not in 1..300", b, lengths[b]);
-    if (c->len_cap < (size_t)B) {
-        if (c->d_lengths) HIP_TRY(hipFree(c->d_lengths));
-        c->d_lengths = nullptr; c->len_cap = 0;
-        HIP_TRY(hipMalloc((void**)&c->d_lengths, (size_t)B * sizeof(int)));
-        c->len_cap = B;
-    }
-    HIP_TRY(hipMemcpyAsync(c->d_lengths, lengths, (size_t)B * sizeof(int), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return 0;
-}
-
-int ensure_vae_ws(amuse_ctx* c, int chunk) {
-    if (c->vae_cap >= (size_t)chunk) return 0;
-    if (c->vae_ws) HIP_TRY(hipFree(c->vae_ws));
-    c->vae_ws = nullptr; c->vae_cap = 0;
-    HIP_TRY(hipMalloc((void**)&c->vae_ws, ((size_t)chunk * kVaeFloatsPerClip + 256) * sizeof(float)));   // (+ 1 KiB: k_vae_fusedx copies a clip's 4.5 KiB of ca in five 1 KiB pieces)
-    c->vae_cap = chunk;
-    return 0;
+int ensure_vae_ws(amuse_ctx* c, int chunk) {   // (+ 1 KiB: k_vae_fusedx copies a clip's 4.5 KiB of ca in five 1 KiB pieces)
+    return ensure(&c->vae_ws, &c->vae_cap, (size_t)chunk, (size_t)chunk * kVaeFloatsPerClip + 256);
 }
 
 // train-mode sampling (amuse_set_sample_dropout) of one amuse_sample / amuse_denoise_step / amuse_profile_sample call: refused where no kernel draws
@@ -261,6 +198,17 @@ int sample_dropout(const amuse_ctx* c, int precision, SampleArgs& a) {
     if (precision == AMUSE_PREC_F32X)
         return fail(AMUSE_ESTATE, "train-mode sampling (amuse_set_sample_dropout p > 0) has no fp32x kernel: use fp32, bf16 or fp16");
     a.drop_thr = c->drop_thr; a.drop_scale = c->drop_scale; a.drop_seed = c->drop_seed;
+    return 0;
+}
+
+// what every entry point on the shipped sampler's kernels puts into its launch: condition tokens, streams, parameters, tile geometry.  The caller has zeroed `a`
+// (and, where the entry point has a train mode, run sample_dropout on it) and adds its time tokens, coefficients and inputs / outputs.
+int sample_args(amuse_ctx* c, const float* con, const float* emo, const float* sty, int B, int precision, hipStream_t st, SampleArgs& a) {
+    int S = 0;
+    if (int e = cond_tokens(c, con, emo, sty, B, &S, st)) return e;
+    set_stream(c, a, precision);
+    a.pvec = c->den_pvec; a.cond_tok = c->cond_tok; a.pe0 = c->den_pe;
+    a.B = B; a.S = S; a.G = pick_group(c, B, S);
     return 0;
 }
 
@@ -413,7 +361,7 @@ int amuse_update_weights_device(amuse_ctx* c, const float* denoiser_params_dev, 
     HIP_TRY(hipSetDevice(c->device));
     if (c->repack.empty())
         if (int e = build_repack_maps(c)) return e;
-    if (prior_params_dev) c->vae_c1_valid[0] = c->vae_c1_valid[1] = c->vae_c1_valid[2] = c->vae_c1_valid[3] = false;
+    if (prior_params_dev) invalidate_c1(c);
     for (const auto& r : c->repack) {
         const float* src = r.prior ? prior_params_dev : denoiser_params_dev;
         if (!src) continue;                             // (only one of the two parameter arrays given)
@@ -423,8 +371,7 @@ int amuse_update_weights_device(amuse_ctx* c, const float* denoiser_params_dev, 
     // the hoisted time-token table belongs to the old time-embedding weights: rebuilt here, stream-ordered, from the schedule's
     // timesteps (still on the device) - no host round trip, the schedule stays set
     if (denoiser_params_dev && c->T > 0)
-        HIP_TRY(launch_time_tokens(c->d_timesteps, c->T, c->den_freqs, c->te_w1t, c->te_b1, c->te_w2t, c->te_b2, c->den_pe + kD, c->d_time_tok,
-                                   (hipStream_t)stream));
+        HIP_TRY(time_tokens(c, c->d_timesteps, c->T, c->den_pe + kD, c->d_time_tok, (hipStream_t)stream));
     return 0;
 }
 
@@ -436,10 +383,10 @@ void amuse_destroy(amuse_ctx* c) {
         if (p) (void)hipFree(p);
     // (the weight images are in `owned`: upload() put them there)  schedule buffers and workspaces:
     void* ptrs[] = {c->d_timesteps, c->d_coef, c->d_time_tok, c->d_ts1, c->d_tt1, c->d_coef1, c->cond_tok, c->lat_tmp, c->fwd_ws, c->vae_ws, c->d_lengths,
-                    c->vae_skip, c->vae_ca_ws, c->vae_c1[0], c->vae_c1[1], c->vae_c1[2], c->vae_c1[3]};
+                    c->vae_skip, c->vae_ca_ws, c->c1_bf16.buf, c->c1_f16.buf, c->c1_rows8.buf, c->c1_clip.buf};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
-    for (hipEvent_t e : c->vae_c1_ev)
+    for (hipEvent_t e : {c->c1_bf16.event, c->c1_f16.event, c->c1_rows8.event, c->c1_clip.event})
         if (e) (void)hipEventDestroy(e);
     delete c;
 }
@@ -530,8 +477,7 @@ int amuse_set_schedule(amuse_ctx* c, const amuse_schedule* s, void* stream) {
     if (c->arch != AMUSE_ARCH_ENC) {
         if (int e = variant_set_schedule(c, st)) { c->T = 0; return e; }
     } else {
-        HIP_TRY(launch_time_tokens(c->d_timesteps, s->n_steps, c->den_freqs, c->te_w1t, c->te_b1, c->te_w2t, c->te_b2,
-                                   c->den_pe + kD, c->d_time_tok, st));
+        HIP_TRY(time_tokens(c, c->d_timesteps, s->n_steps, c->den_pe + kD, c->d_time_tok, st));
     }
     HIP_TRY(hipStreamSynchronize(st));
     return 0;
@@ -548,14 +494,10 @@ int amuse_sample(amuse_ctx* c, const float* con, const float* emo, const float* 
     if (int e = sample_dropout(c, precision, a)) return e;
     if (c->arch != AMUSE_ARCH_ENC)
         return variant_sample(c, con, emo, sty, B, precision, seed, clip_index0, x_init, step_noise, latents_out, traj_out, st);
-    int S = 0;
-    if (int e = cond_tokens(c, con, emo, sty, B, &S, st)) return e;
-    set_stream(c, a, precision);
-    a.pvec = c->den_pvec; a.time_tok = c->d_time_tok; a.cond_tok = c->cond_tok; a.pe0 = c->den_pe;
-    a.coef = c->d_coef; a.x_init = x_init; a.step_noise = step_noise;
-    a.latents_out = latents_out; a.traj_out = traj_out; a.eps_out = nullptr; a.tap_out = nullptr;
+    if (int e = sample_args(c, con, emo, sty, B, precision, st, a)) return e;
+    a.time_tok = c->d_time_tok; a.coef = c->d_coef; a.T = c->T;
+    a.x_init = x_init; a.step_noise = step_noise; a.latents_out = latents_out; a.traj_out = traj_out;
     a.seed = seed; a.clip0 = clip_index0;
-    a.B = B; a.T = c->T; a.S = S; a.G = pick_group(c, B, S); a.no_update = 0;
     HIP_TRY(dispatch_sample(c, a, precision, st));
     return 0;
 }
@@ -569,15 +511,12 @@ int amuse_profile_sample(amuse_ctx* c, const float* con, const float* emo, const
     hipStream_t st = (hipStream_t)stream;
     SampleArgs a{};
     if (int e = sample_dropout(c, precision, a)) return e;
-    int S = 0;
-    if (int e = cond_tokens(c, con, emo, sty, B, &S, st)) return e;
+    if (int e = sample_args(c, con, emo, sty, B, precision, st, a)) return e;
     if (int e = ensure(&c->lat_tmp, &c->lat_cap, (size_t)B * kD)) return e;
     HIP_TRY(hipMemsetAsync(stamps_out, 0, 4 * kProfStamps * sizeof(unsigned long long), st));
-    set_stream(c, a, precision);
-    a.pvec = c->den_pvec; a.time_tok = c->d_time_tok; a.cond_tok = c->cond_tok; a.pe0 = c->den_pe;
-    a.coef = c->d_coef; a.latents_out = c->lat_tmp;
-    a.seed = 1; a.clip0 = 0;
-    a.B = B; a.T = c->T; a.S = S; a.G = pick_group(c, B, S); a.no_update = 0;
+    a.time_tok = c->d_time_tok; a.coef = c->d_coef; a.T = c->T;
+    a.latents_out = c->lat_tmp;
+    a.seed = 1;
     a.prof_out = stamps_out; a.prof_step = prof_step;
     HIP_TRY(dispatch_sample(c, a, precision, st));
     return 0;
@@ -594,16 +533,10 @@ int amuse_denoise_step(amuse_ctx* c, const float* x_t, int timestep, const float
     if (c->arch != AMUSE_ARCH_ENC) return variant_denoise(c, x_t, &timestep, false, con, emo, sty, nullptr, B, precision, eps_out, tap_out, st);
     HIP_TRY(hipMemcpyAsync(c->d_ts1, &timestep, sizeof(int), hipMemcpyHostToDevice, st));
     HIP_TRY(hipStreamSynchronize(st));  // `timestep` lives on this call's stack
-    HIP_TRY(launch_time_tokens(c->d_ts1, 1, c->den_freqs, c->te_w1t, c->te_b1, c->te_w2t, c->te_b2, c->den_pe + kD,
-                               c->d_tt1, st));
-    int S = 0;
-    if (int e = cond_tokens(c, con, emo, sty, B, &S, st)) return e;
-    set_stream(c, a, precision);
-    a.pvec = c->den_pvec; a.time_tok = c->d_tt1; a.cond_tok = c->cond_tok; a.pe0 = c->den_pe;
-    a.coef = c->d_coef1; a.x_init = x_t; a.step_noise = nullptr;
-    a.latents_out = nullptr; a.traj_out = nullptr; a.eps_out = eps_out; a.tap_out = tap_out;
-    a.seed = 0; a.clip0 = 0;
-    a.B = B; a.T = 1; a.S = S; a.G = pick_group(c, B, S); a.no_update = 1;
+    HIP_TRY(time_tokens(c, c->d_ts1, 1, c->den_pe + kD, c->d_tt1, st));
+    if (int e = sample_args(c, con, emo, sty, B, precision, st, a)) return e;
+    a.time_tok = c->d_tt1; a.coef = c->d_coef1; a.T = 1; a.no_update = 1;
+    a.x_init = x_t; a.eps_out = eps_out; a.tap_out = tap_out;
     HIP_TRY(dispatch_sample(c, a, precision, st));
     return 0;
 }
@@ -642,37 +575,40 @@ int amuse_diffusion_forward(amuse_ctx* c, const float* z0, const float* noise, c
     HIP_TRY(hipMemcpyAsync(sb, sqrt_1m_ab, (size_t)B * sizeof(float), hipMemcpyHostToDevice, st));
     HIP_TRY(hipStreamSynchronize(st));  // the host arrays belong to the caller
     HIP_TRY(launch_add_noise(z0, noise, sa, sb, noisy, B, st));
-    HIP_TRY(launch_time_tokens(ts, B, c->den_freqs, c->te_w1t, c->te_b1, c->te_w2t, c->te_b2, c->den_pe + kD, ttok, st));
-    int S = 0;
-    if (int e = cond_tokens(c, con, emo, sty, B, &S, st)) return e;
-    SampleArgs a{};
-    set_stream(c, a, precision);
-    a.pvec = c->den_pvec; a.time_tok = ttok; a.time_tok_clip = ttok; a.cond_tok = c->cond_tok; a.pe0 = c->den_pe;
-    a.coef = c->d_coef1; a.x_init = noisy; a.eps_out = noise_pred_out;
-    a.B = B; a.T = 1; a.S = S; a.G = pick_group(c, B, S); a.no_update = 1;
+    HIP_TRY(time_tokens(c, ts, B, c->den_pe + kD, ttok, st));
+    SampleArgs a{};   // (eval: this entry point has no train mode)
+    if (int e = sample_args(c, con, emo, sty, B, precision, st, a)) return e;
+    a.time_tok = ttok; a.time_tok_clip = ttok; a.coef = c->d_coef1; a.T = 1; a.no_update = 1;
+    a.x_init = noisy; a.eps_out = noise_pred_out;
     HIP_TRY(dispatch_sample(c, a, precision, st));
     if (noisy_out) HIP_TRY(hipMemcpyAsync(noisy_out, noisy, (size_t)B * kD * sizeof(float), hipMemcpyDeviceToDevice, st));
     return 0;
 }
 
+}  // extern "C"
+
 namespace {
-// Block 0's hoisted constant (vae_c1) is produced on the stream of the decode that first needed it; the validity flag is host state.  A later decode on
-// ANOTHER stream (the trainer's sampler stream beside the caller's) must not read it before those launches finish: an event marks the producer's place,
-// and a consumer on a different stream waits on it.  Same stream: nothing to do (stream order).
-hipError_t c1_produced(amuse_ctx* c, int i, hipStream_t st) {
-    if (!c->vae_c1_ev[i])
-        if (hipError_t e = hipEventCreateWithFlags(&c->vae_c1_ev[i], hipEventDisableTiming)) return e;
-    c->vae_c1_stream[i] = st;
-    return hipEventRecord(c->vae_c1_ev[i], st);
+// Block 0's hoisted constant (HoistedC1, amuse_host.hpp) is produced on the stream of the decode that first needed it; the validity flag is host state.  A later decode
+// on ANOTHER stream (the trainer's sampler stream beside the caller's) must not read it before those launches finish: an event marks the producer's place, and a
+// consumer on a different stream waits on it.  Same stream: nothing to do (stream order).
+template <typename F>
+int produce_c1(HoistedC1& h, size_t floats, hipStream_t st, F&& launches) {   // runs `launches` (they fill h.buf) only if the constant is not valid
+    if (h.valid) return 0;
+    if (!h.buf) HIP_TRY(hipMalloc((void**)&h.buf, floats * sizeof(float)));
+    if (int e = launches()) return e;
+    if (!h.event) HIP_TRY(hipEventCreateWithFlags(&h.event, hipEventDisableTiming));
+    h.stream = st;
+    HIP_TRY(hipEventRecord(h.event, st));
+    h.valid = true;
+    return 0;
 }
-hipError_t c1_consumed(amuse_ctx* c, int i, hipStream_t st) {
-    if (!c->vae_c1_ev[i] || c->vae_c1_stream[i] == st) return hipSuccess;
-    return hipStreamWaitEvent(st, c->vae_c1_ev[i], 0);
+hipError_t consume_c1(const HoistedC1& h, hipStream_t st) {
+    if (!h.event || h.stream == st) return hipSuccess;
+    return hipStreamWaitEvent(st, h.event, 0);
 }
-}  // namespace
 
 // train-mode decode (amuse_set_decode_dropout p > 0) is refused where no kernel draws the masks, so that dropout is never silently dropped
-static int decode_dropout_refused(const amuse_ctx* c, int precision) {
+int decode_dropout_refused(const amuse_ctx* c, int precision) {
     if (c->dec_drop_thr == 0) return 0;
     if (!c->has_prior) return fail(AMUSE_ESTATE, "this context was created without MotionPrior weights");
     if (precision == AMUSE_PREC_F32X)
@@ -680,9 +616,156 @@ static int decode_dropout_refused(const amuse_ctx* c, int precision) {
     return 0;
 }
 
-// amuse_vae_decode; clip0 = global index of clip 0 (the dropout masks of train-mode decode; unused in eval)
-static int vae_decode(amuse_ctx* c, const float* z, const int* lengths, int B, int precision, int quat_mode,
-                      float* feats_out, float* poses_out, float* trans_out, void* stream, uint64_t clip0) {
+// one decode call as its kernel families see it; clip0 = global index of clip 0 (the dropout masks of train-mode decode; unused in eval)
+struct DecodeCall {
+    const float* z; const int* lengths; int B, precision, quat_mode;
+    float *feats_out, *poses_out, *trans_out;
+    hipStream_t st; uint64_t clip0;
+};
+template <typename T>
+T* at_clip(T* p, int b0, size_t per_clip) { return p ? p + (size_t)b0 * per_clip : nullptr; }
+hipError_t decode_ca(const amuse_ctx* c, const float* z, bool bias, float* ca, int nb, hipStream_t st) {   // (no bias: the per-head form of train-mode decode)
+    return launch_vae_ca(z, c->vae_wv_t, c->vae_bv, c->vae_wo_t, bias ? c->vae_bo : nullptr, ca, nb, st);
+}
+
+// bf16 / fp16 throughput modes from kFusedMinClips clips up: one persistent workgroup per clip (k_vae_fused.hip)
+int decode_fused16(amuse_ctx* c, const DecodeCall& d) {
+    const bool f16 = d.precision == PREC_F16;
+    const auto launch = f16 ? launch_vae_fusedh : launch_vae_fused;
+    const int chunk = d.B < kVaeFusedChunk ? d.B : kVaeFusedChunk;
+    if (int e = ensure(&c->vae_skip, &c->vae_skip_cap, (size_t)chunk, (size_t)chunk * (kVaeFusedSkipBytesPerClip / sizeof(uint4)))) return e;
+    if (int e = ensure(&c->vae_ca_ws, &c->vae_ca_cap, (size_t)chunk * kLayers * kD + 256)) return e;   // + the DMA's overrun
+    VaeFusedArgs base{};
+    base.wstream = c->dec.fused16[f16]; base.pvec = c->dec.pvec; base.final_bias = c->dec.final_bias; base.pe = c->dec.pe;
+    base.ca = c->vae_ca_ws; base.skip = c->vae_skip; base.quat_mode = d.quat_mode; base.ablate_attention = c->ablate & 1;
+    // Block 0's self-attention half does not depend on the latent (k_vae_fused.hip / amuse_fused.hpp decoder_block, c1): computed once
+    // per weight set by the kernel's own tapped instantiation on one clip, stream-ordered in front of the first decode that uses it
+    // (the same bits as recomputing block 0 per clip: profiles/r04_decode_hoist_ab.txt).
+    HoistedC1& h = f16 ? c->c1_f16 : c->c1_bf16;
+    constexpr size_t kC1Floats = (size_t)kFrames * kD, kTapFloats = 11 * kC1Floats;
+    if (!c->decode_tap && !(c->ablate & 1))
+        if (int e = produce_c1(h, kC1Floats + kTapFloats, d.st, [&]() -> int {
+                float* tap = h.buf + kC1Floats;
+                HIP_TRY(decode_ca(c, d.z, true, c->vae_ca_ws, 1, d.st));
+                VaeFusedArgs fa = base;
+                fa.B = 1; fa.tap_out = tap;
+                HIP_TRY(launch(fa, d.st));
+                HIP_TRY(hipMemcpyAsync(h.buf, tap + 10 * kC1Floats, kC1Floats * sizeof(float), hipMemcpyDeviceToDevice, d.st));
+                return 0;
+            }))
+            return e;
+    if (h.valid) HIP_TRY(consume_c1(h, d.st));
+    return for_chunks(d.B, chunk, [&](int b0, int nb) -> int {
+        HIP_TRY(decode_ca(c, d.z + (size_t)b0 * kD, true, c->vae_ca_ws, nb, d.st));
+        VaeFusedArgs fa = base;
+        fa.lengths = d.lengths ? c->d_lengths + b0 : nullptr;
+        fa.feats_out = at_clip(d.feats_out, b0, kFrames * kFeats);
+        fa.poses_out = at_clip(d.poses_out, b0, kFrames * kJoints * 3);
+        fa.trans_out = at_clip(d.trans_out, b0, kFrames * 3);
+        fa.B = nb;
+        fa.tap_out = b0 == 0 ? c->decode_tap : nullptr;   // (amuse_debug_set_decode_tap: tests)
+        fa.c1 = (h.valid && !fa.tap_out) ? h.buf : nullptr;
+        HIP_TRY(launch(fa, d.st));
+        return 0;
+    });
+}
+
+// the staged kernels' arguments of clips [b0, b0 + nb) of a decode: the decoder's streams, the workspace carved for nb clips (the cross-attention constant in its
+// tail), this chunk's lengths and outputs
+StageArgs decode_stage_args(const amuse_ctx* c, const DecodeCall& d, int b0, int nb, const StageWs& w) {
+    StageArgs a = stage_args(c->dec, d.precision, w, nb);
+    a.rows.ca = w.tail;
+    a.rows.lengths = a.attn.lengths = d.lengths ? c->d_lengths + b0 : nullptr;
+    a.rows.feats_out = at_clip(d.feats_out, b0, kFrames * kFeats);
+    a.rows.poses_out = at_clip(d.poses_out, b0, kFrames * kJoints * 3);
+    a.rows.trans_out = at_clip(d.trans_out, b0, kFrames * 3);
+    a.rows.quat_mode = d.quat_mode;
+    return a;
+}
+
+// the fp32x decode as ONE persistent workgroup per clip (k_vae_fusedx.hip; CLIP) where the call's clips fill rounds of the chip; its scratch arrays are the staged
+// path's attn_o and skip
+int decode_clipx(amuse_ctx* c, const DecodeCall& d) {
+    const int chunk = d.B < kVaeChunk ? d.B : kVaeChunk;
+    if (int e = ensure_vae_ws(c, chunk)) return e;
+    // block 0's self-attention half is one [300][128] constant per weight set for full-length clips (the decoder's queries are the positional table): computed
+    // once by THIS kernel on one clip (c1_out: the same instruction stream, the same bits), then every full-length clip starts behind norm1 and the kernel's
+    // weight stream behind block 0's sixteen attention stages.  Explicit lengths take the full path.
+    const bool hoist = !d.lengths && !c->decode_tap;
+    return for_chunks(d.B, chunk, [&](int b0, int nb) -> int {
+        const StageWs w = carve_stage_ws(c->vae_ws, (size_t)nb * kFrames);
+        const VaeRowsArgs ra = decode_stage_args(c, d, b0, nb, w).rows;
+        HIP_TRY(decode_ca(c, d.z + (size_t)b0 * kD, true, w.tail, nb, d.st));
+        VaeFusedXArgs fx{};
+        fx.wstream = c->dec.fusedx; fx.pvec = ra.pvec; fx.final_bias = ra.final_bias; fx.pe = ra.pe; fx.ca = w.tail;
+        fx.skip = w.skip; fx.obuf = w.attn_o; fx.quat_mode = d.quat_mode;
+        if (hoist) {
+            if (int e = produce_c1(c->c1_clip, (size_t)kFrames * kD, d.st, [&]() -> int {
+                    VaeFusedXArgs px = fx;
+                    px.B = 1; px.c1_out = c->c1_clip.buf;
+                    HIP_TRY(launch_vae_fusedx(px, d.st));
+                    return 0;
+                }))
+                return e;
+            HIP_TRY(consume_c1(c->c1_clip, d.st));
+            fx.c1 = c->c1_clip.buf;
+        }
+        fx.lengths = ra.lengths; fx.feats_out = ra.feats_out; fx.poses_out = ra.poses_out; fx.trans_out = ra.trans_out;
+        fx.tap_out = b0 == 0 ? c->decode_tap : nullptr;
+        fx.B = nb;
+        HIP_TRY(launch_vae_fusedx(fx, d.st));
+        return 0;
+    });
+}
+
+// the row / attention launches.  fp32x: the row stages without split-K (k_vae_rows8.hip; FUSED) or the split-K row kernel k_vae_rows<f16x2> (STAGED), chosen from the
+// clips of the CALL (not of the chunk: a job's last chunk must not change kernels) or as amuse_set_decode_path pins it, so that a job-level choice (amuse_plan) keeps
+// fp32x shards bitwise too.  Train-mode decode: the six dropout sites of every block live - per-head cross-attention partials, the dropout instantiations of the row
+// and attention kernels
+int decode_staged(amuse_ctx* c, const DecodeCall& d, bool rows8, bool drop) {
+    const int chunk = d.B < kVaeChunk ? d.B : kVaeChunk;
+    if (int e = ensure_vae_ws(c, chunk)) return e;
+    // fp32x row stages, all clips full length: block 0's self-attention half is one [300][128] constant per weight set (see decode_fused16) - computed once by these
+    // kernels themselves on one clip (a tile's arithmetic does not depend on its launch: same bits), then every decode starts at stage 1 behind norm1.  Explicit
+    // lengths (even all 300) take the full path.
+    const bool hoist = rows8 && !d.lengths;
+    return for_chunks(d.B, chunk, [&](int b0, int nb) -> int {
+        const StageWs w = carve_stage_ws(c->vae_ws, (size_t)nb * kFrames);
+        StageArgs a = decode_stage_args(c, d, b0, nb, w);
+        HIP_TRY(decode_ca(c, d.z + (size_t)b0 * kD, !drop, w.tail, nb, d.st));
+        if (drop) {   // clip b of this chunk is global clip clip0 + b0 + b
+            VaeDropArgs da{};
+            da.drop_thr = c->dec_drop_thr; da.drop_scale = c->dec_drop_scale; da.drop_seed = c->dec_drop_seed;
+            da.drop_clip0 = (uint32_t)(d.clip0 + (uint64_t)b0);
+            a.rows.drop = a.attn.drop = da;
+            a.rows.ca_bias = c->vae_bo;
+            return run_stages(a, d.precision, {VAE_MODE_DEC_DROP, 0, 1, 0, VAE_MODE_DEC, false}, d.st);
+        }
+        twin_rows8(a, c->dec, rows8);
+        if (hoist) {
+            if (int e = produce_c1(c->c1_rows8, (size_t)kFrames * kD, d.st, [&]() -> int {
+                    VaeRowsArgs p8 = a.rows8;
+                    p8.B = 1; p8.lengths = nullptr; p8.feats_out = p8.poses_out = p8.trans_out = nullptr;
+                    VaeAttnArgs pa = a.attn;
+                    pa.B = 1; pa.lengths = nullptr;
+                    p8.stage = 0;
+                    HIP_TRY(launch_vae_rows8x(p8, d.st));
+                    HIP_TRY(launch_vae_attn(pa, d.precision, VAE_MODE_DEC, d.st));
+                    p8.stage = 1; p8.c1_out = c->c1_rows8.buf;
+                    HIP_TRY(launch_vae_rows8x(p8, d.st));
+                    return 0;
+                }))
+                return e;
+            HIP_TRY(consume_c1(c->c1_rows8, d.st));
+            a.rows8.c1 = c->c1_rows8.buf;
+        }
+        return run_stages(a, d.precision, {VAE_MODE_DEC, hoist ? 1 : 0, rows8 ? 0 : 1, rows8 ? 9 : 0, VAE_MODE_DEC, false}, d.st);
+    });
+}
+
+// amuse_vae_decode: the checks and the choice of kernel family
+int vae_decode(amuse_ctx* c, const float* z, const int* lengths, int B, int precision, int quat_mode,
+               float* feats_out, float* poses_out, float* trans_out, void* stream, uint64_t clip0) {
     if (!c) return fail(AMUSE_EINVAL, "ctx is NULL");
     if (!c->has_prior) return fail(AMUSE_ESTATE, "this context was created without MotionPrior weights");
     if (!z) return fail(AMUSE_EINVAL, "z is NULL");
@@ -691,168 +774,18 @@ static int vae_decode(amuse_ctx* c, const float* z, const int* lengths, int B, i
     if (quat_mode != AMUSE_QUAT_P3D && quat_mode != AMUSE_QUAT_LEGACY) return fail(AMUSE_EINVAL, "bad quat_mode %d", quat_mode);
     if (int e = decode_dropout_refused(c, precision)) return e;
     HIP_TRY(hipSetDevice(c->device));
-    hipStream_t st = (hipStream_t)stream;
-    if (int e = stage_lengths(c, lengths, B, st)) return e;
+    const DecodeCall d{z, lengths, B, precision, quat_mode, feats_out, poses_out, trans_out, (hipStream_t)stream, clip0};
+    if (int e = stage_lengths(c, lengths, B, false, d.st)) return e;
     // train-mode decode runs on the staged family at every clip count, whatever the pin says: the fused kernels and block 0's hoisted constant are eval-only
     const bool drop = c->dec_drop_thr > 0;
     const int path = drop ? (c->last_plan[1] = AMUSE_DECODE_STAGED) : decode_path_of(c, precision, B);
-    if (is_op16(precision) && path != AMUSE_DECODE_STAGED) {
-        // bf16 / fp16 throughput modes from kFusedMinClips clips up: one persistent workgroup per clip (k_vae_fused.hip)
-        const int chunk = B < kVaeFusedChunk ? B : kVaeFusedChunk;
-        if (c->vae_skip_cap < (size_t)chunk) {
-            if (c->vae_skip) HIP_TRY(hipFree(c->vae_skip));
-            c->vae_skip = nullptr; c->vae_skip_cap = 0;
-            HIP_TRY(hipMalloc((void**)&c->vae_skip, (size_t)chunk * kVaeFusedSkipBytesPerClip));
-            c->vae_skip_cap = chunk;
-        }
-        if (int e = ensure(&c->vae_ca_ws, &c->vae_ca_cap, (size_t)chunk * kLayers * kD + 256)) return e;   // + the DMA's overrun
-        // Block 0's self-attention half does not depend on the latent (k_vae_fused.hip / amuse_fused.hpp decoder_block, c1): computed once
-        // per weight set by the kernel's own tapped instantiation on one clip, stream-ordered in front of the first decode that uses it
-        // (the same bits as recomputing block 0 per clip: profiles/r04_decode_hoist_ab.txt).
-        const int pi = precision == PREC_F16 ? 1 : 0;
-        if (!c->vae_c1_valid[pi] && !c->decode_tap && !(c->ablate & 1)) {
-            constexpr size_t kTapFloats = (size_t)11 * kFrames * kD;
-            if (!c->vae_c1[pi]) HIP_TRY(hipMalloc((void**)&c->vae_c1[pi], ((size_t)kFrames * kD + kTapFloats) * sizeof(float)));
-            float* tap = c->vae_c1[pi] + (size_t)kFrames * kD;
-            HIP_TRY(launch_vae_ca(z, c->vae_wv_t, c->vae_bv, c->vae_wo_t, c->vae_bo, c->vae_ca_ws, 1, st));
-            VaeFusedArgs fa{};
-            fa.wstream = precision == PREC_F16 ? c->vae_wfh : c->vae_wf; fa.pvec = c->vae_pvec; fa.final_bias = c->vae_final_bias; fa.pe = c->vae_pe;
-            fa.ca = c->vae_ca_ws; fa.skip = c->vae_skip; fa.B = 1; fa.quat_mode = quat_mode; fa.tap_out = tap;
-            HIP_TRY(precision == PREC_F16 ? launch_vae_fusedh(fa, st) : launch_vae_fused(fa, st));
-            HIP_TRY(hipMemcpyAsync(c->vae_c1[pi], tap + (size_t)10 * kFrames * kD, (size_t)kFrames * kD * sizeof(float), hipMemcpyDeviceToDevice, st));
-            HIP_TRY(c1_produced(c, pi, st));
-            c->vae_c1_valid[pi] = true;
-        }
-        if (c->vae_c1_valid[pi]) HIP_TRY(c1_consumed(c, pi, st));
-        for (int b0 = 0; b0 < B; b0 += chunk) {
-            const int nb = (B - b0) < chunk ? (B - b0) : chunk;
-            HIP_TRY(launch_vae_ca(z + (size_t)b0 * kD, c->vae_wv_t, c->vae_bv, c->vae_wo_t, c->vae_bo, c->vae_ca_ws, nb, st));
-            VaeFusedArgs fa{};
-            fa.wstream = precision == PREC_F16 ? c->vae_wfh : c->vae_wf; fa.pvec = c->vae_pvec; fa.final_bias = c->vae_final_bias; fa.pe = c->vae_pe;
-            fa.ca = c->vae_ca_ws; fa.lengths = lengths ? c->d_lengths + b0 : nullptr; fa.skip = c->vae_skip;
-            fa.feats_out = feats_out ? feats_out + (size_t)b0 * kFrames * kFeats : nullptr;
-            fa.poses_out = poses_out ? poses_out + (size_t)b0 * kFrames * kJoints * 3 : nullptr;
-            fa.trans_out = trans_out ? trans_out + (size_t)b0 * kFrames * 3 : nullptr;
-            fa.B = nb; fa.quat_mode = quat_mode;
-            fa.tap_out = b0 == 0 ? c->decode_tap : nullptr;   // (amuse_debug_set_decode_tap: tests)
-            fa.c1 = (c->vae_c1_valid[pi] && !fa.tap_out) ? c->vae_c1[pi] : nullptr;
-            fa.ablate_attention = c->ablate & 1;
-            HIP_TRY(precision == PREC_F16 ? launch_vae_fusedh(fa, st) : launch_vae_fused(fa, st));
-        }
-        return 0;
-    }
-    const int chunk = B < kVaeChunk ? B : kVaeChunk;
-    if (int e = ensure_vae_ws(c, chunk)) return e;
-    for (int b0 = 0; b0 < B; b0 += chunk) {
-        const int nb = (B - b0) < chunk ? (B - b0) : chunk;
-        const size_t rows = (size_t)nb * kFrames;
-        float* ws = c->vae_ws;
-        VaeRowsArgs ra{};
-        ra.wstream = c->vae_w[precision];
-        memcpy(ra.stage_base, c->vae_stage_base[precision], sizeof(ra.stage_base));
-        memcpy(ra.stage_units, c->vae_stage_units[precision], sizeof(ra.stage_units));
-        ra.pvec = c->vae_pvec; ra.final_bias = c->vae_final_bias; ra.pe = c->vae_pe;
-        ra.x = ws; ws += rows * kD;
-        ra.q = ws; ws += rows * kD;
-        ra.k = ws; ws += rows * kD;
-        ra.v = ws; ws += rows * kD;
-        float* attn_o = ws; ws += rows * kD;
-        ra.attn_o = attn_o;
-        ra.skip = ws; ws += 4 * rows * kD;
-        float* ca = ws;
-        ra.ca = ca;
-        ra.lengths = lengths ? c->d_lengths + b0 : nullptr;
-        ra.feats_out = feats_out ? feats_out + (size_t)b0 * kFrames * kFeats : nullptr;
-        ra.poses_out = poses_out ? poses_out + (size_t)b0 * kFrames * kJoints * 3 : nullptr;
-        ra.trans_out = trans_out ? trans_out + (size_t)b0 * kFrames * 3 : nullptr;
-        ra.B = nb; ra.quat_mode = quat_mode; ra.tiles = 19;
-        VaeAttnArgs aa{};
-        aa.q = ra.q; aa.k = ra.k; aa.v = ra.v; aa.lengths = ra.lengths; aa.o = attn_o; aa.B = nb; aa.q_tiles = 19;
-        if (drop) {
-            // the six dropout sites of every block live: per-head cross-attention partials, the dropout instantiations of the row and attention kernels;
-            // clip b of this chunk is global clip clip0 + b0 + b
-            HIP_TRY(launch_vae_ca(z + (size_t)b0 * kD, c->vae_wv_t, c->vae_bv, c->vae_wo_t, nullptr, ca, nb, st));   // (no bias: the per-head form)
-            VaeDropArgs da{};
-            da.drop_thr = c->dec_drop_thr; da.drop_scale = c->dec_drop_scale; da.drop_seed = c->dec_drop_seed;
-            da.drop_clip0 = (uint32_t)(clip0 + (uint64_t)b0);
-            VaeRowsDropArgs rd{};
-            static_cast<VaeRowsArgs&>(rd) = ra;
-            rd.drop = da; rd.ca_bias = c->vae_bo;
-            VaeAttnDropArgs ad{};
-            static_cast<VaeAttnArgs&>(ad) = aa;
-            ad.drop = da;
-            for (int stage = 0; stage < kVaeStages; ++stage) {
-                rd.stage = stage;
-                ad.layer = stage;
-                HIP_TRY(launch_vae_rows(rd, precision, VAE_MODE_DEC_DROP, st));
-                if (stage < kLayers) HIP_TRY(launch_vae_attn(ad, precision, VAE_MODE_DEC_DROP, st));
-            }
-            continue;
-        }
-        HIP_TRY(launch_vae_ca(z + (size_t)b0 * kD, c->vae_wv_t, c->vae_bv, c->vae_wo_t, c->vae_bo, ca, nb, st));
-        // fp32x: the row stages without split-K (k_vae_rows8.hip; FUSED) or the split-K row kernel k_vae_rows<f16x2> (STAGED), chosen from the clips of the CALL (not of the
-        // chunk: a job's last chunk must not change kernels) or as amuse_set_decode_path pins it, so that a job-level choice (amuse_plan) keeps fp32x shards bitwise too
-        const bool rows8 = precision == PREC_F16X2 && path != AMUSE_DECODE_STAGED;
-        // the fp32x decode as ONE persistent workgroup per clip (k_vae_fusedx.hip; CLIP) where the call's clips fill rounds of the chip; its scratch arrays are this path's
-        // attn_o and skip
-        if (precision == PREC_F16X2 && path == AMUSE_DECODE_CLIP) {
-            // block 0's self-attention half is one [300][128] constant per weight set for full-length clips (the decoder's queries are the positional table): computed
-            // once by THIS kernel on one clip (c1_out: the same instruction stream, the same bits), then every full-length clip starts behind norm1 and the kernel's
-            // weight stream behind block 0's sixteen attention stages.  Explicit lengths take the full path.
-            const bool hoistx = !lengths && !c->decode_tap;
-            if (hoistx && !c->vae_c1_valid[3]) {
-                if (!c->vae_c1[3]) HIP_TRY(hipMalloc((void**)&c->vae_c1[3], (size_t)kFrames * kD * sizeof(float)));
-                VaeFusedXArgs px{};
-                px.wstream = c->vae_wfx; px.pvec = c->vae_pvec; px.final_bias = c->vae_final_bias; px.pe = c->vae_pe; px.ca = ca;
-                px.skip = ra.skip; px.obuf = attn_o; px.B = 1; px.quat_mode = quat_mode; px.c1_out = c->vae_c1[3];
-                HIP_TRY(launch_vae_fusedx(px, st));
-                HIP_TRY(c1_produced(c, 3, st));
-                c->vae_c1_valid[3] = true;
-            }
-            if (hoistx) HIP_TRY(c1_consumed(c, 3, st));
-            VaeFusedXArgs fx{};
-            fx.c1 = hoistx ? c->vae_c1[3] : nullptr;
-            fx.wstream = c->vae_wfx; fx.pvec = c->vae_pvec; fx.final_bias = c->vae_final_bias; fx.pe = c->vae_pe; fx.ca = ca; fx.lengths = ra.lengths;
-            fx.skip = ra.skip; fx.obuf = attn_o; fx.feats_out = ra.feats_out; fx.poses_out = ra.poses_out; fx.trans_out = ra.trans_out;
-            fx.tap_out = b0 == 0 ? c->decode_tap : nullptr;
-            fx.B = nb; fx.quat_mode = quat_mode;
-            HIP_TRY(launch_vae_fusedx(fx, st));
-            continue;
-        }
-        VaeRowsArgs r8 = ra;
-        if (rows8) {
-            r8.wstream = c->vae_w8x;
-            memcpy(r8.stage_base, c->vae_w8x_base, sizeof(r8.stage_base));
-        }
-        // fp32x row stages, all clips full length: block 0's self-attention half is one [300][128] constant per weight set (see the fused
-        // path above) - computed once by these kernels themselves on one clip (a tile's arithmetic does not depend on its launch: same bits),
-        // then every decode starts at stage 1 behind norm1.  Explicit lengths (even all 300) take the full path.
-        const bool hoist8 = rows8 && !lengths;
-        if (hoist8 && !c->vae_c1_valid[2]) {
-            if (!c->vae_c1[2]) HIP_TRY(hipMalloc((void**)&c->vae_c1[2], (size_t)kFrames * kD * sizeof(float)));
-            VaeRowsArgs p8 = r8;
-            p8.B = 1; p8.lengths = nullptr; p8.feats_out = p8.poses_out = p8.trans_out = nullptr;
-            VaeAttnArgs pa = aa;
-            pa.B = 1; pa.lengths = nullptr;
-            p8.stage = 0;
-            HIP_TRY(launch_vae_rows8x(p8, st));
-            HIP_TRY(launch_vae_attn(pa, precision, VAE_MODE_DEC, st));
-            p8.stage = 1; p8.c1_out = c->vae_c1[2];
-            HIP_TRY(launch_vae_rows8x(p8, st));
-            HIP_TRY(c1_produced(c, 2, st));
-            c->vae_c1_valid[2] = true;
-        }
-        if (hoist8) { HIP_TRY(c1_consumed(c, 2, st)); r8.c1 = c->vae_c1[2]; }
-        for (int stage = hoist8 ? 1 : 0; stage < kVaeStages; ++stage) {
-            ra.stage = stage;
-            r8.stage = stage;
-            if (rows8) HIP_TRY(launch_vae_rows8x(r8, st));
-            else HIP_TRY(launch_vae_rows(ra, precision, VAE_MODE_DEC, st));
-            if (stage < kLayers) HIP_TRY(launch_vae_attn(aa, precision, VAE_MODE_DEC, st));
-        }
-    }
-    return 0;
+    if (is_op16(precision) && path != AMUSE_DECODE_STAGED) return decode_fused16(c, d);
+    if (precision == PREC_F16X2 && path == AMUSE_DECODE_CLIP) return decode_clipx(c, d);
+    return decode_staged(c, d, precision == PREC_F16X2 && path != AMUSE_DECODE_STAGED, drop);
 }
+}  // namespace
+
+extern "C" {
 
 int amuse_vae_decode(amuse_ctx* c, const float* z, const int* lengths, int B, int precision, int quat_mode,
                      float* feats_out, float* poses_out, float* trans_out, void* stream) {
@@ -869,64 +802,34 @@ int amuse_vae_encode(amuse_ctx* c, const float* feats, const int* lengths, int B
     if (precision < AMUSE_PREC_F32 || precision > AMUSE_PREC_F16) return fail(AMUSE_EINVAL, "bad precision %d", precision);
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream;
-    if (int e = stage_lengths(c, lengths, B, st)) return e;
+    if (int e = stage_lengths(c, lengths, B, false, st)) return e;
     const int chunk = B < kVaeChunk ? B : kVaeChunk;
     if (int e = ensure_vae_ws(c, chunk)) return e;
-    for (int b0 = 0; b0 < B; b0 += chunk) {
-        const int nb = (B - b0) < chunk ? (B - b0) : chunk;
-        const size_t rows = (size_t)nb * kEncRows;
-        float* ws = c->vae_ws;
-        VaeRowsArgs ra{};
-        ra.wstream = c->vaee_w[precision];
-        memcpy(ra.stage_base, c->vaee_stage_base[precision], sizeof(ra.stage_base));
-        memcpy(ra.stage_units, c->vaee_stage_units[precision], sizeof(ra.stage_units));
-        ra.pvec = c->vaee_pvec; ra.pe = c->vaee_pe; ra.tok = c->vaee_tok; ra.emb_bias = c->vaee_emb_bias;
-        ra.x = ws; ws += rows * kD;
-        ra.q = ws; ws += rows * kD;
-        ra.k = ws; ws += rows * kD;
-        ra.v = ws; ws += rows * kD;
-        float* attn_o = ws; ws += rows * kD;
-        ra.attn_o = attn_o;
-        ra.skip = ws; ws += 4 * rows * kD;
-        ra.stats_out = ws;  // [nb][2][128] <= the decoder's [nb][9][128] cross-attention slot
-        ra.lengths = lengths ? c->d_lengths + b0 : nullptr;
+    // fp32x from kFusedMinClips clips of the call (or as amuse_set_decode_path pins it - the decode's rule): stages 1..9 on the row kernel without split-K (FUSED), or the
+    // whole encoder as one persistent workgroup per clip (CLIP)
+    const int epath = encode_path_of(c, precision, B);
+    const bool rows8 = epath != AMUSE_DECODE_STAGED;
+    return for_chunks(B, chunk, [&](int b0, int nb) -> int {
+        const StageWs w = carve_stage_ws(c->vae_ws, (size_t)nb * kEncRows);
+        StageArgs a = stage_args(c->enc, precision, w, nb);
+        VaeRowsArgs& ra = a.rows;
+        ra.tok = c->vaee_tok;
+        ra.stats_out = w.tail;  // [nb][2][128] <= the decoder's [nb][9][128] cross-attention slot
+        ra.lengths = a.attn.lengths = lengths ? c->d_lengths + b0 : nullptr;
         ra.enc_feats = feats + (size_t)b0 * kFrames * kFeats;
-        ra.B = nb;
-        VaeAttnArgs aa{};
-        aa.q = ra.q; aa.k = ra.k; aa.v = ra.v; aa.lengths = ra.lengths; aa.o = attn_o; aa.B = nb;
-        // fp32x from kFusedMinClips clips of the call (or as amuse_set_decode_path pins it - the decode's rule): stages 1..9 on the row kernel without split-K
-        const int epath = encode_path_of(c, precision, B);
-        const bool rows8 = epath != AMUSE_DECODE_STAGED;
-        if (epath == AMUSE_DECODE_CLIP) {   // (the decode's rule and pins) the whole encoder as one persistent workgroup per clip
+        if (epath == AMUSE_DECODE_CLIP) {
             DenFusedXArgs fx{};
-            fx.wstream = c->vaee_wfx; fx.pvec = c->vaee_pvec; fx.emb_bias = c->vaee_emb_bias; fx.pe = c->vaee_pe; fx.ttok = c->vaee_tok;
-            fx.x_in = ra.enc_feats; fx.eps_out = ra.stats_out; fx.lengths = ra.lengths; fx.obuf = attn_o; fx.skip = ra.skip;
+            fx.wstream = c->enc.fusedx; fx.pvec = ra.pvec; fx.emb_bias = ra.emb_bias; fx.pe = ra.pe; fx.ttok = ra.tok;
+            fx.x_in = ra.enc_feats; fx.eps_out = ra.stats_out; fx.lengths = ra.lengths; fx.obuf = w.attn_o; fx.skip = w.skip;
             fx.B = nb; fx.S = kEncRows; fx.npre = 2; fx.encode = 1;
             HIP_TRY(launch_den_fusedx(fx, st));
-            const size_t o = (size_t)b0 * kD;
-            HIP_TRY(launch_vae_latent(ra.stats_out, eps ? eps + o : nullptr, mu_out ? mu_out + o : nullptr, std_out ? std_out + o : nullptr, latent_out ? latent_out + o : nullptr, nb, st));
-            continue;
+        } else {
+            twin_rows8(a, c->enc, rows8);
+            if (int e = run_stages(a, precision, {VAE_MODE_ENC, 0, 1, rows8 ? 9 : 0, VAE_MODE_ENC, true}, st)) return e;
         }
-        VaeRowsArgs r8 = ra;
-        if (rows8) {
-            r8.wstream = c->vaee_w8x;
-            memcpy(r8.stage_base, c->vaee_w8x_base, sizeof(r8.stage_base));
-        }
-        for (int stage = 0; stage < kVaeStages; ++stage) {
-            ra.stage = stage;
-            ra.tiles = stage == kVaeStages - 1 ? 1 : 19;       // only the distribution rows leave the last block
-            aa.q_tiles = stage == kLayers - 1 ? 1 : 19;
-            r8.stage = stage;
-            r8.tiles = ra.tiles;
-            if (rows8 && stage >= 1) HIP_TRY(launch_vae_rows8x(r8, st, VAE_MODE_ENC));
-            else HIP_TRY(launch_vae_rows(ra, precision, VAE_MODE_ENC, st));
-            if (stage < kLayers) HIP_TRY(launch_vae_attn(aa, precision, VAE_MODE_ENC, st));
-        }
-        const size_t o = (size_t)b0 * kD;
-        HIP_TRY(launch_vae_latent(ra.stats_out, eps ? eps + o : nullptr, mu_out ? mu_out + o : nullptr,
-                                  std_out ? std_out + o : nullptr, latent_out ? latent_out + o : nullptr, nb, st));
-    }
-    return 0;
+        HIP_TRY(launch_vae_latent(ra.stats_out, at_clip(eps, b0, kD), at_clip(mu_out, b0, kD), at_clip(std_out, b0, kD), at_clip(latent_out, b0, kD), nb, st));
+        return 0;
+    });
 }
 
 int amuse_smplx_to_feats(amuse_ctx* c, const float* poses, const float* trans, int B, float* feats_out, void* stream) {

@@ -84,6 +84,30 @@ inline int resolve_path(int pin, int planned, int precision) {
     return (pin == AMUSE_DECODE_CLIP && precision == AMUSE_PREC_F32X) ? AMUSE_DECODE_CLIP : AMUSE_DECODE_FUSED;
 }
 
+// The weight images of one skip network - nine skip-connected blocks over [clips][rows][128]: MotionPrior's decoder and encoder, the pose-space trans_enc Denoiser - in
+// every layout a kernel consumes (amuse_pack.hpp states the layouts), with the small parameters that belong to the network.  A slot a network has no kernel for stays null.
+struct RowNet {
+    uint4* staged[4] = {nullptr, nullptr, nullptr, nullptr};   // row-stage streams [stage][wave][units]: fp32 | bf16 | split-fp16 (fp32x) | fp16 (PREC_* index)
+    uint32_t stage_base[4][kVaeStages];
+    uint32_t stage_units[4][kVaeStages];
+    uint4* rows8 = nullptr;            // fp32x row stages without split-K (k_vae_rows8.hip): one stream per stage, consumption order
+    uint32_t rows8_base[kVaeStages];
+    uint4* fusedx = nullptr;           // fp32x, the whole network as ONE stream of unit pairs for the per-clip kernels (k_vae_fusedx.hip)
+    uint4* fused16[2] = {nullptr, nullptr};   // the per-clip 16-bit kernels' stream (k_vae_fused.hip / k_den_fused.hip): bf16 | fp16
+    float* pvec = nullptr;             // PV_* layout (the trans_dec Denoisers: PVX_*)
+    float* final_bias = nullptr;       // bias of the matrix behind stage 9, zero-padded to [384]
+    float* emb_bias = nullptr;         // bias of the matrix in front of stage 0 [128]
+    float* pe = nullptr;               // positional table [500][128] (the pose-space Denoiser borrows the context's query_pos table)
+};
+// Block 0's self-attention half of the decoder does not depend on the latent: one [300][128] constant per weight set and kernel family, produced on the stream of the
+// decode that first needed it (amuse_api.hip produce_c1 / consume_c1)
+struct HoistedC1 {
+    float* buf = nullptr;
+    bool valid = false;                // (re)computed by the next decode of its family after a weight change
+    hipEvent_t event = nullptr;        // recorded behind the launches that produced buf ...
+    hipStream_t stream = nullptr;      // ... on this stream: a decode on ANOTHER stream waits on the event first
+};
+
 struct amuse_ctx {
     int device = 0;
     int arch = AMUSE_ARCH_ENC;         // Denoiser variant (amuse_create_arch); anything but AMUSE_ARCH_ENC runs through `var`
@@ -116,31 +140,14 @@ struct amuse_ctx {
     float *te_w1t = nullptr, *te_b1 = nullptr, *te_w2t = nullptr, *te_b2 = nullptr;
     float* cond_wt[3] = {nullptr, nullptr, nullptr};
     float* cond_b[3] = {nullptr, nullptr, nullptr};
-    // prior decoder
-    uint4* vae_w[4] = {nullptr, nullptr, nullptr, nullptr};   // staged decode streams: fp32 | bf16 | split-fp16 (fp32x) | fp16
-    uint32_t vae_stage_base[4][kVaeStages];
-    uint32_t vae_stage_units[4][kVaeStages];
-    uint4* vae_wf = nullptr;           // bf16 stream of the fused decode kernel (k_vae_fused.hip)
-    uint4* vae_wfh = nullptr;          // its fp16 twin (k_vae_fusedh.hip, AMUSE_PREC_F16)
-    float* vae_c1[4] = {nullptr, nullptr, nullptr, nullptr};   // block 0's self-attention half of the fused decoder, bf16 | fp16 build: [300][128] (+ the tap scratch behind it); [2]: of the fp32x row stages
-    bool vae_c1_valid[4] = {false, false, false, false};   // (re)computed by the next fused decode after a weight change
-    hipEvent_t vae_c1_ev[4] = {nullptr, nullptr, nullptr, nullptr};     // recorded behind the launches that produced vae_c1[i] ...
-    hipStream_t vae_c1_stream[4] = {nullptr, nullptr, nullptr, nullptr}; // ... on this stream: a decode on ANOTHER stream waits on the event first
-    uint4* vae_w8x = nullptr;          // fp32x row stages without split-K (k_vae_rows8.hip): one stream per stage, consumption order
-    uint32_t vae_w8x_base[kVaeStages];
-    uint4* vaee_wfx = nullptr;         // fp32x encoder as one per-clip kernel (k_vae_fusedx.hip k_den_fusedx<encode>): one stream for the whole network
-    uint4* vae_wfx = nullptr;          // fp32x fused decoder (k_vae_fusedx.hip): one stream of unit pairs for the whole network, consumption order
-    uint4* vaee_w8x = nullptr;         // the same for MotionPrior.encode's stages 1..9 (AMUSE_UPD_ENCODER | AMUSE_UPD_F32X)
-    uint32_t vaee_w8x_base[kVaeStages];
+    // MotionPrior: decoder and encoder networks; the decoder's cross-attention (one memory token: the latent) as plain matrices for launch_vae_ca
+    RowNet dec, enc;
+    float *vae_wv_t = nullptr, *vae_bv = nullptr, *vae_wo_t = nullptr, *vae_bo = nullptr;
+    float* vaee_tok = nullptr;         // global_motion_token [2][128]
+    HoistedC1 c1_bf16, c1_f16;         // of the fused decoder's bf16 | fp16 build: [300][128] + the tap scratch behind it
+    HoistedC1 c1_rows8, c1_clip;       // of the fp32x row stages without split-K | of the fp32x per-clip decoder: [300][128]
     uint4* vae_skip = nullptr; size_t vae_skip_cap = 0;   // clips
     float* vae_ca_ws = nullptr; size_t vae_ca_cap = 0;    // clips
-    float *vae_pvec = nullptr, *vae_final_bias = nullptr, *vae_pe = nullptr;
-    float *vae_wv_t = nullptr, *vae_bv = nullptr, *vae_wo_t = nullptr, *vae_bo = nullptr;
-    // prior encoder (MotionPrior.encode)
-    uint4* vaee_w[4] = {nullptr, nullptr, nullptr, nullptr};
-    uint32_t vaee_stage_base[4][kVaeStages];
-    uint32_t vaee_stage_units[4][kVaeStages];
-    float *vaee_pvec = nullptr, *vaee_pe = nullptr, *vaee_tok = nullptr, *vaee_emb_bias = nullptr;
     // schedule
     int T = 0;
     int* d_timesteps = nullptr;
@@ -182,12 +189,14 @@ int upload(amuse_ctx* c, T** dst, const void* src, size_t bytes, int kind = PREC
     HIP_TRY(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
     return 0;
 }
-int ensure(float** p, size_t* cap, size_t need_floats) {
-    if (*cap >= need_floats) return 0;
+// grow-only buffer: `cap` and `need` in the caller's unit (elements, or clips with `elems` = the elements that many clips take)
+template <typename T>
+int ensure(T** p, size_t* cap, size_t need, size_t elems = 0) {
+    if (*cap >= need) return 0;
     if (*p) HIP_TRY(hipFree(*p));
     *p = nullptr; *cap = 0;
-    HIP_TRY(hipMalloc((void**)p, need_floats * sizeof(float)));
-    *cap = need_floats;
+    HIP_TRY(hipMalloc((void**)p, (elems ? elems : need) * sizeof(T)));
+    *cap = need;
     return 0;
 }
 }  // namespace

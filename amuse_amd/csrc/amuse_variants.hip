@@ -8,24 +8,18 @@ struct amuse_variant {
     // arch DEC: [4 waves][units + kRing][64] per precision (PREC_* index)
     uint4* dec_w[4] = {nullptr, nullptr, nullptr, nullptr};
     uint32_t dec_units[4] = {0, 0, 0, 0};
-    // pose-space archs: staged streams [stage][wave][units] per precision
-    uint4* rows_w[4] = {nullptr, nullptr, nullptr, nullptr};
-    uint32_t stage_base[4][kVaeStages];
-    uint32_t stage_units[4][kVaeStages];
-    uint4* rows8_w = nullptr;                   // fp32x, diffusion_only + trans_enc: stages 1..8 for the row kernel without split-K (k_vae_rows8.hip, ENC form)
-    uint32_t rows8_base[kVaeStages];
-    uint4* fusedx_w = nullptr;                  // fp32x, diffusion_only + trans_enc: the whole step as ONE stream for the per-clip kernel (k_vae_fusedx.hip k_den_fusedx)
-    float* pvec = nullptr;           // PV_* (ENC_POSE) / PVX_* (trans_dec archs) layout
+    // pose-space archs: the step's network.  ENC_POSE (diffusion_only + trans_enc) is a skip network with every stream - rows8: stages 1..8 (k_vae_rows8.hip, ENC form),
+    // fusedx / fused16: the whole step as one stream for k_den_fusedx / k_den_fused; DEC_POSE has the staged streams only.  emb_bias / final_bias: pose_embd.bias,
+    // pose_proj.bias; pe: the context's query_pos table.  Every arch: net.pvec, PV_* (ENC_POSE) / PVX_* (trans_dec archs) layout
+    RowNet net;
     float* m_pe = nullptr;           // mem_pos.pe [500][128]
     float *wkv_t = nullptr, *bkv = nullptr;       // trans_dec: cross-attention k / v projections [9][2][128 in][128 out], [9][2][128]
-    float *emb_bias = nullptr, *final_bias = nullptr;   // pose_embd.bias [128], pose_proj.bias padded to [384]
     float* tkv_sched = nullptr;      // [AMUSE_MAX_STEPS][9][2][128]: K / V of the time memory token per step of the schedule
     // workspaces
     float* ckv = nullptr; size_t ckv_cap = 0;     // [B][ncond][9][2][128]
     float* tkv1 = nullptr; size_t tkv1_cap = 0;   // teacher-forced steps: [1 or B][9][2][128]
     float* ws = nullptr; size_t ws_cap = 0;       // pose stages: x, q, k, v, o, 4 skip levels of [B][304][128]
-    uint4* fused_w[2] = {nullptr, nullptr};       // ENC_POSE: the fused step kernel's stream (k_den_fused.hip), bf16 | fp16
-    uint4* skip = nullptr; size_t skip_cap = 0;   // its skip stack, clips
+    uint4* skip = nullptr; size_t skip_cap = 0;   // ENC_POSE: the fused step kernel's (k_den_fused.hip) skip stack, clips
     float* tt = nullptr; size_t tt_cap = 0;       // teacher-forced steps: time tokens [1 or B][128] | device copy of the timesteps
 };
 
@@ -92,26 +86,6 @@ void pack_dec_layer(std::vector<uint4>& s, int prec, const Params& P, int l, int
     pack_gemm(s, prec, P.get(p + ".linear2.weight"), 128, 512, range(0, 8), range(8 * w, 8 * w + 8));
 }
 
-int stage_lengths_v(amuse_ctx* c, const int* lengths, int B, hipStream_t st) {
-    if (!lengths) return 0;
-    bool full = false;
-    for (int b = 0; b < B; ++b) {
-        if (lengths[b] < 1 || lengths[b] > kFrames) return fail(AMUSE_EINVAL, "lengths[%d] = %d not in 1..300", b, lengths[b]);
-        full |= lengths[b] == kFrames;
-    }
-    // lengths_to_mask sizes the mask by max(lengths) and `sample[~mask.T] = 0` needs it to be 300 (denoiser.py:145,187)
-    if (!full) return fail(AMUSE_EINVAL, "max(lengths) must be 300 (the reference's mask indexing fails otherwise)");
-    if (c->len_cap < (size_t)B) {
-        if (c->d_lengths) HIP_TRY(hipFree(c->d_lengths));
-        c->d_lengths = nullptr; c->len_cap = 0;
-        HIP_TRY(hipMalloc((void**)&c->d_lengths, (size_t)B * sizeof(int)));
-        c->len_cap = B;
-    }
-    HIP_TRY(hipMemcpyAsync(c->d_lengths, lengths, (size_t)B * sizeof(int), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return 0;
-}
-
 // condition tokens (+ positions) into c->cond_tok [B][ncond][128]; trans_dec archs: their K / V into v->ckv
 int variant_cond(amuse_ctx* c, const float* con, const float* emo, const float* sty, int B, int* ncond_out, hipStream_t st) {
     amuse_variant* v = c->var;
@@ -151,18 +125,19 @@ struct PoseStep {
 int step_path_of(amuse_ctx* c, int precision, int B) {
     int path = resolve_path(c->decode_path, plan_step_path(c->arch, precision, B), precision);
     if (c->arch != AMUSE_ARCH_ENC_POSE) path = AMUSE_DECODE_STAGED;
-    if (path == AMUSE_DECODE_CLIP && !c->var->fusedx_w) path = AMUSE_DECODE_FUSED;
-    if (path == AMUSE_DECODE_FUSED && precision == PREC_F16X2 && !c->var->rows8_w) path = AMUSE_DECODE_STAGED;
+    if (path == AMUSE_DECODE_CLIP && !c->var->net.fusedx) path = AMUSE_DECODE_FUSED;
+    if (path == AMUSE_DECODE_FUSED && precision == PREC_F16X2 && !c->var->net.rows8) path = AMUSE_DECODE_STAGED;
     return c->last_plan[3] = path;
 }
 
 int pose_step(amuse_ctx* c, const PoseStep& p, int nb, int precision, bool fused, hipStream_t st) {
     amuse_variant* v = c->var;
+    const RowNet& n = v->net;
     const bool dec = arch_dec(c->arch);
     if (fused) {
         DenFusedArgs fa{};
-        fa.wstream = v->fused_w[precision == PREC_F16]; fa.pvec = v->pvec; fa.final_bias = v->final_bias; fa.emb_bias = v->emb_bias;
-        fa.pe = c->den_pe; fa.ttok = p.ttok; fa.ttok_stride = p.ttok_stride; fa.ctok = p.cond_tok; fa.skip = v->skip;
+        fa.wstream = n.fused16[precision == PREC_F16]; fa.pvec = n.pvec; fa.final_bias = n.final_bias; fa.emb_bias = n.emb_bias;
+        fa.pe = n.pe; fa.ttok = p.ttok; fa.ttok_stride = p.ttok_stride; fa.ctok = p.cond_tok; fa.skip = v->skip;
         fa.eps_out = p.eps_out; fa.coef = p.coef; fa.step_noise = p.step_noise; fa.lengths = p.lengths_dev;
         fa.seed = p.seed; fa.clip0 = p.clip0; fa.step = p.step; fa.B = nb; fa.npre = 1 + p.ncond;
         fa.ablate_attention = c->ablate & 1;
@@ -173,62 +148,42 @@ int pose_step(amuse_ctx* c, const PoseStep& p, int nb, int precision, bool fused
         return 0;
     }
     const int npre = dec ? 0 : 1 + p.ncond, S = kFrames + npre;
-    const size_t rows = (size_t)nb * S;
-    float* ws = v->ws;
-    VaeRowsArgs ra{};
-    ra.wstream = v->rows_w[precision];
-    memcpy(ra.stage_base, v->stage_base[precision], sizeof(ra.stage_base));
-    memcpy(ra.stage_units, v->stage_units[precision], sizeof(ra.stage_units));
-    ra.pvec = v->pvec; ra.final_bias = v->final_bias; ra.pe = c->den_pe; ra.emb_bias = v->emb_bias;
-    ra.x = ws; ws += rows * kD;
-    ra.q = ws; ws += rows * kD;
-    ra.k = ws; ws += rows * kD;
-    ra.v = ws; ws += rows * kD;
-    float* attn_o = ws; ws += rows * kD;
-    ra.attn_o = attn_o;
-    ra.skip = ws;
-    ra.lengths = p.lengths_dev;
-    ra.enc_feats = p.x_in; ra.feats_out = p.eps_out; ra.x_out = p.x_out; ra.coef = p.coef; ra.step_noise = p.step_noise;
-    ra.seed = p.seed; ra.clip0 = p.clip0; ra.step = p.step;
-    ra.B = nb; ra.tiles = 19; ra.S = S; ra.npre = npre;
-    ra.pre_tok_t = p.ttok; ra.pre_tok_t_stride = p.ttok_stride; ra.pre_tok_c = p.cond_tok;
-    ra.mem = MemKV{p.tkv, p.tkv_clip_stride, p.ckv, p.ncond};
-    VaeAttnArgs aa{};
-    aa.q = ra.q; aa.k = ra.k; aa.v = ra.v; aa.lengths = nullptr; aa.o = attn_o; aa.B = nb; aa.q_tiles = 19; aa.S = S;
-    const int mode = dec ? VAE_MODE_DEN_D : VAE_MODE_DEN_E;
-    VaeRowsArgs r8 = ra;
-    if (p.rows8) {   // (fp32x, trans_enc: stages 1..8 are plain encoder-layer stages - the row kernel without split-K, as MotionPrior.encode's)
-        r8.wstream = v->rows8_w;
-        memcpy(r8.stage_base, v->rows8_base, sizeof(r8.stage_base));
-    }
-    if (p.rows8 && p.fusedx && v->fusedx_w) {   // the whole step as one persistent workgroup per clip (its scratch: this path's attn_o and skip arrays)
+    const StageWs w = carve_stage_ws(v->ws, (size_t)nb * S);
+    if (p.rows8 && p.fusedx && n.fusedx) {   // the whole step as one persistent workgroup per clip (its scratch: this path's attn_o and skip arrays)
         DenFusedXArgs fx{};
-        fx.wstream = v->fusedx_w; fx.pvec = v->pvec; fx.emb_bias = v->emb_bias; fx.final_bias = v->final_bias; fx.pe = c->den_pe;
+        fx.wstream = n.fusedx; fx.pvec = n.pvec; fx.emb_bias = n.emb_bias; fx.final_bias = n.final_bias; fx.pe = n.pe;
         fx.ttok = p.ttok; fx.ttok_stride = p.ttok_stride; fx.ctok = p.cond_tok;
         fx.x_in = p.x_in; fx.x_out = p.x_out; fx.eps_out = p.eps_out; fx.coef = p.coef; fx.step_noise = p.step_noise; fx.lengths = p.lengths_dev;
-        fx.obuf = attn_o; fx.skip = ra.skip; fx.seed = p.seed; fx.clip0 = p.clip0; fx.step = p.step; fx.B = nb; fx.S = S; fx.npre = npre;
+        fx.obuf = w.attn_o; fx.skip = w.skip; fx.seed = p.seed; fx.clip0 = p.clip0; fx.step = p.step; fx.B = nb; fx.S = S; fx.npre = npre;
         HIP_TRY(launch_den_fusedx(fx, st));
         return 0;
     }
-    for (int stage = 0; stage < kVaeStages; ++stage) {
-        ra.stage = stage;
-        r8.stage = stage;
-        if (p.rows8 && stage >= 1 && stage <= 8) HIP_TRY(launch_vae_rows8x(r8, st, VAE_MODE_ENC));
-        else HIP_TRY(launch_vae_rows(ra, precision, mode, st));
-        if (stage < kLayers) HIP_TRY(launch_vae_attn(aa, precision, mode, st));
-    }
-    return 0;
+    StageArgs a = stage_args(n, precision, w, nb);
+    VaeRowsArgs& ra = a.rows;
+    ra.lengths = p.lengths_dev;   // (the frames' eps rows; the attention sees every row)
+    ra.enc_feats = p.x_in; ra.feats_out = p.eps_out; ra.x_out = p.x_out; ra.coef = p.coef; ra.step_noise = p.step_noise;
+    ra.seed = p.seed; ra.clip0 = p.clip0; ra.step = p.step;
+    ra.S = a.attn.S = S; ra.npre = npre;
+    ra.pre_tok_t = p.ttok; ra.pre_tok_t_stride = p.ttok_stride; ra.pre_tok_c = p.cond_tok;
+    ra.mem = MemKV{p.tkv, p.tkv_clip_stride, p.ckv, p.ncond};
+    // (fp32x, trans_enc: stages 1..8 are plain encoder-layer stages - the row kernel without split-K, as MotionPrior.encode's)
+    twin_rows8(a, n, p.rows8);
+    return run_stages(a, precision, {dec ? VAE_MODE_DEN_D : VAE_MODE_DEN_E, 0, 1, p.rows8 ? 8 : 0, VAE_MODE_ENC, false}, st);
 }
 int ensure_pose_ws(amuse_variant* v, int chunk, bool fused) {
-    if (fused) {
-        if (v->skip_cap >= (size_t)chunk) return 0;
-        if (v->skip) HIP_TRY(hipFree(v->skip));
-        v->skip = nullptr; v->skip_cap = 0;
-        HIP_TRY(hipMalloc((void**)&v->skip, (size_t)chunk * kVaeFusedSkipBytesPerClip));
-        v->skip_cap = chunk;
-        return 0;
-    }
+    if (fused) return ensure(&v->skip, &v->skip_cap, (size_t)chunk, (size_t)chunk * (kVaeFusedSkipBytesPerClip / sizeof(uint4)));
     return ensure(&v->ws, &v->ws_cap, (size_t)chunk * kPoseWsPerClip);
+}
+// which kernels the steps of a call take and how its clips are chunked (step_path_of: from the CALL's clip count)
+struct PoseRun { bool fused, rows8, fusedx; int chunk; };
+PoseRun pose_run_of(amuse_ctx* c, int precision, int B) {
+    const int spath = step_path_of(c, precision, B);
+    PoseRun r;
+    r.fused = is_op16(precision) && spath != AMUSE_DECODE_STAGED;        // k_den_fused
+    r.rows8 = precision == PREC_F16X2 && spath != AMUSE_DECODE_STAGED;   // k_vae_rows8x<ENC> for stages 1..8
+    r.fusedx = precision == PREC_F16X2 && spath == AMUSE_DECODE_CLIP;    // k_den_fusedx
+    r.chunk = r.fused ? B : (B < kPoseChunk ? B : kPoseChunk);
+    return r;
 }
 }  // namespace
 
@@ -256,47 +211,34 @@ int variant_build(amuse_ctx* c, const float* den, int what) {
         }
     } else {
         const float *w_emb = D.get("pose_embd.weight"), *w_proj = D.get("pose_proj.weight");
-        // staged streams (pack_staged_stream): pose_embd in front of stage 0, pose_proj behind stage 9; between them the encoder blocks' stages (trans_enc) or,
-        // stage i + 1, what follows decoder layer i's self-attention (pack_dec_layer) + in_proj(i + 1) (trans_dec)
-        for (int prec = 0; prec < 4; ++prec) {
-            if (!(what & kUpdBit[prec])) continue;
-            std::vector<uint4> all;
-            const auto content = [&](std::vector<uint4>& s, int st, int w) {
-                if (st == 0) pack_in_matrix_wave(s, prec, w_emb, w);
-                if (!dec) pack_skipnet_stage(s, prec, D, "encoder", st, w);
-                else {
+        RowNet& n = v->net;
+        if (!dec) {
+            // trans_enc: a skip network with pose_embd in front of stage 0 and pose_proj behind stage 9.  Stages 1..8 on the row kernel without split-K (pose_embd /
+            // pose_proj + update stay with k_vae_rows); the whole step as one per-clip stream for k_den_fusedx and, 16-bit, for k_den_fused
+            if (int e = build_rownet_streams(c, n, D, {"encoder", w_emb, w_proj, 1, 8, true, 0}, what)) return e;
+        } else {
+            // trans_dec, staged streams only (pack_staged_stream): between pose_embd and pose_proj, stage i + 1 holds what follows decoder layer i's self-attention
+            // (pack_dec_layer) + in_proj(i + 1)
+            for (int prec = 0; prec < 4; ++prec) {
+                if (!(what & kUpdBit[prec])) continue;
+                std::vector<uint4> all;
+                const auto content = [&](std::vector<uint4>& s, int st, int w) {
+                    if (st == 0) pack_in_matrix_wave(s, prec, w_emb, w);
                     if (st >= 1) pack_dec_layer(s, prec, D, st - 1, w, false);
                     if (st < 9) pack_qkv(s, prec, D.get(dec_name(st) + ".self_attn.in_proj_weight"), w, false);
-                }
-                if (st == 9) pack_out_matrix_wave(s, prec, w_proj, w);
-            };
-            if (int e = pack_staged_stream(all, v->stage_base[prec], v->stage_units[prec], content)) return e;
-            if (upload(c, &v->rows_w[prec], all.data(), all.size() * sizeof(uint4), prec, kUpdBit[prec])) return AMUSE_EHIP;
-        }
-        if (!dec && (what & AMUSE_UPD_F32X)) {   // fp32x row stages without split-K: stages 1..8 (pose_embd / pose_proj + update stay with k_vae_rows)
-            std::vector<uint4> s;
-            if (int e = pack_rows8_stream(s, v->rows8_base, D, "encoder", 1, 8, nullptr)) return e;
-            if (upload(c, &v->rows8_w, s.data(), s.size() * sizeof(uint4), PREC_F16X2, AMUSE_UPD_F32X)) return AMUSE_EHIP;
-        }
-        if (!dec && (what & AMUSE_UPD_F32X)) {   // fp32x: the whole step as one per-clip stream (k_den_fusedx): pose_embd in front, pose_proj behind
-            std::vector<uint4> s;
-            if (int e = pack_fusedx_stream(s, D, "encoder", w_emb, w_proj)) return e;
-            if (upload(c, &v->fusedx_w, s.data(), s.size() * sizeof(uint4), PREC_F16X2, AMUSE_UPD_F32X)) return AMUSE_EHIP;
-        }
-        if (!dec)   // 16-bit fused step kernel (k_den_fused.hip): the fused decoder's layout with pose_embd in front and encoder blocks
-            for (const int p16 : {PREC_BF16, PREC_F16}) {
-                if (!(what & kUpdBit[p16])) continue;
-                std::vector<uint4> s;
-                if (int e = pack_fused16_stream(s, p16, D, "encoder", w_emb, w_proj)) return e;
-                if (upload(c, &v->fused_w[p16 == PREC_F16], s.data(), s.size() * sizeof(uint4), p16, kUpdBit[p16])) return AMUSE_EHIP;
+                    if (st == 9) pack_out_matrix_wave(s, prec, w_proj, w);
+                };
+                if (int e = pack_staged_stream(all, n.stage_base[prec], n.stage_units[prec], content)) return e;
+                if (upload(c, &n.staged[prec], all.data(), all.size() * sizeof(uint4), prec, kUpdBit[prec])) return AMUSE_EHIP;
             }
+        }
         std::vector<float> fb(16 * kFeatTiles, 0.f);
         memcpy(fb.data(), D.get("pose_proj.bias"), kFeats * 4);
-        if (upload(c, &v->final_bias, fb.data(), fb.size() * 4) || upload(c, &v->emb_bias, D.get("pose_embd.bias"), 128 * 4)) return AMUSE_EHIP;
+        if (upload(c, &n.final_bias, fb.data(), fb.size() * 4) || upload(c, &n.emb_bias, D.get("pose_embd.bias"), 128 * 4)) return AMUSE_EHIP;
     }
     {
         const std::vector<float> pv = dec ? build_pvec_dec(D) : build_pvec(D, "encoder", false);
-        if (upload(c, &v->pvec, pv.data(), pv.size() * 4)) return AMUSE_EHIP;
+        if (upload(c, &v->net.pvec, pv.data(), pv.size() * 4)) return AMUSE_EHIP;
     }
     if (dec) {
         std::vector<float> wkv((size_t)kLayers * 2 * kD * kD), bkv((size_t)kLayers * 2 * kD);
@@ -312,6 +254,7 @@ int variant_build(amuse_ctx* c, const float* den, int what) {
     }
     // what every arch shares with the shipped configuration: positions, timestep frequencies, time-embedding MLP + condition projections
     if (upload(c, &c->den_pe, D.get("query_pos.pe"), 500 * 128 * 4) || upload(c, &v->m_pe, D.get("mem_pos.pe"), 500 * 128 * 4)) return AMUSE_EHIP;
+    v->net.pe = c->den_pe;
     float fr[128];
     for (int k = 0; k < 128; ++k) fr[k] = expf(-logf(10000.f) * (float)k / 128.f);
     if (!c->den_freqs && upload(c, &c->den_freqs, fr, sizeof(fr), PREC_F32, kImgConst)) return AMUSE_EHIP;   // (amuse_set_schedule may have installed the caller's values)
@@ -330,7 +273,7 @@ void variant_destroy(amuse_ctx* c) {
 
 int variant_set_schedule(amuse_ctx* c, hipStream_t st) {
     // time token of every step + its position: query_pos.pe[0] in front of the frames, mem_pos.pe[0] as the first memory token
-    HIP_TRY(launch_time_tokens(c->d_timesteps, c->T, c->den_freqs, c->te_w1t, c->te_b1, c->te_w2t, c->te_b2, time_pe_row(c), c->d_time_tok, st));
+    HIP_TRY(time_tokens(c, c->d_timesteps, c->T, time_pe_row(c), c->d_time_tok, st));
     if (arch_dec(c->arch)) HIP_TRY(launch_mem_kv(c->d_time_tok, c->T, c->var->wkv_t, c->var->bkv, c->var->tkv_sched, st));
     return 0;
 }
@@ -343,7 +286,7 @@ int variant_sample(amuse_ctx* c, const float* con, const float* emo, const float
     if (!arch_pose(c->arch)) {
         SampleDecArgs a{};
         a.wstream = v->dec_w[precision]; a.wave_units = v->dec_units[precision];
-        a.pvec = v->pvec; a.pe0 = c->den_pe;
+        a.pvec = v->net.pvec; a.pe0 = c->den_pe;
         a.mem = MemKV{v->tkv_sched, 0, v->ckv, ncond};
         a.tkv_step_stride = kTkv;
         a.coef = c->d_coef; a.x_init = x_init; a.step_noise = step_noise;
@@ -356,15 +299,10 @@ int variant_sample(amuse_ctx* c, const float* con, const float* emo, const float
     const size_t sd = AMUSE_POSE_STATE;
     if (x_init) HIP_TRY(hipMemcpyAsync(out, x_init, (size_t)B * sd * sizeof(float), hipMemcpyDeviceToDevice, st));
     else HIP_TRY(launch_counter_normal(seed, clip0, B, 0, 0, out, st, (int)sd));
-    const int spath = step_path_of(c, precision, B);
-    const bool fused = is_op16(precision) && spath != AMUSE_DECODE_STAGED;        // k_den_fused
-    const bool rows8 = precision == PREC_F16X2 && spath != AMUSE_DECODE_STAGED;   // k_vae_rows8x<ENC> for stages 1..8
-    const bool fusedx = precision == PREC_F16X2 && spath == AMUSE_DECODE_CLIP;    // k_den_fusedx
-    const int chunk = fused ? B : (B < kPoseChunk ? B : kPoseChunk);
-    if (int e = ensure_pose_ws(v, chunk, fused)) return e;
+    const PoseRun run = pose_run_of(c, precision, B);
+    if (int e = ensure_pose_ws(v, run.chunk, run.fused)) return e;
     for (int step = 0; step < c->T; ++step) {
-        for (int b0 = 0; b0 < B; b0 += chunk) {
-            const int nb = (B - b0) < chunk ? (B - b0) : chunk;
+        const int e = for_chunks(B, run.chunk, [&](int b0, int nb) {
             PoseStep p{};
             p.x_in = out + (size_t)b0 * sd; p.x_out = out + (size_t)b0 * sd; p.eps_out = nullptr;
             p.coef = c->d_coef + (size_t)step * 8;
@@ -374,9 +312,10 @@ int variant_sample(amuse_ctx* c, const float* con, const float* emo, const float
             p.cond_tok = c->cond_tok + (size_t)b0 * ncond * kD;
             p.ckv = v->ckv ? v->ckv + (size_t)b0 * ncond * kTkv : nullptr;
             p.lengths_dev = nullptr;   // the sampling loop passes full lengths (infer_ldm.py:135)
-            p.ncond = ncond; p.step = step; p.seed = seed; p.clip0 = clip0 + (uint64_t)b0; p.rows8 = rows8; p.fusedx = fusedx;
-            if (int e = pose_step(c, p, nb, precision, fused, st)) return e;
-        }
+            p.ncond = ncond; p.step = step; p.seed = seed; p.clip0 = clip0 + (uint64_t)b0; p.rows8 = run.rows8; p.fusedx = run.fusedx;
+            return pose_step(c, p, nb, precision, run.fused, st);
+        });
+        if (e) return e;
         if (traj_out) HIP_TRY(hipMemcpyAsync(traj_out + (size_t)step * B * sd, out, (size_t)B * sd * sizeof(float), hipMemcpyDeviceToDevice, st));
     }
     return 0;
@@ -392,7 +331,7 @@ int variant_denoise(amuse_ctx* c, const float* x_t, const int* timesteps, bool p
     int* ts = reinterpret_cast<int*>(ttok + (size_t)B * kD);     // [nt]
     HIP_TRY(hipMemcpyAsync(ts, timesteps, (size_t)nt * sizeof(int), hipMemcpyHostToDevice, st));
     HIP_TRY(hipStreamSynchronize(st));   // the host array belongs to the caller
-    HIP_TRY(launch_time_tokens(ts, nt, c->den_freqs, c->te_w1t, c->te_b1, c->te_w2t, c->te_b2, time_pe_row(c), ttok, st));
+    HIP_TRY(time_tokens(c, ts, nt, time_pe_row(c), ttok, st));
     if (arch_dec(c->arch)) {
         if (int e = ensure(&v->tkv1, &v->tkv1_cap, (size_t)nt * kTkv)) return e;
         HIP_TRY(launch_mem_kv(ttok, nt, v->wkv_t, v->bkv, v->tkv1, st));
@@ -402,7 +341,7 @@ int variant_denoise(amuse_ctx* c, const float* x_t, const int* timesteps, bool p
     if (!arch_pose(c->arch)) {
         SampleDecArgs a{};
         a.wstream = v->dec_w[precision]; a.wave_units = v->dec_units[precision];
-        a.pvec = v->pvec; a.pe0 = c->den_pe;
+        a.pvec = v->net.pvec; a.pe0 = c->den_pe;
         a.mem = MemKV{v->tkv1, per_clip ? (size_t)kTkv : 0, v->ckv, ncond};
         a.tkv_step_stride = 0;
         a.coef = c->d_coef1; a.x_init = x_t; a.eps_out = eps_out; a.tap_out = tap_out;
@@ -411,16 +350,11 @@ int variant_denoise(amuse_ctx* c, const float* x_t, const int* timesteps, bool p
         return 0;
     }
     if (tap_out) return fail(AMUSE_EINVAL, "taps exist for the latent variants only");
-    if (int e = stage_lengths_v(c, lengths, B, st)) return e;
+    if (int e = stage_lengths(c, lengths, B, true, st)) return e;
     const size_t sd = AMUSE_POSE_STATE;
-    const int spath = step_path_of(c, precision, B);
-    const bool fused = is_op16(precision) && spath != AMUSE_DECODE_STAGED;        // k_den_fused
-    const bool rows8 = precision == PREC_F16X2 && spath != AMUSE_DECODE_STAGED;   // k_vae_rows8x<ENC> for stages 1..8
-    const bool fusedx = precision == PREC_F16X2 && spath == AMUSE_DECODE_CLIP;    // k_den_fusedx
-    const int chunk = fused ? B : (B < kPoseChunk ? B : kPoseChunk);
-    if (int e = ensure_pose_ws(v, chunk, fused)) return e;
-    for (int b0 = 0; b0 < B; b0 += chunk) {
-        const int nb = (B - b0) < chunk ? (B - b0) : chunk;
+    const PoseRun run = pose_run_of(c, precision, B);
+    if (int e = ensure_pose_ws(v, run.chunk, run.fused)) return e;
+    return for_chunks(B, run.chunk, [&](int b0, int nb) {
         PoseStep p{};
         p.x_in = x_t + (size_t)b0 * sd; p.x_out = nullptr; p.eps_out = eps_out + (size_t)b0 * sd; p.coef = nullptr;
         p.ttok = ttok + (per_clip ? (size_t)b0 * kD : 0); p.ttok_stride = per_clip ? kD : 0;
@@ -428,8 +362,7 @@ int variant_denoise(amuse_ctx* c, const float* x_t, const int* timesteps, bool p
         p.cond_tok = c->cond_tok + (size_t)b0 * ncond * kD;
         p.ckv = v->ckv ? v->ckv + (size_t)b0 * ncond * kTkv : nullptr;
         p.lengths_dev = lengths ? c->d_lengths + b0 : nullptr;
-        p.ncond = ncond; p.rows8 = rows8; p.fusedx = fusedx;
-        if (int e = pose_step(c, p, nb, precision, fused, st)) return e;
-    }
-    return 0;
+        p.ncond = ncond; p.rows8 = run.rows8; p.fusedx = run.fusedx;
+        return pose_step(c, p, nb, precision, run.fused, st);
+    });
 }

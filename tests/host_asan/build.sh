@@ -1,5 +1,5 @@
 #!/bin/bash
-# builds tests/host_asan/{host_asan,plan_sweep,pack_images} (the library's host code + stubbed runtime, -fsanitize=address,undefined): build.sh <out dir>
+# builds tests/host_asan/{host_asan,plan_sweep,pack_images,launch_args} (the library's host code + stubbed runtime, -fsanitize=address,undefined): build.sh <out dir>
 set -e
 here="$(cd "$(dirname "$0")" && pwd)"
 out=${1:-/tmp/amuse_host_asan}
@@ -18,3 +18,6 @@ $HIPCC --offload-host-only -std=c++17 $SAN -c "$here/hip_stub.cpp" -x hip -o "$o
 # the image log of the weight packers (tests/test_pack_images_cpu.py) on the same objects
 /opt/rocm/lib/llvm/bin/clang++ -std=c++17 $SAN -c "$here/pack_images.cpp" -o "$out/pack_images.o"
 /opt/rocm/lib/llvm/bin/clang++ $SAN "$out/pack_images.o" "$out/hip_stub.o" "$out/amuse_api.o" "$out/amuse_variants.o" "$out/amuse_audio_api.o" -o "$out/pack_images"
+# the launch log of the launch sequences (tests/test_launch_args_cpu.py) on the same objects
+/opt/rocm/lib/llvm/bin/clang++ -std=c++17 $SAN -c "$here/launch_args.cpp" -o "$out/launch_args.o"
+/opt/rocm/lib/llvm/bin/clang++ $SAN "$out/launch_args.o" "$out/hip_stub.o" "$out/amuse_api.o" "$out/amuse_variants.o" "$out/amuse_audio_api.o" -o "$out/launch_args"

@@ -6,12 +6,19 @@
 // The image log (amuse_stub_log(1), off by default; tests/test_pack_images_cpu.py): every host-to-"device" hipMemcpy prints its size, a 64-bit FNV-1a digest
 // and its first word; every launcher that takes a weight stream prints the digest of the image behind `wstream` and the stage / unit tables it is handed;
 // launch_repack prints element count, kind, the image it overwrites and a digest of its gather map.  That pins every byte the packers produce on any machine.
+//
+// The launch log (amuse_stub_log(2); tests/test_launch_args_cpu.py): one line per runtime call and per launch, in order - every launcher prints its name, its stream and
+// every field of its argument struct, hipMalloc / hipFree the block's size, the copies and memsets kind, size and pointers, hipEventRecord / hipStreamWaitEvent their
+// event and stream.  Pointers are printed so that the text is the same on any machine: `0`, `dev#<n>+<offset>/<block size>` inside the process's n-th hipMalloc block while it is live,
+// `<name>+<offset>` inside a buffer the driver registered (amuse_stub_name), `host` otherwise; streams and events by their order of creation; weight streams also
+// by image digest, stage tables as digests.  That pins what the image log leaves open: workspace carving, chunk offsets, the hoist launches and launch order.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <string>
 
 #include "../../amuse_amd/csrc/amuse_audio.hpp"
 #include "../../amuse_amd/csrc/amuse_kernels.hpp"
@@ -19,9 +26,10 @@
 static long g_live = 0;
 long amuse_stub_live_allocations() { return g_live; }
 
-static bool g_log = false;
-static std::map<const void*, uint64_t> g_image;   // "device" pointer -> digest of the last upload to it (while the log is on)
-void amuse_stub_log(int on) { g_log = on != 0; }
+static int g_level = 0;        // 0 off | 1 image log | 2 launch log
+static bool g_log = false;     // the image log's lines
+static std::map<const void*, uint64_t> g_image;   // "device" pointer -> digest of the last upload to it (while a log is on)
+void amuse_stub_log(int on) { g_level = on; g_log = on == 1; }
 static uint64_t fnv1a(const void* p, size_t n) {
     const unsigned char* b = static_cast<const unsigned char*>(p);
     uint64_t h = 0xcbf29ce484222325ull;
@@ -37,77 +45,251 @@ static void log_upload(const void* d, const void* s, size_t n) {
     memcpy(&first, s, n < 4 ? n : 4);
     const uint64_t h = fnv1a(s, n);
     g_image[d] = h;
-    printf("upload bytes=%zu digest=%016llx first=%08x\n", n, (unsigned long long)h, first);
+    if (g_log) printf("upload bytes=%zu digest=%016llx first=%08x\n", n, (unsigned long long)h, first);
 }
 
+// ---- the launch log's vocabulary
+struct Range { size_t bytes; std::string name; };
+struct Block { size_t bytes; int id; };
+static std::map<const char*, Block> g_blocks;    // live hipMalloc blocks; id = the n-th hipMalloc of the process
+static int g_nblocks = 0;
+static std::map<const char*, Range> g_named;      // the driver's buffers (amuse_stub_name)
+static std::map<const void*, int> g_streams, g_events;
+static int g_nstreams = 0, g_nevents = 0;
+void amuse_stub_name(const char* name, const void* p, size_t bytes) {
+    if (bytes) g_named[static_cast<const char*>(p)] = {bytes, name};
+    else g_named.erase(static_cast<const char*>(p));
+}
+static std::string ptr_text(const void* pv) {
+    const char* p = static_cast<const char*>(pv);
+    if (!p) return "0";
+    char buf[96];
+    auto b = g_blocks.upper_bound(p);
+    if (b != g_blocks.begin() && (size_t)(p - (--b)->first) <= b->second.bytes) {   // (one past the end is still that block: the tail of a carve)
+        snprintf(buf, sizeof(buf), "dev#%d+%zu/%zu", b->second.id, (size_t)(p - b->first), b->second.bytes);
+        return buf;
+    }
+    auto r = g_named.upper_bound(p);
+    if (r != g_named.begin() && (size_t)(p - (--r)->first) <= r->second.bytes) {
+        snprintf(buf, sizeof(buf), "%s+%zu", r->second.name.c_str(), (size_t)(p - r->first));
+        return buf;
+    }
+    return "host";
+}
+static std::string handle_text(const std::map<const void*, int>& ids, const void* h) {
+    if (!h) return "0";
+    const auto it = ids.find(h);
+    return it == ids.end() ? "?" : "#" + std::to_string(it->second);
+}
+// one line of the launch log: `name key=value ...`, printed when it goes out of scope
+struct Line {
+    std::string s;
+    explicit Line(const char* name) : s(name) {}
+    ~Line() { puts(s.c_str()); }
+    Line& kv(const char* k, const std::string& v) { s += ' '; s += k; s += '='; s += v; return *this; }
+    Line& p(const char* k, const void* v) { return kv(k, ptr_text(v)); }
+    Line& i(const char* k, long long v) { return kv(k, std::to_string(v)); }
+    Line& u(const char* k, unsigned long long v) { return kv(k, std::to_string(v)); }
+    Line& f(const char* k, float v) { char b[40]; snprintf(b, sizeof(b), "%a", (double)v); return kv(k, b); }   // (hex float: exact)
+    Line& x(const char* k, unsigned long long v) { char b[24]; snprintf(b, sizeof(b), "%016llx", v); return kv(k, b); }
+    Line& st(hipStream_t v) { return kv("stream", handle_text(g_streams, v)); }
+    Line& w(const void* v) { return p("wstream", v).x("image", image_of(v)); }
+};
+#define P_(f) p(#f, a.f)
+#define I_(f) i(#f, (long long)a.f)
+#define U_(f) u(#f, (unsigned long long)a.f)
+static const char* kind_text(hipMemcpyKind k) {
+    return k == hipMemcpyHostToDevice ? "h2d" : k == hipMemcpyDeviceToHost ? "d2h" : k == hipMemcpyDeviceToDevice ? "d2d" : k == hipMemcpyHostToHost ? "h2h" : "default";
+}
+static void log_copy(const char* name, void* d, const void* s, size_t n, hipMemcpyKind k) { Line(name).kv("kind", kind_text(k)).u("bytes", n).p("dst", d).p("src", s); }
+
 extern "C" {
-hipError_t hipMalloc(void** p, size_t n) { *p = malloc(n ? n : 1); ++g_live; return *p ? hipSuccess : hipErrorOutOfMemory; }
-hipError_t hipFree(void* p) { if (p) { if (g_log) g_image.erase(p); free(p); --g_live; } return hipSuccess; }
+hipError_t hipMalloc(void** p, size_t n) {
+    *p = malloc(n ? n : 1);
+    ++g_live;
+    if (*p) g_blocks[static_cast<const char*>(*p)] = {n, ++g_nblocks};
+    if (g_level == 2) Line("hipMalloc").u("bytes", n).p("ptr", *p);
+    return *p ? hipSuccess : hipErrorOutOfMemory;
+}
+hipError_t hipFree(void* p) {
+    if (p) {
+        g_image.erase(p);
+        if (g_level == 2) Line("hipFree").p("ptr", p);
+        g_blocks.erase(static_cast<const char*>(p));
+        free(p);
+        --g_live;
+    }
+    return hipSuccess;
+}
 hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind k) {
-    if (g_log && k == hipMemcpyHostToDevice) log_upload(d, s, n);
+    if (g_level == 2) log_copy("hipMemcpy", d, s, n, k);
+    if (g_level && k == hipMemcpyHostToDevice) log_upload(d, s, n);
     memcpy(d, s, n);
     return hipSuccess;
 }
-hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t) { memcpy(d, s, n); return hipSuccess; }
-hipError_t hipMemset(void* d, int v, size_t n) { memset(d, v, n); return hipSuccess; }
-hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t) { memset(d, v, n); return hipSuccess; }
+hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind k, hipStream_t st) {
+    if (g_level == 2) { Line l("hipMemcpyAsync"); l.kv("kind", kind_text(k)).u("bytes", n).p("dst", d).p("src", s).st(st); }
+    memcpy(d, s, n);
+    return hipSuccess;
+}
+hipError_t hipMemset(void* d, int v, size_t n) {
+    if (g_level == 2) Line("hipMemset").i("value", v).u("bytes", n).p("dst", d);
+    memset(d, v, n);
+    return hipSuccess;
+}
+hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t st) {
+    if (g_level == 2) Line("hipMemsetAsync").i("value", v).u("bytes", n).p("dst", d).st(st);
+    memset(d, v, n);
+    return hipSuccess;
+}
 hipError_t hipSetDevice(int) { return hipSuccess; }
 hipError_t hipGetLastError(void) { return hipSuccess; }
 const char* hipGetErrorString(hipError_t) { return "stub"; }
-hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { *s = reinterpret_cast<hipStream_t>(malloc(8)); ++g_live; return hipSuccess; }
-hipError_t hipStreamDestroy(hipStream_t s) { free(s); --g_live; return hipSuccess; }
+hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { *s = reinterpret_cast<hipStream_t>(malloc(8)); ++g_live; g_streams[*s] = ++g_nstreams; return hipSuccess; }
+hipError_t hipStreamDestroy(hipStream_t s) { g_streams.erase(s); free(s); --g_live; return hipSuccess; }
 hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
-hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) { return hipSuccess; }
-hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { *e = reinterpret_cast<hipEvent_t>(malloc(8)); ++g_live; return hipSuccess; }
-hipError_t hipEventDestroy(hipEvent_t e) { free(e); --g_live; return hipSuccess; }
-hipError_t hipEventRecord(hipEvent_t, hipStream_t) { return hipSuccess; }
+hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned) {
+    if (g_level == 2) Line("hipStreamWaitEvent").kv("event", handle_text(g_events, e)).st(s);
+    return hipSuccess;
+}
+hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { *e = reinterpret_cast<hipEvent_t>(malloc(8)); ++g_live; g_events[*e] = ++g_nevents; return hipSuccess; }
+hipError_t hipEventDestroy(hipEvent_t e) { g_events.erase(e); free(e); --g_live; return hipSuccess; }
+hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) {
+    if (g_level == 2) Line("hipEventRecord").kv("event", handle_text(g_events, e)).st(s);
+    return hipSuccess;
+}
 }
 
 namespace amuse {
-static hipError_t log_sample(const char* name, const SampleArgs& a, int prec) {
+static hipError_t log_sample(const char* name, const SampleArgs& a, int prec, hipStream_t st) {
     if (g_log) printf("%s prec=%d image=%016llx wave_units=%u a=%u b=%u\n", name, prec, image_of(a.wstream), a.wave_units, a.wave_units_a, a.wave_units_b);
+    if (g_level == 2)   // (drop_epoch: the launchers set it themselves)
+        Line(name).i("prec", prec).st(st).w(a.wstream).U_(wave_units).U_(wave_units_a).U_(wave_units_b).P_(pvec).P_(time_tok).P_(time_tok_clip).P_(cond_tok).P_(pe0).P_(coef)
+            .P_(x_init).P_(step_noise).P_(latents_out).P_(traj_out).P_(eps_out).P_(tap_out).U_(seed).U_(clip0).I_(B).I_(T).I_(S).I_(G).I_(no_update).P_(prof_out).I_(prof_step)
+            .U_(drop_thr).f("drop_scale", a.drop_scale).U_(drop_seed);
     return hipSuccess;
 }
-static hipError_t log_rows(const char* name, const VaeRowsArgs& a, int prec, int mode) {
+static void log_drop(Line& l, const VaeDropArgs& a) { l.U_(drop_thr).f("drop_scale", a.drop_scale).U_(drop_seed).U_(drop_clip0); }
+static hipError_t log_rows(const char* name, const VaeRowsArgs& a, int prec, int mode, hipStream_t st) {
     if (g_log)
         printf("%s prec=%d mode=%d stage=%d image=%016llx stage_base=%016llx stage_units=%016llx\n", name, prec, mode, a.stage, image_of(a.wstream),
                (unsigned long long)fnv1a(a.stage_base, sizeof(a.stage_base)), (unsigned long long)fnv1a(a.stage_units, sizeof(a.stage_units)));
+    if (g_level == 2) {
+        Line l(name);
+        l.i("prec", prec).i("mode", mode).st(st).w(a.wstream).x("stage_base", fnv1a(a.stage_base, sizeof(a.stage_base))).x("stage_units", fnv1a(a.stage_units, sizeof(a.stage_units)))
+            .P_(pvec).P_(final_bias).P_(pe).P_(ca).P_(lengths).P_(x).P_(q).P_(k).P_(v).P_(attn_o).P_(skip).P_(feats_out).P_(poses_out).P_(trans_out).I_(B).I_(stage).I_(quat_mode)
+            .I_(tiles).P_(c1).P_(c1_out).P_(enc_feats).P_(tok).P_(emb_bias).P_(stats_out).I_(S).I_(npre).P_(pre_tok_t).U_(pre_tok_t_stride).P_(pre_tok_c)
+            .p("mem.tkv", a.mem.tkv).u("mem.tkv_clip_stride", a.mem.tkv_clip_stride).p("mem.ckv", a.mem.ckv).i("mem.ncond", a.mem.ncond)
+            .P_(coef).P_(x_out).P_(step_noise).U_(seed).U_(clip0).I_(step);
+        if (mode == VAE_MODE_DEC_DROP) {   // the argument is a VaeRowsDropArgs handed over by its base
+            const VaeRowsDropArgs& d = static_cast<const VaeRowsDropArgs&>(a);
+            log_drop(l, d.drop);
+            l.p("ca_bias", d.ca_bias);
+        }
+    }
     return hipSuccess;
 }
 static hipError_t log_stream(const char* name, const void* wstream) {
     if (g_log) printf("%s image=%016llx\n", name, image_of(wstream));
     return hipSuccess;
 }
-hipError_t launch_sample(const SampleArgs& a, int prec, hipStream_t) { return log_sample("launch_sample", a, prec); }
-hipError_t launch_sample8(const SampleArgs& a, hipStream_t) { return log_sample("launch_sample8", a, -1); }
-hipError_t launch_sample8x(const SampleArgs& a, hipStream_t) { return log_sample("launch_sample8x", a, -1); }
-hipError_t launch_sample8h(const SampleArgs& a, hipStream_t) { return log_sample("launch_sample8h", a, -1); }
-hipError_t launch_time_tokens(const int*, int, const float*, const float*, const float*, const float*, const float*, const float*, float*, hipStream_t) { return hipSuccess; }
-hipError_t launch_cond_tokens(const CondArgs&, hipStream_t) { return hipSuccess; }
-hipError_t launch_repack(const float*, const int* map, void* dst, size_t n, int kind, hipStream_t) {   // (the gather map is host memory here)
+static hipError_t log_vae_fused(const char* name, const VaeFusedArgs& a, hipStream_t st) {
+    if (g_level == 2)
+        Line(name).st(st).w(a.wstream).P_(pvec).P_(final_bias).P_(pe).P_(ca).P_(lengths).P_(skip).P_(feats_out).P_(poses_out).P_(trans_out).P_(tap_out).P_(c1).I_(B).I_(quat_mode)
+            .I_(ablate_attention);
+    return log_stream(name, a.wstream);
+}
+static hipError_t log_den_fused(const char* name, const DenFusedArgs& a, hipStream_t st) {
+    if (g_level == 2)
+        Line(name).st(st).w(a.wstream).P_(pvec).P_(final_bias).P_(emb_bias).P_(pe).P_(ttok).U_(ttok_stride).P_(ctok).P_(skip).P_(x).P_(eps_out).P_(coef).P_(step_noise).P_(lengths)
+            .U_(seed).U_(clip0).I_(step).I_(B).I_(npre).I_(ablate_attention);
+    return log_stream(name, a.wstream);
+}
+hipError_t launch_sample(const SampleArgs& a, int prec, hipStream_t st) { return log_sample("launch_sample", a, prec, st); }
+hipError_t launch_sample8(const SampleArgs& a, hipStream_t st) { return log_sample("launch_sample8", a, -1, st); }
+hipError_t launch_sample8x(const SampleArgs& a, hipStream_t st) { return log_sample("launch_sample8x", a, -1, st); }
+hipError_t launch_sample8h(const SampleArgs& a, hipStream_t st) { return log_sample("launch_sample8h", a, -1, st); }
+hipError_t launch_time_tokens(const int* ts, int T, const float* freqs, const float* w1t, const float* b1, const float* w2t, const float* b2, const float* pe1, float* out, hipStream_t st) {
+    if (g_level == 2) Line("launch_time_tokens").st(st).p("timesteps", ts).i("T", T).p("freqs", freqs).p("w1t", w1t).p("b1", b1).p("w2t", w2t).p("b2", b2).p("pe1", pe1).p("out", out);
+    return hipSuccess;
+}
+hipError_t launch_cond_tokens(const CondArgs& a, hipStream_t st) {
+    if (g_level == 2)
+        Line("launch_cond_tokens").st(st).p("z0", a.z[0]).p("z1", a.z[1]).p("z2", a.z[2]).p("wt0", a.wt[0]).p("wt1", a.wt[1]).p("wt2", a.wt[2]).p("bias0", a.bias[0])
+            .p("bias1", a.bias[1]).p("bias2", a.bias[2]).P_(pe).P_(out).I_(B).I_(ncond).I_(pe_base);
+    return hipSuccess;
+}
+hipError_t launch_repack(const float* params, const int* map, void* dst, size_t n, int kind, hipStream_t st) {   // (the gather map is host memory here)
     if (g_log) printf("launch_repack n=%zu kind=%d image=%016llx map=%016llx\n", n, kind, image_of(dst), (unsigned long long)fnv1a(map, n * sizeof(int)));
+    if (g_level == 2) Line("launch_repack").st(st).p("params", params).x("map", fnv1a(map, n * sizeof(int))).p("dst", dst).x("image", image_of(dst)).u("n", n).i("kind", kind);
     return hipSuccess;
 }
-hipError_t launch_add_noise(const float*, const float*, const float*, const float*, float*, int, hipStream_t, int) { return hipSuccess; }
-hipError_t launch_counter_normal(uint64_t, uint64_t, int, int, int, float*, hipStream_t, int) { return hipSuccess; }
-hipError_t launch_vae_rows(const VaeRowsArgs& a, int prec, int mode, hipStream_t) { return log_rows("launch_vae_rows", a, prec, mode); }
-hipError_t launch_vae_rows8x(const VaeRowsArgs& a, hipStream_t, int mode) { return log_rows("launch_vae_rows8x", a, -1, mode); }
-hipError_t launch_vae_attn(const VaeAttnArgs&, int, int, hipStream_t) { return hipSuccess; }
-hipError_t launch_vae_fused(const VaeFusedArgs& a, hipStream_t) { return log_stream("launch_vae_fused", a.wstream); }
-hipError_t launch_vae_fusedh(const VaeFusedArgs& a, hipStream_t) { return log_stream("launch_vae_fusedh", a.wstream); }
-hipError_t launch_den_fused(const DenFusedArgs& a, hipStream_t) { return log_stream("launch_den_fused", a.wstream); }
-hipError_t launch_den_fusedh(const DenFusedArgs& a, hipStream_t) { return log_stream("launch_den_fusedh", a.wstream); }
-hipError_t launch_vae_fusedx(const VaeFusedXArgs& a, hipStream_t) { return log_stream("launch_vae_fusedx", a.wstream); }
-hipError_t launch_den_fusedx(const DenFusedXArgs& a, hipStream_t) { return log_stream("launch_den_fusedx", a.wstream); }
-hipError_t launch_sample_dec(const SampleDecArgs& a, int prec, hipStream_t) {
+hipError_t launch_add_noise(const float* z0, const float* noise, const float* sa, const float* sb, float* out, int B, hipStream_t st, int nfeat) {
+    if (g_level == 2) Line("launch_add_noise").st(st).p("z0", z0).p("noise", noise).p("sa", sa).p("sb", sb).p("out", out).i("B", B).i("nfeat", nfeat);
+    return hipSuccess;
+}
+hipError_t launch_counter_normal(uint64_t seed, uint64_t clip0, int B, int step, int rng_stream, float* out, hipStream_t st, int nfeat) {
+    if (g_level == 2) Line("launch_counter_normal").st(st).u("seed", seed).u("clip0", clip0).i("B", B).i("step", step).i("rng_stream", rng_stream).p("out", out).i("nfeat", nfeat);
+    return hipSuccess;
+}
+hipError_t launch_vae_rows(const VaeRowsArgs& a, int prec, int mode, hipStream_t st) { return log_rows("launch_vae_rows", a, prec, mode, st); }
+hipError_t launch_vae_rows8x(const VaeRowsArgs& a, hipStream_t st, int mode) { return log_rows("launch_vae_rows8x", a, -1, mode, st); }
+hipError_t launch_vae_attn(const VaeAttnArgs& a, int prec, int mode, hipStream_t st) {
+    if (g_level == 2) {
+        Line l("launch_vae_attn");
+        l.i("prec", prec).i("mode", mode).st(st).P_(q).P_(k).P_(v).P_(lengths).P_(o).I_(B).I_(q_tiles).I_(S);
+        if (mode == VAE_MODE_DEC_DROP) {   // the argument is a VaeAttnDropArgs handed over by its base
+            const VaeAttnDropArgs& d = static_cast<const VaeAttnDropArgs&>(a);
+            l.i("layer", d.layer);
+            log_drop(l, d.drop);
+        }
+    }
+    return hipSuccess;
+}
+hipError_t launch_vae_fused(const VaeFusedArgs& a, hipStream_t st) { return log_vae_fused("launch_vae_fused", a, st); }
+hipError_t launch_vae_fusedh(const VaeFusedArgs& a, hipStream_t st) { return log_vae_fused("launch_vae_fusedh", a, st); }
+hipError_t launch_den_fused(const DenFusedArgs& a, hipStream_t st) { return log_den_fused("launch_den_fused", a, st); }
+hipError_t launch_den_fusedh(const DenFusedArgs& a, hipStream_t st) { return log_den_fused("launch_den_fusedh", a, st); }
+hipError_t launch_vae_fusedx(const VaeFusedXArgs& a, hipStream_t st) {
+    if (g_level == 2)
+        Line("launch_vae_fusedx").st(st).w(a.wstream).P_(pvec).P_(final_bias).P_(pe).P_(ca).P_(lengths).P_(skip).P_(obuf).P_(feats_out).P_(poses_out).P_(trans_out).P_(tap_out)
+            .P_(c1).P_(c1_out).I_(B).I_(quat_mode);
+    return log_stream("launch_vae_fusedx", a.wstream);
+}
+hipError_t launch_den_fusedx(const DenFusedXArgs& a, hipStream_t st) {
+    if (g_level == 2)
+        Line("launch_den_fusedx").st(st).w(a.wstream).P_(pvec).P_(emb_bias).P_(final_bias).P_(pe).P_(ttok).U_(ttok_stride).P_(ctok).P_(x_in).P_(x_out).P_(eps_out).P_(coef)
+            .P_(step_noise).P_(lengths).P_(obuf).P_(skip).U_(seed).U_(clip0).I_(step).I_(B).I_(S).I_(npre).I_(encode);
+    return log_stream("launch_den_fusedx", a.wstream);
+}
+hipError_t launch_sample_dec(const SampleDecArgs& a, int prec, hipStream_t st) {
     if (g_log) printf("launch_sample_dec prec=%d image=%016llx wave_units=%u\n", prec, image_of(a.wstream), a.wave_units);
+    if (g_level == 2)
+        Line("launch_sample_dec").i("prec", prec).st(st).w(a.wstream).U_(wave_units).P_(pvec).P_(pe0).p("mem.tkv", a.mem.tkv).u("mem.tkv_clip_stride", a.mem.tkv_clip_stride)
+            .p("mem.ckv", a.mem.ckv).i("mem.ncond", a.mem.ncond).U_(tkv_step_stride).P_(coef).P_(x_init).P_(step_noise).P_(latents_out).P_(traj_out).P_(eps_out).P_(tap_out)
+            .U_(seed).U_(clip0).I_(B).I_(T).I_(no_update);
     return hipSuccess;
 }
-hipError_t launch_mem_kv(const float*, int, const float*, const float*, float*, hipStream_t) { return hipSuccess; }
-hipError_t launch_feats_to_smplx(const float*, size_t, int, float*, float*, hipStream_t) { return hipSuccess; }
-hipError_t launch_smplx_to_feats(const float*, const float*, size_t, float*, hipStream_t) { return hipSuccess; }
-hipError_t launch_vae_latent(const float*, const float*, float*, float*, float*, int, hipStream_t) { return hipSuccess; }
-hipError_t launch_vae_ca(const float*, const float*, const float*, const float*, const float*, float*, int, hipStream_t) { return hipSuccess; }
+hipError_t launch_mem_kv(const float* tok, int N, const float* wkv_t, const float* bkv, float* kv, hipStream_t st) {
+    if (g_level == 2) Line("launch_mem_kv").st(st).p("tok", tok).i("N", N).p("wkv_t", wkv_t).p("bkv", bkv).p("kv", kv);
+    return hipSuccess;
+}
+hipError_t launch_feats_to_smplx(const float* feats, size_t nrows, int quat_mode, float* poses, float* trans, hipStream_t st) {
+    if (g_level == 2) Line("launch_feats_to_smplx").st(st).p("feats", feats).u("nrows", nrows).i("quat_mode", quat_mode).p("poses", poses).p("trans", trans);
+    return hipSuccess;
+}
+hipError_t launch_smplx_to_feats(const float* poses, const float* trans, size_t nrows, float* feats, hipStream_t st) {
+    if (g_level == 2) Line("launch_smplx_to_feats").st(st).p("poses", poses).p("trans", trans).u("nrows", nrows).p("feats", feats);
+    return hipSuccess;
+}
+hipError_t launch_vae_latent(const float* stats, const float* eps, float* mu, float* std, float* latent, int B, hipStream_t st) {
+    if (g_level == 2) Line("launch_vae_latent").st(st).p("stats", stats).p("eps", eps).p("mu", mu).p("std", std).p("latent", latent).i("B", B);
+    return hipSuccess;
+}
+hipError_t launch_vae_ca(const float* z, const float* wv_t, const float* bv, const float* wo_t, const float* bo, float* ca, int B, hipStream_t st) {
+    if (g_level == 2) Line("launch_vae_ca").st(st).p("z", z).p("wv_t", wv_t).p("bv", bv).p("wo_t", wo_t).p("bo", bo).p("ca", ca).i("B", B);
+    return hipSuccess;
+}
 hipError_t launch_gemm(const GemmArgs&, int, hipStream_t) { return hipSuccess; }
 hipError_t launch_fbank(const float*, int, int, const float*, const float*, const int*, float, float, float*, hipStream_t) { return hipSuccess; }
 hipError_t launch_im2col(const float*, unsigned short*, int, hipStream_t) { return hipSuccess; }
@@ -120,3 +302,6 @@ hipError_t launch_ast_attn(const unsigned short*, const unsigned short*, unsigne
 hipError_t launch_ast_pool(const float*, const float*, const float*, int, float*, int, hipStream_t) { return hipSuccess; }
 hipError_t launch_ast_head(const float*, int, const float*, const float*, const unsigned short*, const float*, float*, int, hipStream_t) { return hipSuccess; }
 }  // namespace amuse
+// a second stream for drivers that do not include the HIP headers (tests/host_asan/launch_args.cpp)
+void* amuse_stub_stream_create() { hipStream_t s = nullptr; (void)hipStreamCreateWithFlags(&s, 0); return s; }
+void amuse_stub_stream_destroy(void* s) { (void)hipStreamDestroy(static_cast<hipStream_t>(s)); }

@@ -25,6 +25,7 @@ EXPORTS = [
     "amuse_counter_normal", "amuse_set_clips_per_group", "amuse_set_decode_path", "amuse_plan", "amuse_debug_last_plan", "amuse_profile_sample",
     "amuse_audio_create", "amuse_audio_destroy", "amuse_audio_fbank", "amuse_audio_encode", "amuse_audio_features",
     "amuse_audio_set_precision", "amuse_audio_precision",
+    "amuse_audio_set_tail", "amuse_audio_encode_labels", "amuse_audio_reconstruct", "amuse_debug_tail_hidden", "amuse_debug_tail_pack", "amuse_debug_tail_gemm",
     "amuse_debug_gemm",
     "amuse_debug_tile", "amuse_debug_f16_split", "amuse_debug_set_decode_tap",
     "amuse_create_arch", "amuse_denoiser_param_count", "amuse_arch", "amuse_state_dim", "amuse_denoise_step_pose", "amuse_feats_to_smplx",
@@ -136,6 +137,14 @@ def load() -> C.CDLL:
     lib.amuse_audio_set_precision.argtypes = [vp, C.c_int]
     lib.amuse_audio_precision.argtypes = [vp]
     lib.amuse_audio_set_precision.restype = lib.amuse_audio_precision.restype = C.c_int
+    lib.amuse_audio_set_tail.argtypes = [vp, fp, C.c_size_t]
+    lib.amuse_audio_encode_labels.argtypes = [vp, C.c_int, C.c_int, fp, C.c_int, fp, fp, vp]
+    lib.amuse_audio_reconstruct.argtypes = [vp, fp, fp, fp, C.c_int, C.c_int, fp, vp]
+    lib.amuse_debug_tail_hidden.argtypes = [vp, fp, fp, fp, C.c_int, C.c_int, fp, vp]
+    lib.amuse_debug_tail_pack.argtypes = [fp, C.c_int, C.c_int, C.c_int, vp]
+    lib.amuse_debug_tail_gemm.argtypes = [fp, vp, fp, C.c_int, C.c_int, C.c_int, C.c_int, fp, vp]
+    for n in ("amuse_audio_set_tail", "amuse_audio_encode_labels", "amuse_audio_reconstruct", "amuse_debug_tail_hidden", "amuse_debug_tail_pack", "amuse_debug_tail_gemm"):
+        getattr(lib, n).restype = C.c_int
     lib.amuse_debug_gemm.argtypes = [vp, vp, fp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
     lib.amuse_debug_tile.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp]
     lib.amuse_debug_f16_split.argtypes = [C.POINTER(C.c_float), C.c_size_t, C.POINTER(C.c_uint16), C.POINTER(C.c_uint16)]

@@ -43,8 +43,10 @@ class AudioEngine:
 
     def __init__(self, con_sd: Dict[str, np.ndarray], emo_sd: Dict[str, np.ndarray], sty_sd: Dict[str, np.ndarray],
                  device="cuda:0", norm_mean: float = NORM_MEAN, norm_std: float = NORM_STD, frame_based_feats: bool = True,
-                 precision: str = "bf16"):
+                 precision: str = "bf16", tail_sd: Optional[Dict[str, np.ndarray]] = None):
         self.lib = _lib.load()
+        self.frame_based_feats = bool(frame_based_feats)
+        self.has_tail = False
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise _lib.AmuseHipError("amuse_amd runs on an MI355X (torch device 'cuda:N'); there is no CPU path")
@@ -60,6 +62,16 @@ class AudioEngine:
             raise _lib.AmuseHipError(f"amuse_audio_create failed: {self.lib.amuse_last_error().decode()}")
         if precision != "bf16":
             self.set_precision(precision)
+        if tail_sd is not None:
+            self.set_tail(tail_sd)
+
+    def set_tail(self, tail_sd: Dict[str, np.ndarray]) -> None:
+        """Upload AST_EVP's classifier heads, fusion and decoder (audio_weights.ast_tail_param_spec; amuse_audio_set_tail): enables encode_labels'
+        labels, reconstruct and metrics."""
+        flat = flatten_state_dict(tail_sd, aw.ast_tail_param_spec())
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.amuse_audio_set_tail(self.ctx, flat.ctypes.data_as(C.c_void_p), flat.size))
+        self.has_tail = True
 
     def set_precision(self, precision: str) -> None:
         """"bf16" | "fp32x" (amuse_audio_set_precision): governs encode / features / features_ragged / process_single_seq; fbank is fp32 in both.
@@ -117,6 +129,66 @@ class AudioEngine:
             _lib.check(self.lib.amuse_audio_encode(self.ctx, WHICH[which], _ptr(fb), B, _ptr(feat), _ptr(hid),
                                                    0 if tap_block is None else int(tap_block), self._stream()))
         return feat if tap_block is None else (feat, hid)
+
+    def _fbanks(self, fbank) -> torch.Tensor:
+        fb = torch.as_tensor(fbank).to(device=self.device, dtype=torch.float32).contiguous()
+        if fb.dim() == 2:
+            fb = fb[None]
+        if fb.dim() != 3 or tuple(fb.shape[1:]) != (1024, 128):
+            raise ValueError(f"fbank must be (B, 1024, 128), got {tuple(fb.shape)}")
+        return fb
+
+    def encode_labels(self, which: str, fbank, frame_based: Optional[bool] = None):
+        """ASTModel.forward(fbank, frame_based_feats) of encoder 'con' | 'emo' | 'sty' (audio_main_new.py:174-204): -> (feature (B, 256), predicted_labels
+        (B, 8) for 'emo', (B, 30) for 'sty', None for 'con', whose label_dim is 0).  frame_based None = the engine's flag."""
+        fb = self._fbanks(fbank)
+        B = fb.shape[0]
+        feat = torch.empty(B, 256, device=self.device, dtype=torch.float32)
+        logits = None if which == "con" else torch.empty(B, aw.TAIL_LABELS[which], device=self.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.amuse_audio_encode_labels(self.ctx, WHICH[which], -1 if frame_based is None else int(bool(frame_based)), _ptr(fb), B,
+                                                          _ptr(feat), _ptr(logits), self._stream()))
+        return feat, logits
+
+    def reconstruct(self, con, emo, sty, group: int = 1) -> torch.Tensor:
+        """AST_EVP.reconstruct(cat(emo, sty, con), reconstruct_only=True) (AST_EVP.py:70-82): three (B, 256) embeddings -> (B, 1024, 128) fbanks.  The
+        reference's layers see the batch as one sequence; `group` rows in a row form such a sequence here (group = B: the reference's call, group = 1: a clip
+        on its own, as collect_audio_metrics runs it)."""
+        ts = [torch.as_tensor(t).to(device=self.device, dtype=torch.float32).contiguous() for t in (con, emo, sty)]
+        ts = [t[None] if t.dim() == 1 else t for t in ts]
+        B = ts[0].shape[0]
+        if any(tuple(t.shape) != (B, 256) for t in ts):
+            raise ValueError(f"con / emo / sty must each be (B, 256), got {[tuple(t.shape) for t in ts]}")
+        out = torch.empty(B, 1024, 128, device=self.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.amuse_audio_reconstruct(self.ctx, _ptr(ts[0]), _ptr(ts[1]), _ptr(ts[2]), B, int(group), _ptr(out), self._stream()))
+        return out
+
+    def _tail_hidden(self, con, emo, sty, group: int = 1) -> torch.Tensor:
+        """reconstruct up to the last Linear's input, (B, 1024) fp32 (amuse_debug_tail_hidden; tests)"""
+        ts = [torch.as_tensor(t).to(device=self.device, dtype=torch.float32).contiguous() for t in (con, emo, sty)]
+        B = ts[0].shape[0]
+        out = torch.empty(B, 1024, device=self.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.amuse_debug_tail_hidden(self.ctx, _ptr(ts[0]), _ptr(ts[1]), _ptr(ts[2]), B, int(group), _ptr(out), self._stream()))
+        return out
+
+    def metrics(self, fbank) -> dict:
+        """AST_EVP.eval_func(fbank, frame_based_feats, metrics=True) (AST_EVP.py:91-103) for ONE clip, (1, 1024, 128) or (1024, 128): the first pass is
+        frame-based whatever the engine's flag (hard-coded at AST_EVP.py:93), the reconstruction is encoded again as it is, with the engine's flag.
+        -> {"fbanks" (1024, 128), "emo" / "sty" / "con" and "new_emo" / "new_sty" / "new_con": {"feature" (256,), "predicted_labels" (1, L) | None}}."""
+        fb = self._fbanks(fbank)
+        if fb.shape[0] != 1:
+            raise ValueError("metrics takes one clip, as collect_audio_metrics does (the reference squeezes the batch dimension)")
+        first = {w: self.encode_labels(w, fb, True) for w in ("emo", "sty", "con")}
+        fbanks = self.reconstruct(first["con"][0], first["emo"][0], first["sty"][0], group=1)
+        second = {w: self.encode_labels(w, fbanks, self.frame_based_feats) for w in ("emo", "sty", "con")}
+        out = {"fbanks": fbanks[0]}
+        for w in ("emo", "sty", "con"):
+            out[w] = {"feature": first[w][0][0], "predicted_labels": first[w][1]}
+        for w in ("emo", "sty", "con"):
+            out[f"new_{w}"] = {"feature": second[w][0][0], "predicted_labels": second[w][1]}
+        return out
 
     def features(self, waves):
         """-> (con, emo, sty), each (B, 256): process_single_seq for a batch of waveforms."""

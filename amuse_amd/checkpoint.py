@@ -19,7 +19,7 @@ from __future__ import annotations
 
 import re
 from pathlib import Path
-from typing import Dict, Tuple, Union
+from typing import Dict, Optional, Tuple, Union
 
 import numpy as np
 import torch
@@ -126,12 +126,27 @@ def load_ast_checkpoint(path: Path) -> Dict[str, Dict[str, np.ndarray]]:
     return out
 
 
+def load_ast_tail(path: Path):
+    """-> the tensors of audio_weights.ast_tail_param_spec (classifier heads, fusion, decode) from the file load_ast_checkpoint reads, or None when
+    the file holds none of them (an encoders-only checkpoint: the front-end then works without reconstruct / labels).  A file with SOME of them is an error."""
+    sd = torch.load(path, map_location="cpu", weights_only=False)
+    spec = aw.ast_tail_param_spec()
+    missing = [k for k in spec if k not in sd]
+    if len(missing) == len(spec):
+        return None
+    if missing:
+        raise KeyError(f"AST checkpoint misses {len(missing)} keys of the fusion / decoder / classifier tail, e.g. {missing[:3]}")
+    return {k: sd[k].detach().cpu().numpy().astype(np.float32) for k in spec}
+
+
 def save_ast_reference_format(model_dir: Path, sds: Dict[str, Dict[str, np.ndarray]], epoch: int = 12, emo_acc: float = 0.91,
-                              person_acc: float = 0.88) -> Path:
-    """Write an AST_EVP state dict in the reference's on-disk form (tests / demos)."""
+                              person_acc: float = 0.88, tail: Optional[Dict[str, np.ndarray]] = None) -> Path:
+    """Write an AST_EVP state dict in the reference's on-disk form (tests / demos); `tail` adds the entries of audio_weights.ast_tail_param_spec."""
     model_dir = Path(model_dir)
     model_dir.mkdir(parents=True, exist_ok=True)
     path = model_dir / f"model_e{epoch}_loss0.1234_tEAcc{emo_acc:.4f}_tPAcc{person_acc:.4f}.pt"
     flat = {f"{enc}_enc.{k}": torch.from_numpy(np.asarray(v)) for enc, sd in sds.items() for k, v in sd.items()}
+    if tail is not None:
+        flat.update({k: torch.from_numpy(np.array(v, dtype=np.float32)) for k, v in tail.items()})
     torch.save(flat, path)
     return path

@@ -8,6 +8,7 @@
 
 #include "../../include/amuse_hip.h"
 #include "amuse_audio.hpp"
+#include "amuse_audio_tail.hpp"
 #include "amuse_audio_x.hpp"
 
 using namespace amuse;
@@ -16,6 +17,9 @@ int amuse_fail_msg(int code, const char* msg);   // amuse_api.hip: the library's
 // The parity mode (AMUSE_PREC_F32X) lives in amuse_audio_x.hip and is reached through this WEAK reference only: where that unit is not linked (the host-only
 // build of tests/host_asan, whose stub defines the bf16 launchers alone) the address is null and amuse_audio_set_precision refuses the mode.
 extern "C" const amuse::AudioXOps* amuse_audio_x_ops(void) __attribute__((weak));
+// AST_EVP's tail (classifier heads, fusion, decoder: amuse_audio_tail.hip) is reached the same way: without that unit amuse_audio_set_tail, amuse_audio_reconstruct
+// and the labels of amuse_audio_encode_labels return AMUSE_ESTATE.
+extern "C" const amuse::AudioTailOps* amuse_audio_tail_ops(void) __attribute__((weak));
 
 namespace {
 
@@ -78,6 +82,10 @@ struct amuse_audio_ctx {
     int precision = AMUSE_PREC_BF16;
     void* xstate = nullptr;
     std::vector<float> host_params[3];
+    // amuse_audio_set_tail: the tail's state (amuse_audio_tail.hip) and the second pooling buffer of amuse_audio_encode_labels ((cls + dist) row sums of a chunk)
+    void* tail = nullptr;
+    float* pooled2 = nullptr;
+    int pooled2_cap = 0;
 };
 
 namespace {
@@ -194,7 +202,7 @@ int ensure_side_streams(amuse_audio_ctx* c) {
 }
 
 // one encoder over nb <= cap clips whose fbanks are at `fbank`
-int run_encoder(const amuse_audio_ctx* c, const Workspace& w, const Encoder& E, const float* fbank, int nb, float* feat_out,
+int run_encoder(const Workspace& w, const Encoder& E, int frame_based, const float* fbank, int nb, float* feat_out,
                 float* hidden_out, int tap_block, hipStream_t st) {
     const int M = nb * kAstRows;   // a clip owns 1216 rows: 1214 tokens + 2 pad rows
     HIP_TRY(launch_im2col(fbank, w.P, nb, st));
@@ -223,8 +231,8 @@ int run_encoder(const amuse_audio_ctx* c, const Workspace& w, const Encoder& E, 
         if (hidden_out && l == tap_block)
             HIP_TRY(launch_untile_f32(w.X, hidden_out, M, kAstDim, kAstRows, kAstTokens, st));
     }
-    HIP_TRY(launch_ast_pool(w.X, E.norm_w, E.norm_b, c->frame_based, w.pooled, nb, st));
-    HIP_TRY(launch_ast_head(w.pooled, c->frame_based, E.fh_ln_w, E.fh_ln_b, E.fh_w, E.fh_b, feat_out, nb, st));
+    HIP_TRY(launch_ast_pool(w.X, E.norm_w, E.norm_b, frame_based, w.pooled, nb, st));
+    HIP_TRY(launch_ast_head(w.pooled, frame_based, E.fh_ln_w, E.fh_ln_b, E.fh_w, E.fh_b, feat_out, nb, st));
     return 0;
 }
 
@@ -233,11 +241,26 @@ int mode_ensure_ws(amuse_audio_ctx* c, int slot, int nb) {
     if (c->precision == AMUSE_PREC_F32X) return amuse_audio_x_ops()->ensure_ws(c->xstate, slot, nb);
     return ensure_ws(c->ws[slot], nb);
 }
-int mode_run_encoder(const amuse_audio_ctx* c, int slot, int which, const float* fbank, int nb, float* feat_out, float* hidden_out, int tap_block,
+int mode_run_encoder(const amuse_audio_ctx* c, int slot, int which, int frame_based, const float* fbank, int nb, float* feat_out, float* hidden_out, int tap_block,
                      hipStream_t st) {
     if (c->precision == AMUSE_PREC_F32X)
-        return amuse_audio_x_ops()->run_encoder(c->xstate, slot, which, c->frame_based, fbank, nb, feat_out, hidden_out, tap_block, st);
-    return run_encoder(c, c->ws[slot], c->enc[which], fbank, nb, feat_out, hidden_out, tap_block, st);
+        return amuse_audio_x_ops()->run_encoder(c->xstate, slot, which, frame_based, fbank, nb, feat_out, hidden_out, tap_block, st);
+    return run_encoder(c->ws[slot], c->enc[which], frame_based, fbank, nb, feat_out, hidden_out, tap_block, st);
+}
+// the OTHER pooling of the residual stream the last mode_run_encoder left in workspace `slot`: v.norm, then the (cls + dist) row sums (k_ast_pool, frame_based 0)
+int mode_pool_cls(const amuse_audio_ctx* c, int slot, int which, float* pooled, int nb, hipStream_t st) {
+    if (c->precision == AMUSE_PREC_F32X) return amuse_audio_x_ops()->pool(c->xstate, slot, which, 0, pooled, nb, st);
+    const Encoder& E = c->enc[which];
+    HIP_TRY(launch_ast_pool(c->ws[slot].X, E.norm_w, E.norm_b, 0, pooled, nb, st));
+    return 0;
+}
+int ensure_pooled2(amuse_audio_ctx* c, int nb) {
+    if (c->pooled2_cap >= nb) return 0;
+    if (c->pooled2) HIP_TRY(hipFree(c->pooled2));
+    c->pooled2 = nullptr; c->pooled2_cap = 0;
+    HIP_TRY(hipMalloc((void**)&c->pooled2, (size_t)nb * kAstPoolSplit * kAstDim * 4));
+    c->pooled2_cap = nb;
+    return 0;
 }
 
 }  // namespace
@@ -305,6 +328,8 @@ void amuse_audio_destroy(amuse_audio_ctx* c) {
     for (void* p : c->owned) (void)hipFree(p);
     for (Workspace& w : c->ws) free_ws(w);
     if (c->xstate) amuse_audio_x_ops()->destroy(c->xstate);
+    if (c->tail) amuse_audio_tail_ops()->destroy(c->tail);
+    if (c->pooled2) (void)hipFree(c->pooled2);
     if (c->fbank) (void)hipFree(c->fbank);
     for (int i = 0; i < 2; ++i) {
         if (c->side[i]) (void)hipStreamDestroy(c->side[i]);
@@ -333,7 +358,7 @@ int amuse_audio_encode(amuse_audio_ctx* c, int which, const float* fbank, int B,
     if (int e = mode_ensure_ws(c, 0, chunk)) return e;
     for (int b0 = 0; b0 < B; b0 += chunk) {
         const int nb = (B - b0) < chunk ? (B - b0) : chunk;
-        if (int e = mode_run_encoder(c, 0, which, fbank + (size_t)b0 * kAstFrames * kAstMel, nb, feat_out + (size_t)b0 * kAstFeat,
+        if (int e = mode_run_encoder(c, 0, which, c->frame_based, fbank + (size_t)b0 * kAstFrames * kAstMel, nb, feat_out + (size_t)b0 * kAstFeat,
                                 hidden_out ? hidden_out + (size_t)b0 * kAstTokens * kAstDim : nullptr, tap_block, (hipStream_t)stream))
             return e;
     }
@@ -362,15 +387,76 @@ int amuse_audio_features(amuse_audio_ctx* c, const float* waves, int n_samples, 
         for (int e = 1; e < 3; ++e) {
             if (!outs[e]) continue;
             HIP_TRY(hipStreamWaitEvent(c->side[e - 1], c->ev_fork, 0));
-            if (int rc = mode_run_encoder(c, e, e, c->fbank, nb, outs[e] + (size_t)b0 * kAstFeat, nullptr, 0, c->side[e - 1])) return rc;
+            if (int rc = mode_run_encoder(c, e, e, c->frame_based, c->fbank, nb, outs[e] + (size_t)b0 * kAstFeat, nullptr, 0, c->side[e - 1])) return rc;
             HIP_TRY(hipEventRecord(c->ev_join[e - 1], c->side[e - 1]));
         }
         if (outs[0])
-            if (int rc = mode_run_encoder(c, 0, 0, c->fbank, nb, outs[0] + (size_t)b0 * kAstFeat, nullptr, 0, st)) return rc;
+            if (int rc = mode_run_encoder(c, 0, 0, c->frame_based, c->fbank, nb, outs[0] + (size_t)b0 * kAstFeat, nullptr, 0, st)) return rc;
         for (int e = 1; e < 3; ++e)
             if (outs[e]) HIP_TRY(hipStreamWaitEvent(st, c->ev_join[e - 1], 0));   // (also: the next chunk's fbank overwrites c->fbank)
     }
     return 0;
+}
+
+int amuse_audio_set_tail(amuse_audio_ctx* c, const float* tail_params, size_t n) {
+    if (!c || !tail_params) return failf(AMUSE_EINVAL, "NULL argument%s");
+    if (n != AMUSE_AST_TAIL_PARAMS) return failf(AMUSE_EINVAL, "%stail parameter count mismatch: %ld (want %ld)", "", (long)n, (long)AMUSE_AST_TAIL_PARAMS);
+    if (!amuse_audio_tail_ops) return failf(AMUSE_ESTATE, "the audio model's tail (amuse_audio_tail) is not linked into this build%s");
+    HIP_TRY(hipSetDevice(c->device));
+    void* fresh = nullptr;
+    if (int e = amuse_audio_tail_ops()->create(&fresh, tail_params)) return e;
+    if (c->tail) amuse_audio_tail_ops()->destroy(c->tail);
+    c->tail = fresh;
+    return 0;
+}
+
+int amuse_audio_encode_labels(amuse_audio_ctx* c, int which, int frame_based, const float* fbank, int B, float* feat_out, float* logits_out, void* stream) {
+    if (!c || !fbank || !feat_out) return failf(AMUSE_EINVAL, "NULL argument%s");
+    if (which < 0 || which > 2) return failf(AMUSE_EINVAL, "%sencoder index %ld not in 0..2", "", which);
+    if (B < 1) return failf(AMUSE_EINVAL, "%sB must be >= 1, got %ld", "", B);
+    if (logits_out && which == AMUSE_AUDIO_CON) return failf(AMUSE_EINVAL, "the content encoder has no classifier head (label_dim 0): logits_out must be NULL%s");
+    if (logits_out && !amuse_audio_tail_ops) return failf(AMUSE_ESTATE, "the audio model's tail (amuse_audio_tail) is not linked into this build%s");
+    if (logits_out && !c->tail) return failf(AMUSE_ESTATE, "no tail set: call amuse_audio_set_tail before asking for labels%s");
+    const int fb = frame_based < 0 ? c->frame_based : (frame_based ? 1 : 0);
+    const int L = which == AMUSE_AUDIO_EMO ? kTailLabelsEmo : kTailLabelsSty;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)stream;
+    const int chunk = B < kChunk ? B : kChunk;
+    if (int e = mode_ensure_ws(c, 0, chunk)) return e;
+    if (logits_out && fb)
+        if (int e = ensure_pooled2(c, chunk)) return e;
+    for (int b0 = 0; b0 < B; b0 += chunk) {
+        const int nb = (B - b0) < chunk ? (B - b0) : chunk;
+        float* feat = feat_out + (size_t)b0 * kAstFeat;
+        if (int e = mode_run_encoder(c, 0, which, fb, fbank + (size_t)b0 * kAstFrames * kAstMel, nb, feat, nullptr, 0, st)) return e;
+        if (!logits_out) continue;
+        // frame-based: the labels come from (cls + dist) / 2 of the final norm - the pooling the features did NOT take: a second launch_ast_pool into a second buffer
+        if (fb)
+            if (int e = mode_pool_cls(c, 0, which, c->pooled2, nb, st)) return e;
+        if (int e = amuse_audio_tail_ops()->labels(c->tail, which, fb, fb ? c->pooled2 : feat, nb, logits_out + (size_t)b0 * L, st)) return e;
+    }
+    return 0;
+}
+
+namespace {
+int reconstruct_checked(amuse_audio_ctx* c, const float* con, const float* emo, const float* sty, int B, int group, float* fbank_out, float* hidden_out, void* stream) {
+    if (!c || !con || !emo || !sty || (!fbank_out && !hidden_out)) return failf(AMUSE_EINVAL, "NULL argument%s");
+    if (B < 1 || group < 1 || group > kTailMaxGroup || B % group)
+        return failf(AMUSE_EINVAL, "%sgroup must be in 1..16 and divide B (B %ld, group %ld)", "", B, group);
+    if (!amuse_audio_tail_ops) return failf(AMUSE_ESTATE, "the audio model's tail (amuse_audio_tail) is not linked into this build%s");
+    if (!c->tail) return failf(AMUSE_ESTATE, "no tail set: call amuse_audio_set_tail first%s");
+    HIP_TRY(hipSetDevice(c->device));
+    return amuse_audio_tail_ops()->reconstruct(c->tail, c->precision, con, emo, sty, B, group, fbank_out, hidden_out, (hipStream_t)stream);
+}
+}  // namespace
+
+int amuse_audio_reconstruct(amuse_audio_ctx* c, const float* con, const float* emo, const float* sty, int B, int group, float* fbank_out, void* stream) {
+    if (!fbank_out) return failf(AMUSE_EINVAL, "NULL argument%s");
+    return reconstruct_checked(c, con, emo, sty, B, group, fbank_out, nullptr, stream);
+}
+int amuse_debug_tail_hidden(amuse_audio_ctx* c, const float* con, const float* emo, const float* sty, int B, int group, float* hidden_out, void* stream) {
+    if (!hidden_out) return failf(AMUSE_EINVAL, "NULL argument%s");
+    return reconstruct_checked(c, con, emo, sty, B, group, nullptr, hidden_out, stream);
 }
 
 int amuse_audio_set_precision(amuse_audio_ctx* c, int precision) {

@@ -188,6 +188,14 @@ int x_run_encoder(void* state, int slot, int which, int frame_based, const float
     return 0;
 }
 
+int x_pool(void* state, int slot, int which, int frame_based, float* pooled, int nb, hipStream_t st) {
+    StateX* c = static_cast<StateX*>(state);
+    const WorkspaceX& w = c->ws[slot];
+    if (nb < 1 || nb > w.cap) return failf(AMUSE_ESTATE, "audio fp32x: workspace holds %s%ld clips", "", w.cap);
+    HIP_TRY(launch_ast_pool(w.X, c->enc[which].norm_w, c->enc[which].norm_b, frame_based, pooled, nb, st));
+    return 0;
+}
+
 void x_destroy(void* state) {
     StateX* c = static_cast<StateX*>(state);
     if (!c) return;
@@ -206,7 +214,7 @@ int x_create(void** state, const float* const params[3]) {
     return 0;
 }
 
-const AudioXOps kOps = {x_create, x_destroy, x_ensure_ws, x_run_encoder};
+const AudioXOps kOps = {x_create, x_destroy, x_ensure_ws, x_run_encoder, x_pool};
 
 }  // namespace
 

@@ -48,6 +48,9 @@ struct AudioXOps {
     // one encoder over nb <= capacity clips whose fbanks are at `fbank` (the contract of amuse_audio_api.hip run_encoder)
     int (*run_encoder)(void* state, int slot, int which, int frame_based, const float* fbank, int nb, float* feat_out, float* hidden_out, int tap_block,
                        hipStream_t st);
+    // v.norm + k_ast_pool with the given pooling over the residual stream the last run_encoder left in workspace `slot`, into `pooled` [nb][kAstPoolSplit][768]
+    // (amuse_audio_encode_labels: the labels' pooling where it differs from the features')
+    int (*pool)(void* state, int slot, int which, int frame_based, float* pooled, int nb, hipStream_t st);
 };
 
 }  // namespace amuse

@@ -17,6 +17,7 @@ What is mirrored                                   reference
 from __future__ import annotations
 
 import json
+import pickle
 from pathlib import Path
 from typing import Callable, Dict, Optional
 
@@ -131,16 +132,18 @@ class PretrainedLPDM_v1:
             sds = ckpt.load_ast_checkpoint(best)
             self.set_audio_encoders(sds["con"], sds["emo"], sds["sty"], wd.get("dataset_mean", -9.173025),
                                     wd.get("dataset_std", 5.062332), wd.get("frame_based_feats", True),
-                                    precision=wd.get("audio_precision", "bf16"))   # (this path's own key; amuse_amd.main --audio-precision sets it)
+                                    precision=wd.get("audio_precision", "bf16"),   # (this path's own key; amuse_amd.main --audio-precision sets it)
+                                    tail_sd=ckpt.load_ast_tail(best))             # fusion / decoder / classifier heads, when the file has them
         elif self.audio_encoder is None:
             raise FileNotFoundError(f"[LATDIFF] AST checkpoint directory {ast_dir} not found (TRAIN_PARAM.{tag}.pretrained_ast); "
                                     f"construct PretrainedLPDM_v1(audio_encoder=...) to run from precomputed embeddings")
         return ldm_epoch
 
-    def set_audio_encoders(self, con_sd, emo_sd, sty_sd, norm_mean=-9.173025, norm_std=5.062332, frame_based_feats=True, precision="bf16"):
+    def set_audio_encoders(self, con_sd, emo_sd, sty_sd, norm_mean=-9.173025, norm_std=5.062332, frame_based_feats=True, precision="bf16", tail_sd=None):
         """Build the HIP audio front-end from three ASTModel state dicts (AST_EVP.{con,emo,sty}_enc).  precision: "bf16" (throughput arithmetic) or
-        "fp32x" (the parity mode: embeddings within 1e-5 of the fp32 oracle's, AudioEngine.set_precision)."""
-        self.audio_engine = AudioEngine(con_sd, emo_sd, sty_sd, self.device, norm_mean, norm_std, frame_based_feats, precision=precision)
+        "fp32x" (the parity mode: embeddings within 1e-5 of the fp32 oracle's, AudioEngine.set_precision).  tail_sd: AST_EVP's fusion / decoder /
+        classifier heads (audio_weights.ast_tail_param_spec) for collect_audio_metrics; None = encoders only, as before."""
+        self.audio_engine = AudioEngine(con_sd, emo_sd, sty_sd, self.device, norm_mean, norm_std, frame_based_feats, precision=precision, tail_sd=tail_sd)
 
     @classmethod
     def from_state_dicts(cls, denoiser_sd: Dict[str, np.ndarray], prior_sd: Optional[Dict[str, np.ndarray]],
@@ -216,6 +219,26 @@ class PretrainedLPDM_v1:
             raise NotImplementedError("no audio encoders loaded: setup() found no AST checkpoint; call "
                                       "set_audio_encoders(...), pass audio_encoder=..., or feed precomputed embeddings")
         return self.audio_engine.process_single_seq(sliced_chunk, framerate, baseline)
+
+    def collect_audio_metrics(self, sliced_chunk, framerate=16000 // 2, baseline=False, tgtpath=None):
+        """infer_ldm.py:195-208: kaldi fbank -> pad / normalise -> AST_EVP.eval_func(metrics=True) (encoders + classifier heads, fusion + decoder back to
+        a 1024 x 128 fbank, encoders again) -> <tgtpath>/audio_metrics/fbank.pkl, the reference's dict: "fbanks", "emo" / "sty" / "con" and "new_emo" /
+        "new_sty" / "new_con", each {"feature", "predicted_labels"} (None for con).  Deviation: the tensors are moved to the CPU before pickling (the
+        reference pickles them on its device, so its file only loads where that device exists).  Returns the dict."""
+        if self.audio_engine is None or not getattr(self.audio_engine, "has_tail", False):
+            raise NotImplementedError("collect_audio_metrics needs the HIP audio front-end WITH AST_EVP's fusion / decoder / classifier heads: the AST "
+                                      "checkpoint setup() found has none; call set_audio_encoders(..., tail_sd=...)")
+        w = torch.as_tensor(sliced_chunk)
+        if w.dim() == 2:
+            w = w[0]
+        d = self.audio_engine.metrics(self.audio_engine.fbank(w[None]))
+        cpu = lambda v: v.detach().cpu() if isinstance(v, torch.Tensor) else v
+        fbank_dict = {k: ({kk: cpu(vv) for kk, vv in v.items()} if isinstance(v, dict) else cpu(v)) for k, v in d.items()}
+        metric_dump = Path(tgtpath) / "audio_metrics"
+        metric_dump.mkdir(parents=True, exist_ok=True)
+        with open(metric_dump / "fbank.pkl", "wb") as f:
+            pickle.dump(fbank_dict, f)
+        return fbank_dict
 
     def process_seq_list(self, chunks, framerate=16000 // 2, baseline=False):
         """process_single_seq for a list of waveforms -> [(con, emo, sty), ...], each (1, 256).  The reference embeds audio by

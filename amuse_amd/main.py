@@ -186,6 +186,10 @@ def main(argv=None):
                     help="arithmetic of the audio front-end (fbank + 3 x AST) of infer_gesture / edit_gesture.  bf16 (default): bf16 operands, embeddings ~5e-3 off the "
                          "fp32 encoders; fp32x: split-fp16 operands, embeddings within 1e-5 - the mode in which a --precision fp32x run is in parity FROM THE WAVEFORM "
                          "(1.04 GB more device memory for the weight images, several times the front-end's time)")
+    ap.add_argument("--audio-metrics", action="store_true",
+                    help="infer_gesture: also write <rep>/rst_0/<audio stem>/audio_metrics/fbank.pkl for every audio - the dict of the reference's "
+                         "collect_audio_metrics (encoder features + predicted emotion / speaker labels, the fbank AST_EVP's fusion + decoder reconstruct from "
+                         "them, and the encoders' outputs on that reconstruction).  Needs an AST checkpoint that holds the fusion / decoder / classifier heads")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--gpus", type=int, default=1, help="one process per GPU on this node: train_gesture = data-parallel ranks (RCCL all-reduce); infer_gesture / "
                                                          "edit_gesture = the job list cut into contiguous ranges, each rank embeds, samples and writes its own (no collective; "
@@ -258,13 +262,15 @@ def main(argv=None):
             setattr(model, k, tp["test"][k]["use"])
         wd = tp["wav_dtw_mfcc"]
         model.set_audio_encoders(*(aw.make_ast_weights(0, n) for n in aw.ENCODERS), wd.get("dataset_mean", -9.173025),
-                                 wd.get("dataset_std", 5.062332), wd.get("frame_based_feats", True), precision=args.audio_precision)
+                                 wd.get("dataset_std", 5.062332), wd.get("frame_based_feats", True), precision=args.audio_precision,
+                                 tail_sd=aw.make_ast_tail_weights(0) if args.audio_metrics else None)
         ldm_epoch = 0
     else:
         config["_ldm_cfg_override"] = ldm_cfg
         tp["wav_dtw_mfcc"]["audio_precision"] = args.audio_precision
         model = PretrainedLPDM_v1(None)
         ldm_epoch = model.setup(config, device, processed, None, False, baseline, verbose=False, diffonly=diffonly)
+    tp["test"]["audio_metrics"] = bool(args.audio_metrics)
     model.precision = args.precision
     print(f"[amuse_amd] sampler / decoder precision: {args.precision}; audio front-end precision: {args.audio_precision}"
           + (" (split-fp16 AST encoders: with --precision fp32 / fp32x the run is in parity from the waveform)" if args.audio_precision == "fp32x"

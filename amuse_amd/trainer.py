@@ -427,6 +427,13 @@ class trainer:
                     if sd is not None:
                         print(f"VISUALIZATION: LIST AUDIOS {i} =====>")
                     self._animate(sd, video_dump_r / f"rst_{i}")
+            # opt-in (amuse_amd.main --audio-metrics): the reference's collect_audio_metrics (infer_ldm.py:195-208) for each of this rank's audios,
+            # beside its motion: <rep>/rst_0/<audio stem>/audio_metrics/fbank.pkl
+            if self.config["TRAIN_PARAM"]["test"].get("audio_metrics", False):
+                for k, a in enumerate(audios):
+                    if mine[k]:
+                        wave = load_wav(a)
+                        self.model.collect_audio_metrics(wave - wave.mean(), framerate=16000, baseline=baseline, tgtpath=video_dump_r / "rst_0" / a.stem)
         print(f"[LDM EVAL] Audio list inference done, total time elapsed: {time.time() - start_time:.4f} s")
 
     # ------------------------------------------------------------------ edit tasks

@@ -400,6 +400,57 @@ int amuse_audio_features(amuse_audio_ctx* ctx, const float* waves, int n_samples
 int amuse_audio_set_precision(amuse_audio_ctx* ctx, int precision);
 int amuse_audio_precision(const amuse_audio_ctx* ctx);
 
+/* ------------------------------------------------------------------------------------------------
+ * Audio model metrics: the tail of AST_EVP behind the three encoders, as PretrainedLPDM_v1.collect_audio_metrics reaches it
+ * (models/latent_diffusion/infer_ldm.py:195-208 -> Pretrained_AST_EVP.get_reconstructed_fbank -> AST_EVP.eval_func(metrics=True),
+ * models/audio/AST_EVP.py:84-103): the classifier heads of emo_enc / sty_enc (audio_main_new.py:76-81,191-204), FusionBlock and
+ * DecoderBlock (AST_EVP.py:12-42,63-82).  The two-encoder ablations (fusion_ablation / reconstruct_ablation) are not built.
+ *
+ * Parameters: ONE flat fp32 array of AMUSE_AST_TAIL_PARAMS floats, AST_EVP's state-dict entries in this order (amuse_amd/audio_weights.py
+ * ast_tail_param_spec is the authority): for enc in (emo_enc, sty_enc), L = 8 / 30: mlp_head.0.weight [256], .bias, mlp_head.1.weight [L][256], .bias,
+ * mlp_head_featbased.0.weight [768], .bias, mlp_head_featbased.1.weight [L][768], .bias; fusion.layers.{0,1} (d = 768), fusion.norm.weight, .bias,
+ * fusion.fc.weight [512][768], .bias; decode.layers.{0..3} (d = 512), decode.norm.weight, .bias, decode.projection.0.weight [1024][512], .bias,
+ * decode.projection.2.weight [131072][1024], .bias.  A layer is nn.TransformerEncoderLayer(d, nhead=4) in torch's order: self_attn.in_proj_weight [3d][d],
+ * self_attn.in_proj_bias, self_attn.out_proj.weight [d][d], .bias, linear1.weight [2048][d], .bias, linear2.weight [d][2048], .bias, norm1.weight, .bias,
+ * norm2.weight, .bias (post-norm, ReLU, eps 1e-5, dropout inactive).
+ *
+ * Arithmetic.  Heads, fusion, decoder layers and the 512 -> 1024 projection are fp32 in BOTH precisions of the context: fp32 weights, FMAs with fp32
+ * accumulation, two-pass LayerNorm, q scaled by head_dim ** -0.5, softmax over the at most 16 keys of a group.  The 1024 -> 131072 projection follows
+ * amuse_audio_set_precision: AMUSE_PREC_BF16 - weights and activations rounded to bf16 (nearest even), fp32 accumulation on v_mfma_f32_16x16x32_bf16, fp32
+ * bias; AMUSE_PREC_F32X - the contract of the encoders' parity mode: hi = rn16(x), lo = rn16(x - hi) of weights and activations, a product is
+ * Wl.xh + Wh.xl + Wh.xh on v_mfma_f32_16x16x32_f16, lo.lo dropped; that mode's weight image (537 MB; the bf16 one is 268 MB) is built on the first
+ * reconstruct in the mode from a host copy kept until then.  bf16 results are bit for bit unchanged by a round trip through AMUSE_PREC_F32X.
+ *
+ * amuse_audio_set_tail uploads the parameters (host memory; again replaces them).  Not stream-ordered.  The tail has ONE workspace: its calls on one
+ * context must not overlap on different streams. */
+#define AMUSE_AST_TAIL_PARAMS 158950988u
+int amuse_audio_set_tail(amuse_audio_ctx* ctx, const float* tail_params, size_t n);
+/* amuse_audio_encode with the pooling chosen per call (frame_based 1: mean over the patch tokens, 0: (cls + dist) / 2, < 0: the context's - feat_out is then
+ * bit for bit what amuse_audio_encode writes), plus the encoder's classifier head: logits_out dev [B][8] (AMUSE_AUDIO_EMO) / [B][30] (AMUSE_AUDIO_STY),
+ * nullable.  Frame-based: mlp_head_featbased((cls + dist) / 2 of the final norm) - a second pooling launch over the same residual stream; otherwise
+ * mlp_head(features).  Returns AMUSE_EINVAL for a non-NULL logits_out with AMUSE_AUDIO_CON (label_dim 0: the reference's predicted_labels is None),
+ * AMUSE_ESTATE when logits are asked for and no tail is set or the build lacks the tail's translation unit (amuse_audio_tail.hip); nothing is launched then. */
+int amuse_audio_encode_labels(amuse_audio_ctx* ctx, int which, int frame_based, const float* fbank, int B, float* feat_out, float* logits_out, void* stream);
+/* AST_EVP.reconstruct(cat(emo, sty, con), reconstruct_only=True): con / emo / sty dev [B][256] -> fbank_out dev [B][1024][128] (output f = 128 h + w).
+ * The reference hands the layers a 2-D tensor, which torch treats as ONE sequence whose tokens are the batch rows: the rows of a call attend to each other.
+ * `group` = S in 1..16 with B % S == 0 restates that: consecutive runs of S rows form one sequence (S = B: the reference's batch; S = 1: the single clip of
+ * collect_audio_metrics, softmax exactly 1).  A row's bits depend on its group's contents and its position inside the group and on nothing else (not on
+ * B, the group's index or the 32-row chunking).  AMUSE_EINVAL for a bad B / group or NULL, AMUSE_ESTATE without a tail (as above); nothing is launched then. */
+int amuse_audio_reconstruct(amuse_audio_ctx* ctx, const float* con, const float* emo, const float* sty, int B, int group, float* fbank_out, void* stream);
+/* The same up to the last Linear's input, for tests: hidden_out dev [B][1024] = ReLU(decode.projection.0(...)), fp32. */
+int amuse_debug_tail_hidden(amuse_audio_ctx* ctx, const float* con, const float* emo, const float* sty, int B, int group, float* hidden_out, void* stream);
+
+/* The last Linear's kernel in isolation (csrc/k_audio_tail.hip), for tests and tools/gpu_audio_tail_cost.py: out[B][N] = A[B][K] . W[N][K]^T + bias, A / bias /
+ * out dev fp32 row-major, B >= 1 (passes of 32 rows), N % 256 == 0, K % 64 == 0, 64 <= K <= 1024, precision AMUSE_PREC_BF16 or AMUSE_PREC_F32X.
+ * W_packed (dev) is the kernel's own weight order, written by amuse_debug_tail_pack (host memory, no GPU call): 1 KiB units of [64 lanes][8 x 16 bit] = 16
+ * features x 32 k, lane (g, i) = W[16 t + i][32 s + 8 g .. + 7]; the units of feature tile t are consecutive (s ascending), tiles ascending.  As an index
+ * into 16-bit elements:
+ *     bf16:  ((f >> 4) * (K >> 5) + (k >> 5)) * 512 + ((((k & 31) >> 3) << 4) + (f & 15)) * 8 + (k & 7)              holds bf16(W[f][k]), N * K elements
+ *     fp32x: ((f >> 4) * (K >> 5) + (k >> 5)) * 1024 + plane * 512 + (the same lane / element term)                   plane 0 = hi, 1 = lo (amuse_debug_f16_split), 2 * N * K
+ * A wave reads a contiguous run of tiles, i.e. one contiguous byte range. */
+int amuse_debug_tail_pack(const float* W, int N, int K, int precision, void* out);
+int amuse_debug_tail_gemm(const float* A, const void* W_packed, const float* bias, int B, int N, int K, int precision, float* out, void* stream);
+
 /* The front-end's GEMM kernel in isolation, for tests and tools/gpu_gemm_bench.py: out = A . W^T + bias.
  * The front-end keeps every GEMM operand TILE-MAJOR in HBM (16-row x 32-feature tiles of 64 lanes x 8 elements, a bf16
  * tile being one MFMA fragment; amuse_amd/csrc/amuse_audio.hpp): A dev bf16 tile-major [M rounded up to 128][K], W dev

@@ -32,7 +32,9 @@ EXPORTS = [
     "amuse_debug_set_ablation", "amuse_set_sample_dropout", "amuse_set_decode_dropout",
     "amuse_train_ws_floats", "amuse_train_set_lane", "amuse_train_ln_fwd", "amuse_train_ln_bwd", "amuse_train_bias_gelu_drop_fwd", "amuse_train_bias_gelu_drop_bwd", "amuse_train_colsum",
     "amuse_train_layer_fwd", "amuse_train_layer_bwd", "amuse_train_linear_fwd", "amuse_train_linear_bwd", "amuse_train_adamw", "amuse_train_adamw_dev", "amuse_train_epoch_advance", "amuse_train_epoch_set", "amuse_train_attn_fwd", "amuse_train_attn_bwd",
+    "amuse_body_create", "amuse_body_destroy", "amuse_body_set_subjects", "amuse_body_reserve", "amuse_body_forward", "amuse_body_vertex_loss", "amuse_body_info",
 ]
+BODY_ROT_AA, BODY_ROT_6D = 0, 1   # include/amuse_hip.h AMUSE_BODY_ROT_*
 
 
 class AmuseHipError(RuntimeError):
@@ -49,6 +51,12 @@ class TrainLayer(C.Structure):
                 + [(n, _FP) for n in ("Wo bo g1 be1 Wv bv Wc bc g2 be2 W1 b1 W2 b2 g3 be3 x o2 mem x1 zh1 r1 c vk xm zh2 r2 h a out zh3 r3 tmp dout dx do2 dmem "
                                       "dWo dbo dg1 dbe1 dWv dbv dWc dbc dg2 dbe2 dW1 db1 dW2 db2 dg3 dbe3 s128a s128b s512a s512b sdc ws Win bin qkv lse dqkv dWin dbin").split()]
                 + [("off_self", C.c_uint64)])
+
+
+class BodyModelC(C.Structure):
+    """include/amuse_hip.h `amuse_body_model` (host arrays)."""
+    _fields_ = [("V", C.c_int), ("n_betas", C.c_int), ("v_template", C.POINTER(C.c_float)), ("shapedirs", C.POINTER(C.c_float)), ("posedirs", C.POINTER(C.c_float)),
+                ("J_regressor", C.POINTER(C.c_float)), ("weights", C.POINTER(C.c_float)), ("parents", C.POINTER(C.c_int))]
 
 
 class Schedule(C.Structure):
@@ -179,6 +187,18 @@ def load() -> C.CDLL:
               "amuse_train_layer_fwd", "amuse_train_layer_bwd", "amuse_train_linear_fwd", "amuse_train_linear_bwd"):
         getattr(lib, n).restype = C.c_int
     for n in ("amuse_audio_fbank", "amuse_audio_encode", "amuse_audio_features", "amuse_debug_gemm", "amuse_debug_tile"):
+        getattr(lib, n).restype = C.c_int
+    # SMPL-X body model (csrc/amuse_body.hip)
+    lib.amuse_body_create.restype = vp
+    lib.amuse_body_create.argtypes = [C.c_int, C.POINTER(BodyModelC)]
+    lib.amuse_body_destroy.restype = None
+    lib.amuse_body_destroy.argtypes = [vp]
+    lib.amuse_body_set_subjects.argtypes = [vp, C.POINTER(C.c_float), C.c_int]
+    lib.amuse_body_reserve.argtypes = [vp, C.c_size_t]
+    lib.amuse_body_forward.argtypes = [vp, fp, C.c_int, fp, vp, C.c_int, C.c_int, C.c_int, fp, fp, vp]
+    lib.amuse_body_vertex_loss.argtypes = [vp, fp, fp, fp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp]
+    lib.amuse_body_info.argtypes = [vp, C.c_int]
+    for n in ("amuse_body_set_subjects", "amuse_body_reserve", "amuse_body_forward", "amuse_body_vertex_loss", "amuse_body_info"):
         getattr(lib, n).restype = C.c_int
     if lib.amuse_abi_version() != ABI_VERSION:
         raise AmuseHipError(f"ABI mismatch: library {lib.amuse_abi_version()} vs binding {ABI_VERSION}")

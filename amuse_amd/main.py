@@ -91,12 +91,19 @@ def train_gesture_entry(args, dirname: Path, config: dict):
     # silently training another objective
     if ld.get("optimizer_name", "adamw") != "adamw":
         raise SystemExit(f"train_gesture: optimizer_name {ld.get('optimizer_name')!r}: the reference's LPDM trainer builds AdamW only (trainer.py:184)")
+    # the two vertex-displacement terms (latent_losses.py:135-146,173-250) need the user's own SMPL-X model files (licensed; the reference's trainer.py:94-104
+    # loads them from <root>/body_models/codebase/models/smplx)
+    smplx_dir = None
     if ld.get("vtex_displacement", False) and not args.skip_vtex_loss:
-        raise SystemExit("train_gesture: TRAIN_PARAM.latent_diffusion.vtex_displacement is True (scripts/overrides/train_gesture.yaml:25): the "
-                         "rec / gen vertex-displacement loss terms need the licensed SMPL-X body models (latent_losses.py:173-250), which this "
-                         "path does not have.  Pass --skip-vtex-loss to train WITHOUT those two terms (checkpoint names then read vtexR0.0000 / "
-                         "vtexG0.0000), or set vtex_displacement: False")
-    if ld.get("vtex_displacement", False):
+        from . import body
+        smplx_dir = Path(args.smplx_models) if args.smplx_models else dirname / "body_models" / "codebase" / "models" / "smplx"
+        if not body.models_present(smplx_dir):
+            raise SystemExit("train_gesture: TRAIN_PARAM.latent_diffusion.vtex_displacement is True (scripts/overrides/train_gesture.yaml:25): the "
+                             "rec / gen vertex-displacement loss terms need the licensed SMPL-X body models (latent_losses.py:173-250), and "
+                             f"{', '.join(body.SMPLX_FILES.values())} were not all found in {smplx_dir} (--smplx-models DIR names another directory).  "
+                             "Pass --skip-vtex-loss to train WITHOUT those two terms (checkpoint names then read vtexR0.0000 / "
+                             "vtexG0.0000), or set vtex_displacement: False")
+    elif ld.get("vtex_displacement", False):
         print("[LPDM-T] WARNING: vtex_displacement is True in the configuration but --skip-vtex-loss drops both vertex-displacement terms", flush=True)
     ldm_cfg = config.get("_ldm_cfg")
     argv = ["--batch", str(ld.get("batch_size", 32)), "--epochs", str(args.epochs or ld.get("n_epochs", 12000)),
@@ -123,6 +130,12 @@ def train_gesture_entry(args, dirname: Path, config: dict):
         argv += ["--device", args.device]
     if args.iters_per_epoch:
         argv += ["--iters-per-epoch", str(args.iters_per_epoch)]
+    if smplx_dir is not None:
+        version = str(tp.get("wav_dtw_mfcc", {}).get("ablation_version") or "v0")
+        if version not in ("v0", "v1"):
+            raise SystemExit(f"train_gesture: TRAIN_PARAM.wav_dtw_mfcc.ablation_version is {version!r}: the vertex-displacement terms know the dataset versions "
+                             "v0 (male / female body model by the actor) and v1 (neutral), as latent_losses.py:184-199 does")
+        argv += ["--smplx-models", str(smplx_dir), "--dataset-version", version]
     print(f"Experiment init: AMUSE, fn: train_gesture, time: {time.asctime()}")
     try:
         return train_gesture.main(argv)
@@ -201,6 +214,8 @@ def main(argv=None):
     ap.add_argument("--iters-per-epoch", type=int, default=None, help="train_gesture --synthetic: iterations per epoch")
     ap.add_argument("--skip-vtex-loss", action="store_true", help="train_gesture: train without the two vertex-displacement loss terms when the "
                                                                   "configuration asks for them (they need the SMPL-X body models)")
+    ap.add_argument("--smplx-models", default=None, help="train_gesture: directory holding SMPLX_MALE.npz, SMPLX_FEMALE.npz, SMPLX_NEUTRAL.npz for the vertex-displacement "
+                                                         "loss terms (default: <root>/body_models/codebase/models/smplx, the reference's path)")
     args = ap.parse_args(argv)
     fn = args.fn[0]
     if fn not in ("infer_gesture", "edit_gesture", "train_gesture"):

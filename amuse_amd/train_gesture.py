@@ -77,11 +77,18 @@ class LatentPriorLosses:
     """Stage / version / lambdas of the loss config select the terms exactly as latent_losses.py:36-98 does; update()
     returns the weighted total of one iteration and accumulates the un-weighted terms, compute() averages them."""
 
-    def __init__(self, cfg: Optional[dict] = None, device="cpu"):
+    def __init__(self, cfg: Optional[dict] = None, device="cpu", body=None):
+        """body: amuse_amd.body.BodyLosses (the SMPL-X models the reference's trainer loads, trainer.py:94-104) - needed by vtex_displacement: True, which adds
+        rec_vtex_displacement / gen_vtex_displacement as latent_losses.py:135-146 does: SmoothL1 on the vertices of (reconstruction, batch) and (generation, batch),
+        weight LAMBDA_REC, part of `total`, NO gradient (_get_vertices runs under no_grad).  Deviation, stated: the vertices are posed from the 6D feature rows
+        the trainer already has, not from their matrix -> axis-angle -> matrix round trip (identity up to fp32 rounding; tests/test_body_host_cpu.py)."""
         c = dict(LOSS_CFG)
         c.update((cfg or {}).get("losses", cfg or {}))
-        if c.get("vtex_displacement"):
-            raise NotImplementedError("vertex-displacement losses need the SMPL-X body models (trainer.py:91-104); not built")
+        if c.get("vtex_displacement") and body is None:
+            raise NotImplementedError("vertex-displacement losses need the SMPL-X body models (trainer.py:91-104): pass body=amuse_amd.body.BodyLosses(...)")
+        self.body = body if c.get("vtex_displacement") else None
+        if self.body is not None and c["stage"] != "vae_diffusion":
+            raise ValueError(f"vtex_displacement loss is only in vae_diffusion, but {c['stage']}")   # latent_losses.py:33
         self.cfg, self.d = c, device
         self.stage, self.version = c["stage"], c["train_lpdm"]["version"]
         losses = []
@@ -95,6 +102,8 @@ class LatentPriorLosses:
                 losses.append("latent_feature")
             else:
                 raise ValueError(f"train_lpdm_version {self.version} not supported, choose: v0 or v1")
+            if self.body is not None:
+                losses += ["rec_vtex_displacement", "gen_vtex_displacement"]
         if self.stage not in ("vae", "diffusion", "vae_diffusion"):
             raise ValueError(f"Stage {self.stage} not supported")
         losses.append("total")
@@ -140,6 +149,11 @@ class LatentPriorLosses:
                     total = total + self._update_loss("gen_feature", rs_set["gen_m_rst"], rs_set["m_ref"])
             else:
                 total = total + self._update_loss("latent_feature", rs_set["lat_rm"], rs_set["lat_m"])
+            if self.body is not None:       # values only; accumulated in place on the device (a captured step replays these launches)
+                rec, gen = self.body.terms(rs_set["m_ref"], rs_set["m_rst"], rs_set.get("gen_m_rst"), rs_set.get("attr"), rs_set.get("subjects"))
+                self.sums["rec_vtex_displacement"] += rec
+                self.sums["gen_vtex_displacement"] += gen
+                total = total + self.cfg["LAMBDA_REC"] * (rec + gen)
         self.sums["total"] += total.detach()
         self.count += 1
         return total
@@ -195,7 +209,7 @@ class GestureTrainer:
 
     def __init__(self, prior: MotionPrior, ldm: LatentDiffusionTrainModule, device, lr: float = 1e-4, loss_cfg: Optional[dict] = None,
                  inner_sampler: Optional[Callable] = None, process_group=None, world: int = 1, kind: Optional[str] = None,
-                 grads_mode: str = "steal", sampler_stream: bool = True, optimizer: str = "flat", denoiser_stream: bool = True):
+                 grads_mode: str = "steal", sampler_stream: bool = True, optimizer: str = "flat", denoiser_stream: bool = True, body=None):
         self.model = {"prior": prior.to(device), "ldm": ldm.to(device)}
         # torch.distributions.Normal validates its arguments with blocking device -> host reads (6 per iteration: the host then waits for the previous
         # iteration's backward + optimizer step before it dispatches anything of the next, tools/probes/train_host/sync_points.py).  Off on the GPU
@@ -203,7 +217,7 @@ class GestureTrainer:
         if torch.device(device).type == "cuda" and os.environ.get("AMUSE_TRAIN_VALIDATE", "0") != "1":
             prior.validate_args = False
         self.device = torch.device(device)
-        self.lpdm_losses = LatentPriorLosses(loss_cfg, self.device)
+        self.lpdm_losses = LatentPriorLosses(loss_cfg, self.device, body=body)
         self.inner_sampler = inner_sampler      # (con, emo, sty, bsz) -> noise2feats (B,300,333) or None
         self.world, self.pg = world, process_group
         self.kind = kind                        # ablation variant of the LMDB id (trainer.py:393-399): full / emotion / identity
@@ -342,7 +356,7 @@ class GestureTrainer:
             with torch.no_grad():
                 gen = self.inner_sampler(con, emo, sty, motion.shape[0])
         rs_set = {"m_ref": motion, "m_rst": feats_rst, "dist_m": dist_m, "dist_ref": dist_ref, "noise_pred": n_set["noise_pred"],
-                  "noise": n_set["noise"], "gen_m_rst": gen, "attr": batch.get("ld_attr")}
+                  "noise": n_set["noise"], "gen_m_rst": gen, "attr": batch.get("ld_attr"), "subjects": batch.get("ld_subjects")}
         return self.lpdm_losses.update(rs_set)
 
     def train_step(self, batch, **explicit) -> torch.Tensor:
@@ -390,6 +404,8 @@ class GestureTrainer:
         keys = [k for k in ("ld_motion", "ld_audio_con", "ld_audio_emo", "ld_audio_sty") if batch.get(k) is not None]
         static = {k: batch[k].to(self.device).clone() for k in keys}
         static["ld_attr"] = batch.get("ld_attr")
+        if self.lpdm_losses.body is not None:        # the gendered split as device data: a replay follows the new batch's actors
+            static["ld_subjects"] = self.lpdm_losses.body.subjects(batch["ld_attr"])
         lib = train_ops._st(self.device)["lib"]
         self.lpdm_opt.push_step()
         count0 = self.lpdm_losses.count
@@ -421,6 +437,8 @@ class GestureTrainer:
         g = self._graph
         for k in g["keys"]:
             g["static"][k].copy_(batch[k], non_blocking=True)
+        if "ld_subjects" in g["static"]:
+            g["static"]["ld_subjects"].copy_(torch.from_numpy(self.lpdm_losses.body.subject_rows(batch["ld_attr"])))
         g["g1"].replay()
         self.allreduce_gradients()
         g["g2"].replay()
@@ -699,7 +717,7 @@ def ablation_kind(lmdb_id: Optional[str]) -> Optional[str]:
 def build_trainer(device, rank: int = 0, world: int = 1, process_group=None, seed: int = 0, use_hip_sampler: bool = True,
                   dropout: float = 0.1, sampler_refresh: int = 1, ldm_cfg: Optional[dict] = None, lr: float = 1e-4,
                   kind: Optional[str] = None, inner: Optional[str] = None, grads_mode: str = "steal", sampler_stream: bool = True,
-                  optimizer: str = "flat", denoiser_stream: bool = True) -> GestureTrainer:
+                  optimizer: str = "flat", denoiser_stream: bool = True, body=None) -> GestureTrainer:
     """Random-init prior + ldm (the deterministic weights of amuse_amd/weights.py, identical on every rank - what DDP's
     initial broadcast gives the reference's DataParallel-less single-GPU run) and the trainer around them.
     lr = TRAIN_PARAM.latent_diffusion.lr_base (trainer.py:181-184); ldm_cfg = configs/<arch>.json merged with diff_o.yaml (its
@@ -713,8 +731,11 @@ def build_trainer(device, rank: int = 0, world: int = 1, process_group=None, see
     loss_cfg = None
     if (ldm_cfg or {}).get("losses") is not None:   # trainer.py:175-177: SMPL-X data switches the joints terms off; the vertex terms are not built
         loss_cfg = dict(ldm_cfg["losses"], use_recons_joints=False, vtex_displacement=False)
+    if body is not None:                            # the vertex terms are on exactly when the caller hands over the body models (amuse_amd.body.BodyLosses)
+        loss_cfg = dict(loss_cfg or LOSS_CFG, vtex_displacement=True)
     tr = GestureTrainer(prior, ldm, device, lr=lr, loss_cfg=loss_cfg, inner_sampler=None, process_group=process_group,
-                        world=world, kind=None if kind == "full" else kind, grads_mode=grads_mode, sampler_stream=sampler_stream, optimizer=optimizer, denoiser_stream=denoiser_stream)
+                        world=world, kind=None if kind == "full" else kind, grads_mode=grads_mode, sampler_stream=sampler_stream, optimizer=optimizer, denoiser_stream=denoiser_stream,
+                        body=body)
     inner = inner or os.environ.get("AMUSE_TRAIN_INNER", "eval")
     if inner not in ("eval", "train", "train-hip", "train-hip-decode"):
         raise ValueError(f"inner sampler {inner!r}: 'eval' (the persistent HIP sampler kernel, default), 'train' (the reference's train-mode semantics, dropout "
@@ -858,6 +879,10 @@ def main(argv=None):
                          "trainer's modules; train-hip-decode = train-hip with the decode in the HIP decode kernels too (amuse_set_decode_dropout), on the sampler's stream")
     ap.add_argument("--no-graph", action="store_true", help="keep the iteration eager (default on the GPU: captured as two HIP graphs after three eager iterations)")
     ap.add_argument("--ldm-cfg", default=None, help="JSON file: configs/<arch>.json merged with diff_o.yaml (losses, schedulers); default: the shipped values")
+    ap.add_argument("--smplx-models", default=None, help="directory holding SMPLX_MALE.npz, SMPLX_FEMALE.npz and SMPLX_NEUTRAL.npz: train WITH the two vertex-displacement "
+                                                         "loss terms (TRAIN_PARAM.latent_diffusion.vtex_displacement); default: without them")
+    ap.add_argument("--dataset-version", default="v0", choices=["v0", "v1"], help="wav_dtw_mfcc.ablation_version: v0 poses every clip through the male / female body "
+                                                                                  "model of its actor, v1 through the neutral one (only with --smplx-models)")
     args = ap.parse_args(argv)
     from . import launch
     if args.gpus > 1 and not launch.launched_by_torchrun():
@@ -886,8 +911,14 @@ def main(argv=None):
         import json
         ldm_cfg = json.load(open(args.ldm_cfg))
     kind = args.kind or ablation_kind(args.cache)
+    body = None
+    if args.smplx_models:
+        from . import body as body_mod
+        body = body_mod.BodyLosses(body_mod.load_models(args.smplx_models), device, version=args.dataset_version)
+        if rank == 0:
+            print(f"[LPDM-T] vertex-displacement losses ON: SMPL-X models from {args.smplx_models} (V = {body.V}, dataset version {args.dataset_version})", flush=True)
     tr = build_trainer(device, rank, world, process_group=pg, use_hip_sampler=device.type == "cuda", ldm_cfg=ldm_cfg, lr=args.lr, kind=kind,
-                       inner=args.inner_sampler)
+                       inner=args.inner_sampler, body=body)
     tr.use_graph = device.type == "cuda" and not args.no_graph
     if rank == 0:
         lc = tr.lpdm_losses.cfg

@@ -570,6 +570,62 @@ int amuse_train_linear_fwd(const float* x, const float* W, const float* b, long 
 int amuse_train_linear_bwd(const float* dy, const float* x, const float* W, long rows, int K, int N, float* dW, float* db, float* dx,
                            int accumulate_dx, float* ws, void* stream);
 
+/* ------------------------------------------------------------------ SMPL-X body model (csrc/amuse_body.hip, k_body.hip; amuse_amd/body.py)
+ * Replaces what the reference gets from the `smplx` package in LatentPriorLosses._get_vertices (models/latent_diffusion/utils/latent_losses.py:135-146,173-250):
+ * SMPLX(num_betas = n_betas, use_pca=False, flat_hand_mean=True) called with expression = 0 - linear blend skinning, generic in the vertex count - and the two
+ * vertex-displacement terms built on it.  A context of its own, independent of amuse_ctx; the arrays are what a user loads from their own SMPLX_*.npz.
+ * `smplx` is not a dependency of this project: parity is against a RESTATEMENT of the published algorithm (tests/body_ref.py), not a pin.
+ * Per frame: v_shaped = v_template + shapedirs . betas; J = J_regressor . v_shaped (both hoisted per subject: amuse_body_set_subjects); R_j = Rodrigues(pose_j)
+ * (angle = |pose_j + 1e-8|, a zero vector gives the identity) or the Gram-Schmidt of rotation_6d_to_matrix; pose_feature = (R_1..R_54 - I) row-major [486];
+ * v_posed = v_shaped + pose_feature . posedirs; the kinematic chain over `parents`; A_j = [G_j.R | G_j.t - G_j.R J_j];
+ * vertex_v = (sum_j w[v][j] A_j) . [v_posed_v; 1] + transl, posed joint j = G_j.t + transl.
+ * Host arrays of the model (fp32 / int32, copied by amuse_body_create):
+ *   v_template [V][3], shapedirs [V][3][n_betas], posedirs [486][V * 3] (the file's [V][3][486] transposed), J_regressor [55][V], weights [V][55],
+ *   parents [55] with parents[0] = -1 and 0 <= parents[j] < j (AMUSE_EINVAL otherwise: amuse_body_create returns NULL). */
+typedef struct amuse_body_ctx amuse_body_ctx;
+typedef struct {
+    int V, n_betas;
+    const float* v_template;
+    const float* shapedirs;
+    const float* posedirs;
+    const float* J_regressor;
+    const float* weights;
+    const int* parents;
+} amuse_body_model;
+/* rotation input: AA = axis-angle rows, 6D = the project's feature rows [N][F][333] (55 x 6D | translation) */
+enum { AMUSE_BODY_ROT_AA = 0, AMUSE_BODY_ROT_6D = 1 };
+/* Packs the pose-corrective matrix into MFMA-fragment order (four output slots x, y, z, pad per vertex; hi and lo fp16 planes of the entries pre-scaled by a
+ * power of two - exact, undone on the accumulator - so that their pieces stay clear of fp16's subnormals) and the skinning weights into per-vertex
+ * (joint, weight) lists padded to the model's largest non-zero count (exact for any weight matrix, dense rows included).  Returns NULL on failure. */
+amuse_body_ctx* amuse_body_create(int device, const amuse_body_model* model);
+void amuse_body_destroy(amuse_body_ctx* ctx);
+/* betas host [S][n_betas]: v_shaped and J of every subject, on the host in double, uploaded as fp32 (the reference recomputes them per frame: the same values).
+ * Not stream-ordered: call it between, not during, the context's calls. */
+int amuse_body_set_subjects(amuse_body_ctx* ctx, const float* betas, int S);
+/* Sizes the workspace for calls of up to `frames` = N * F frames (three motion sets).  The compute calls size it themselves on first use; after a reserve that
+ * covers them they allocate nothing and synchronise nothing, so they can sit inside a captured graph.  Preconditions:
+ *   - growing allocates (so it must not happen inside a capture: reserve, or run the call once eagerly, BEFORE capturing); the outgrown workspace stays alive
+ *     until amuse_body_destroy, so a graph captured earlier keeps replaying into valid memory;
+ *   - a context has ONE workspace: its compute calls must not overlap in time, i.e. one stream per context (or calls ordered by events), as for amuse_ctx.
+ * Not stream-ordered itself: call it between, not during, the context's calls. */
+int amuse_body_reserve(amuse_body_ctx* ctx, size_t frames);
+/* rot_kind AA: rot dev [N][F][55][3], trans dev [N][F][3] or NULL (zero); 6D: rot dev [N][F][333], trans ignored (the row's last three).
+ * subject_dev: DEVICE int32 [N], the subject (row of amuse_body_set_subjects) of each clip; a clip whose value lies outside 0..S-1 is SKIPPED: its output rows
+ * are left untouched and it adds nothing to the loss sums (the trainer's gendered split: each model's call names its own clips, on the device).
+ * joints_out dev [N][F][55][3], vertices_out dev [N][F][V][3], either nullable (64-bit offsets).
+ * precision: AMUSE_PREC_F32X - the pose-blend product on split-fp16 operands (Pl.fh + Ph.fl + Ph.fh on v_mfma_f32_16x16x32_f16, fp32 accumulation) - or
+ * AMUSE_PREC_F16 (one product); everything else is fp32 in both.  Other values: AMUSE_EINVAL. */
+int amuse_body_forward(amuse_body_ctx* ctx, const float* rot, int rot_kind, const float* trans, const int* subject_dev, int N, int F, int precision,
+                       float* joints_out, float* vertices_out, void* stream);
+/* The two vertex-displacement terms: sums_out dev double [2] = the SmoothL1 (beta 1) SUMS over all N F V 3 vertex coordinates of (a, ref) and (b, ref); b may be
+ * NULL (sums_out[1] = 0).  The caller divides (by N F V 3 for the reference's mean).  ref / a / b: rot_kind 6D dev [N][F][333]; AA dev [N][F][168] = 55 x 3
+ * axis-angle | translation (the trainer's ld_motion rows).  No vertex array is written: the sets of a frame tile meet in registers.  Deterministic: per-workgroup
+ * fp32 partials, then a fixed-order double sum in a second launch; no float atomics. */
+int amuse_body_vertex_loss(amuse_body_ctx* ctx, const float* ref, const float* a, const float* b, int rot_kind, const int* subject_dev, int N, int F,
+                           int precision, double* sums_out, void* stream);
+/* diagnostics (host values): what = 0 V, 1 largest non-zero count of a skinning row, 2 the power-of-two pre-scale exponent of posedirs, 3 subjects set */
+int amuse_body_info(const amuse_body_ctx* ctx, int what);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,6 +33,7 @@ EXPORTS = [
     "amuse_train_ws_floats", "amuse_train_set_lane", "amuse_train_ln_fwd", "amuse_train_ln_bwd", "amuse_train_bias_gelu_drop_fwd", "amuse_train_bias_gelu_drop_bwd", "amuse_train_colsum",
     "amuse_train_layer_fwd", "amuse_train_layer_bwd", "amuse_train_linear_fwd", "amuse_train_linear_bwd", "amuse_train_adamw", "amuse_train_adamw_dev", "amuse_train_epoch_advance", "amuse_train_epoch_set", "amuse_train_attn_fwd", "amuse_train_attn_bwd",
     "amuse_body_create", "amuse_body_destroy", "amuse_body_set_subjects", "amuse_body_reserve", "amuse_body_forward", "amuse_body_vertex_loss", "amuse_body_info",
+    "amuse_body_enable_grad", "amuse_body_vertex_loss_grad",
 ]
 BODY_ROT_AA, BODY_ROT_6D = 0, 1   # include/amuse_hip.h AMUSE_BODY_ROT_*
 
@@ -198,7 +199,10 @@ def load() -> C.CDLL:
     lib.amuse_body_forward.argtypes = [vp, fp, C.c_int, fp, vp, C.c_int, C.c_int, C.c_int, fp, fp, vp]
     lib.amuse_body_vertex_loss.argtypes = [vp, fp, fp, fp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp]
     lib.amuse_body_info.argtypes = [vp, C.c_int]
-    for n in ("amuse_body_set_subjects", "amuse_body_reserve", "amuse_body_forward", "amuse_body_vertex_loss", "amuse_body_info"):
+    lib.amuse_body_enable_grad.argtypes = [vp]
+    lib.amuse_body_vertex_loss_grad.argtypes = [vp, fp, fp, fp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, fp, fp, vp]
+    for n in ("amuse_body_set_subjects", "amuse_body_reserve", "amuse_body_forward", "amuse_body_vertex_loss", "amuse_body_info", "amuse_body_enable_grad",
+              "amuse_body_vertex_loss_grad"):
         getattr(lib, n).restype = C.c_int
     if lib.amuse_abi_version() != ABI_VERSION:
         raise AmuseHipError(f"ABI mismatch: library {lib.amuse_abi_version()} vs binding {ABI_VERSION}")

@@ -87,17 +87,17 @@ def _split_rows(rows: torch.Tensor, kind: str):
     return rows[..., :NJ * w].reshape(rows.shape[:-1] + (NJ, w)), rows[..., NJ * w:NJ * w + 3]
 
 
-def torch_forward(model: BodyModel, betas, rot, trans=None, subject=None, kind: str = "aa", frames_per_pass: int = 64):
+def torch_forward(model: BodyModel, betas, rot, trans=None, subject=None, kind: str = "aa", frames_per_pass: int = 64, differentiable: bool = False):
     """float64 on rot's device: betas [S,B], rot [N,F,55,3] / [N,F,55,6], trans [N,F,3] or None, subject [N] (default: clip n -> row n % S)
-    -> joints [N,F,55,3], vertices [N,F,V,3]."""
+    -> joints [N,F,55,3], vertices [N,F,V,3].  differentiable: rot / trans are not detached, so autograd reaches them (the oracle of the HIP backward pass)."""
     dev = rot.device
     t64 = lambda a: torch.as_tensor(np.asarray(a), dtype=torch.float64, device=dev) if not torch.is_tensor(a) else a.to(dev, torch.float64)
-    rot = rot.detach().to(torch.float64)
+    rot = (rot if differentiable else rot.detach()).to(torch.float64)
     N, F = rot.shape[:2]
     V = model.V
     betas = t64(betas)
     sub = torch.arange(N, device=dev) % betas.shape[0] if subject is None else torch.as_tensor(subject, device=dev).long().clamp(0, betas.shape[0] - 1)
-    tr = torch.zeros(N, F, 3, dtype=torch.float64, device=dev) if trans is None else trans.detach().to(torch.float64)
+    tr = torch.zeros(N, F, 3, dtype=torch.float64, device=dev) if trans is None else (trans if differentiable else trans.detach()).to(torch.float64)
     vs = t64(model.v_template)[None] + torch.einsum("vcb,nb->nvc", t64(model.shapedirs), betas[sub])
     J = torch.einsum("jv,nvc->njc", t64(model.J_regressor), vs)
     P, W = t64(model.posedirs), t64(model.weights)
@@ -130,8 +130,19 @@ def _smooth_l1_sum(a, ref):
     return torch.where(d < 1.0, 0.5 * d * d, d - 0.5).sum()
 
 
-def torch_loss_sums(model: BodyModel, betas, ref, a, b=None, subject=None, kind: str = "6d", frames_per_pass: int = 32) -> torch.Tensor:
-    """SmoothL1 (beta 1) SUMS of (a, ref) and (b, ref) over the vertices, float64 [2]; ref / a / b are rows: [N,F,333] (6d) or [N,F,168] (aa)."""
+def torch_loss_sums(model: BodyModel, betas, ref, a, b=None, subject=None, kind: str = "6d", frames_per_pass: int = 32, differentiable: bool = False) -> torch.Tensor:
+    """SmoothL1 (beta 1) SUMS of (a, ref) and (b, ref) over the vertices, float64 [2]; ref / a / b are rows: [N,F,333] (6d) or [N,F,168] (aa).
+    differentiable: the sums carry gradient to a and b (never to ref, as in amuse_body_vertex_loss_grad)."""
+    if differentiable:
+        parts = [[], []]
+        for f0 in range(0, ref.shape[1], frames_per_pass):
+            sl = slice(f0, f0 + frames_per_pass)
+            vr = torch_forward(model, betas, *_split_rows(ref[:, sl], kind), subject=subject, kind=kind)[1]
+            for i, c in enumerate((a, b)):
+                if c is not None:
+                    parts[i].append(_smooth_l1_sum(torch_forward(model, betas, *_split_rows(c[:, sl], kind), subject=subject, kind=kind, differentiable=True)[1], vr))
+        zero = torch.zeros((), dtype=torch.float64, device=ref.device)
+        return torch.stack([torch.stack(p).sum() if p else zero for p in parts])
     out = torch.zeros(2, dtype=torch.float64, device=ref.device)
     F = ref.shape[1]
     for f0 in range(0, F, frames_per_pass):
@@ -175,7 +186,12 @@ class BodyEngine:
     __del__ = close
 
     def info(self) -> dict:
-        return {k: self.lib.amuse_body_info(self.ctx, i) for i, k in enumerate(("V", "skin_nnz", "posedirs_shift", "subjects"))}
+        return {k: self.lib.amuse_body_info(self.ctx, i) for i, k in enumerate(("V", "skin_nnz", "posedirs_shift", "subjects", "grad"))}
+
+    def enable_grad(self) -> None:
+        """Upload the transposed posedirs image vertex_loss_grad needs (about 86 MB at V = 10,475) and let reserve() size the backward partials too.  Allocates
+        and copies synchronously: call it BEFORE capturing a graph, and reserve() after it.  Idempotent."""
+        _lib.check(self.lib.amuse_body_enable_grad(self.ctx))
 
     def set_subjects(self, betas) -> None:
         b = np.ascontiguousarray(np.asarray(betas, dtype=np.float32).reshape(-1, self.model.n_betas))
@@ -233,6 +249,57 @@ class BodyEngine:
         return out
 
 
+    def vertex_loss_grad(self, ref, a, b=None, subject=None, scale=(1.0, 1.0), out=None, precision: Optional[str] = None):
+        """scale[i] x d(SmoothL1 sum of (a | b, ref))/d(a | b): feature rows [N,F,333] (6D only) -> (grad_a, grad_b | None), device float32 [N,F,333].  `out`:
+        a pair of tensors to write into (rows of skipped clips are left as they are; without `out` they are zero).  Needs enable_grad().  Deterministic."""
+        ref, a = self._f32(ref), self._f32(a)
+        N, F = int(ref.shape[0]), int(ref.shape[1])
+        assert ref.numel() == N * F * 333 and a.shape == ref.shape and (b is None or b.shape == ref.shape), (tuple(ref.shape), tuple(a.shape))
+        ga, gb = out if out is not None else (torch.zeros_like(a), torch.zeros_like(a) if b is not None else None)
+        assert self._f32(ga).shape == a.shape and (b is None or self._f32(gb).shape == a.shape)
+        _lib.check(self.lib.amuse_body_vertex_loss_grad(self.ctx, ref.data_ptr(), a.data_ptr(), self._f32(b).data_ptr() if b is not None else None, _lib.BODY_ROT_6D,
+                                                        self._subject(subject, N).data_ptr(), N, F, _PREC[precision or self.precision], float(scale[0]), float(scale[1]),
+                                                        ga.data_ptr(), gb.data_ptr() if b is not None else None, self._stream()))
+        return ga, (gb if b is not None else None)
+
+
+class VertexLossFn(torch.autograd.Function):
+    """sums [2] (float64) = BodyEngine.vertex_loss(ref, a, b) for EVERY engine of `engines` ([(engine, subject int32 [N]), ...]: the gendered split, each engine
+    skipping the other's clips), differentiable in a and b (6D feature rows).  Backward runs amuse_body_vertex_loss_grad for the inputs that require grad - each
+    engine writes its own clips' rows of one zero-initialised buffer - and multiplies by grad_output once.  A candidate that needs no gradient is not passed
+    to the backward kernels at all."""
+
+    @staticmethod
+    def forward(ctx, engines, ref, a, b, precision):
+        total = None
+        for eng, sub in engines:
+            s = eng.vertex_loss(ref, a, b, sub, "6d", precision=precision)
+            total = s if total is None else total + s
+        ctx.engines, ctx.precision, ctx.has_b = engines, precision, b is not None
+        ctx.save_for_backward(ref, a, *([b] if b is not None else []))
+        return total
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        saved = ctx.saved_tensors
+        ref, a, b = saved[0], saved[1], (saved[2] if ctx.has_b else None)
+        need_a, need_b = ctx.needs_input_grad[2], ctx.has_b and ctx.needs_input_grad[3]
+        ga = gb = None
+        if need_a or need_b:
+            # the kernel's first candidate is the one that needs a gradient; the second rides along only if both do
+            first, second = (a, b if need_b else None) if need_a else (b, None)
+            g1, g2 = torch.zeros_like(first), (torch.zeros_like(first) if second is not None else None)
+            for eng, sub in ctx.engines:
+                eng.vertex_loss_grad(ref, first, second, sub, out=(g1, g2), precision=ctx.precision)
+            go = grad_out.to(torch.float32)
+            if need_a:
+                ga = g1 * go[0]
+                gb = g2 * go[1] if need_b else None
+            else:
+                gb = g1 * go[1]
+        return None, None, ga, gb, None
+
+
 SMPLX_FILES = {"male": "SMPLX_MALE.npz", "female": "SMPLX_FEMALE.npz", "neutral": "SMPLX_NEUTRAL.npz"}
 
 
@@ -254,9 +321,9 @@ class BodyLosses:
     DEVIATION from the reference, stated: the trainer feeds the 6D feature rows it already has (rotation by rotation_6d_to_matrix's Gram-Schmidt); the reference
     converts matrix -> axis-angle -> matrix first, which is the identity up to fp32 rounding (tests/test_body_host_cpu.py holds the two together)."""
 
-    def __init__(self, models: dict, device, version: str = "v0", precision: str = "fp32x", actors=None):
+    def __init__(self, models: dict, device, version: str = "v0", precision: str = "fp32x", actors=None, grad: bool = False):
         from . import npz_writer
-        self.device, self.version = torch.device(device), version
+        self.device, self.version, self.grad = torch.device(device), version, bool(grad)
         if version not in ("v0", "v1"):
             raise ValueError(f"dataset version {version!r}: v0 (gendered models) or v1 (neutral)")
         self.genders = ("male", "female") if version == "v0" else ("neutral",)
@@ -281,6 +348,8 @@ class BodyLosses:
             for g in self.genders:
                 self.engines[g] = BodyEngine(self.device, self.models[g], precision)
                 self.engines[g].set_subjects(self.betas)
+                if self.grad:
+                    self.engines[g].enable_grad()
             self._out = {g: torch.zeros(2, dtype=torch.float64, device=self.device) for g in self.genders}
 
     def close(self):
@@ -303,9 +372,37 @@ class BodyLosses:
     def subjects(self, attr) -> torch.Tensor:
         return torch.from_numpy(self.subject_rows(attr)).to(self.device)
 
-    def terms(self, m_ref, m_rst, gen_m_rst=None, attr=None, subjects=None):
-        """feature rows [B,F,333] -> (rec_vtex_displacement, gen_vtex_displacement): SmoothL1 means over B F V 3, float32 scalars on the device, no gradient;
-        gen is 0 without a generation (a CPU run has no in-loop sampler)."""
+    def reserve(self, frames: int) -> None:
+        for e in self.engines.values():
+            e.reserve(frames)
+
+    def _terms_grad(self, m_ref, m_rst, gen_m_rst, attr, subjects):
+        """terms() with gradient: DEVIATION from the reference, opt-in (its vertices are computed under no_grad, latent_losses.py:173).  The two means carry
+        gradient to m_rst, and to gen_m_rst when that requires grad; the reference motion gets none.  The gendered split stays device data."""
+        B, F = int(m_ref.shape[0]), int(m_ref.shape[1])
+        subjects = self.subjects(attr) if subjects is None else subjects
+        f = lambda x: None if x is None else x.to(torch.float32).contiguous()
+        ref, rst, gen = f(m_ref.detach()), f(m_rst), f(gen_m_rst)
+        if self.device.type == "cuda":
+            for e in self.engines.values():
+                e.enable_grad()
+            total = VertexLossFn.apply([(self.engines[g], subjects[i]) for i, g in enumerate(self.genders)], ref, rst, gen, None)
+        else:
+            rows = subjects.cpu().numpy()
+            total = torch.zeros(2, dtype=torch.float64)
+            for i, g in enumerate(self.genders):
+                idx = np.nonzero(rows[i] >= 0)[0]
+                if len(idx):
+                    pick = lambda x: None if x is None else x[idx]
+                    total = total + torch_loss_sums(self.models[g], self.betas, pick(ref), pick(rst), pick(gen), subject=rows[i][idx], kind="6d", differentiable=True)
+        mean = (total / float(B * F * self.V * 3)).to(torch.float32)
+        return mean[0], mean[1]
+
+    def terms(self, m_ref, m_rst, gen_m_rst=None, attr=None, subjects=None, grad: Optional[bool] = None):
+        """feature rows [B,F,333] -> (rec_vtex_displacement, gen_vtex_displacement): SmoothL1 means over B F V 3, float32 scalars on the device, no gradient
+        (grad, default the constructor's: with gradient, see _terms_grad); gen is 0 without a generation (a CPU run has no in-loop sampler)."""
+        if self.grad if grad is None else grad:
+            return self._terms_grad(m_ref, m_rst, gen_m_rst, attr, subjects)
         with torch.no_grad():
             B, F = int(m_ref.shape[0]), int(m_ref.shape[1])
             subjects = self.subjects(attr) if subjects is None else subjects

@@ -9,32 +9,11 @@
 #include "../../include/amuse_hip.h"
 #include "amuse_body.hpp"
 #include "amuse_body_pack.hpp"
-
-__attribute__((visibility("hidden"), format(printf, 2, 3))) int amuse_failf(int code, const char* fmt, ...);
-#define fail(...) amuse_failf(__VA_ARGS__)
-#define HIP_TRY(expr)                                                                                   \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess) return fail(AMUSE_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
+#include "amuse_body_bwd.hpp"
+#include "amuse_body_host.hpp"
 
 using namespace amuse;
 namespace ab = amuse_body;
-
-struct amuse_body_ctx {
-    int device = 0;
-    int V = 0, groups = 0, n_betas = 0, nnz = 0, shift = 0, S = 0;
-    std::vector<float> v_template, shapedirs, Jreg;   // host copies for amuse_body_set_subjects
-    signed char parents[56];
-    uint16_t *pd_hi = nullptr, *pd_lo = nullptr;
-    void* skin = nullptr;
-    float *v_shaped = nullptr, *J = nullptr;
-    // workspace for `cap` frames (a multiple of 16) x kBodyMaxSets motion sets
-    size_t cap = 0;
-    float *A = nullptr, *tr = nullptr, *partials = nullptr;
-    uint16_t* pf = nullptr;   // [sets][hi | lo][cap * 512]
-    std::vector<void*> retired;   // workspaces outgrown by a later call: kept until destroy, a graph captured earlier still replays into them
-};
 
 namespace {
 void retire_ws(amuse_body_ctx* c) {
@@ -44,17 +23,31 @@ void retire_ws(amuse_body_ctx* c) {
     c->pf = nullptr;
     c->cap = 0;
 }
+int reserve_grad(amuse_body_ctx* c, size_t need) {   // the backward partials: tiles * bwd_chunks(tiles) <= tiles + 512 workgroups
+    if (!c->grad || need <= c->gcap) return 0;
+    for (void* p : {(void*)c->dA_part, (void*)c->dpf_part})
+        if (p) c->retired.push_back(p);
+    c->dA_part = c->dpf_part = nullptr;
+    c->gcap = 0;
+    const size_t wgs = ab::bwd_partial_workgroups(need);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipMalloc((void**)&c->dA_part, wgs * 16 * kBodyDAStride * sizeof(float)));
+    HIP_TRY(hipMalloc((void**)&c->dpf_part, wgs * kBodyDpfFloats * sizeof(float)));
+    c->gcap = need;
+    return 0;
+}
 int reserve(amuse_body_ctx* c, size_t frames) {
     const size_t need = (frames + 15) / 16 * 16;
-    if (need <= c->cap) return 0;
-    retire_ws(c);
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipMalloc((void**)&c->A, kBodyMaxSets * need * kBodyAFloats * sizeof(float)));
-    HIP_TRY(hipMalloc((void**)&c->tr, kBodyMaxSets * need * 4 * sizeof(float)));
-    HIP_TRY(hipMalloc((void**)&c->pf, kBodyMaxSets * 2 * need * ab::kPoseK * sizeof(uint16_t)));
-    HIP_TRY(hipMalloc((void**)&c->partials, (need / 16 + 1025) * 2 * sizeof(float)));   // tiles * skin_chunks(tiles) <= tiles + 1024
-    c->cap = need;
-    return 0;
+    if (need > c->cap) {
+        retire_ws(c);
+        HIP_TRY(hipSetDevice(c->device));
+        HIP_TRY(hipMalloc((void**)&c->A, kBodyMaxSets * need * kBodyAFloats * sizeof(float)));
+        HIP_TRY(hipMalloc((void**)&c->tr, kBodyMaxSets * need * 4 * sizeof(float)));
+        HIP_TRY(hipMalloc((void**)&c->pf, kBodyMaxSets * 2 * need * ab::kPoseK * sizeof(uint16_t)));
+        HIP_TRY(hipMalloc((void**)&c->partials, (need / 16 + 1025) * 2 * sizeof(float)));   // tiles * skin_chunks(tiles) <= tiles + 1024
+        c->cap = need;
+    }
+    return reserve_grad(c, c->cap);
 }
 struct SetPtrs { float *A, *tr; uint16_t *pf_hi, *pf_lo; };
 SetPtrs set_ptrs(const amuse_body_ctx* c, int s) {
@@ -93,6 +86,12 @@ void skin_args(const amuse_body_ctx* c, BodySkinArgs& a, const int* subject_dev,
     a.vertices_out = nullptr; a.partials = c->partials;
 }
 }  // namespace
+
+int amuse_body_reserve_ws(amuse_body_ctx* c, size_t frames) { return reserve(c, frames); }
+int amuse_body_check_call(const amuse_body_ctx* c, const int* subject_dev, int N, int F, int precision, int rot_kind) { return check_call(c, subject_dev, N, F, precision, rot_kind); }
+int amuse_body_pose_rows6d(const amuse_body_ctx* c, int s, const float* rows, const int* subject_dev, int nframes, int F, void* stream) {
+    return pose_set(c, s, rows, 333, rows + 330, 333, AMUSE_BODY_ROT_6D, subject_dev, nframes, F, nullptr, static_cast<hipStream_t>(stream));
+}
 
 extern "C" {
 
@@ -141,7 +140,7 @@ void amuse_body_destroy(amuse_body_ctx* c) {
     if (!c) return;
     retire_ws(c);
     for (void* p : c->retired) (void)hipFree(p);
-    for (void* p : {(void*)c->pd_hi, (void*)c->pd_lo, c->skin, (void*)c->v_shaped, (void*)c->J})
+    for (void* p : {(void*)c->pd_hi, (void*)c->pd_lo, c->skin, (void*)c->v_shaped, (void*)c->J, (void*)c->pt_hi, (void*)c->pt_lo, (void*)c->dA_part, (void*)c->dpf_part})
         if (p) (void)hipFree(p);
     delete c;
 }
@@ -216,6 +215,7 @@ int amuse_body_info(const amuse_body_ctx* c, int what) {
         case 1: return c->nnz;
         case 2: return c->shift;
         case 3: return c->S;
+        case 4: return c->grad;
         default: return fail(AMUSE_EINVAL, "amuse_body_info: what %d", what);
     }
 }

@@ -145,6 +145,52 @@ inline void shape_subject(int V, int n_betas, const float* v_template, const flo
     }
 }
 
+// ---- gradients: the transposed image.  The backward kernel's second product sums over the vertices: dpf[feature][frame] = sum_k Pt[feature][k] dp[k][frame] with
+// k = (vertex-in-group, group parity, coordinate | pad) of a PAIR of consecutive vertex groups - the order in which the forward product's accumulators of two
+// groups already sit in a lane.  Unit (pair, feature tile of 16) = 64 lanes x 8 halfs: lane (kg = vertex & 3, row = feature & 15) holds, at element
+// j = 4 (group & 1) + c, the SAME hi | lo halfs as the forward planes hold for posedirs[feature][vertex * 3 + c] (same pre-scale).  512 feature rows (486 + pad).
+// Size: pairs * 32 * 512 halfs per plane = pairs * 65,536 bytes for hi + lo: 85,852,160 bytes at V = 10,475 (1,310 pairs).
+inline int vertex_pairs(int V) { return (vertex_groups(V) + 1) / 2; }
+inline size_t posedirs_t_index(int v, int c, int k) {
+    const int group = v >> 2, q = group >> 1, ft = k >> 4;
+    return ((((size_t)q * 32 + ft) * 64) + (size_t)((v & 3) * 16 + (k & 15))) * 8 + (size_t)((group & 1) * 4 + c);
+}
+inline size_t posedirs_t_plane_halfs(int V) { return (size_t)vertex_pairs(V) * 32 * 64 * 8; }
+
+// from the dense matrix (the definition; tests) ...
+inline void pack_posedirs_t(const float* pd, int V, int shift, std::vector<uint16_t>& hi, std::vector<uint16_t>& lo) {
+    const size_t n = posedirs_t_plane_halfs(V);
+    hi.assign(n, 0);
+    lo.assign(n, 0);
+    const float s = ldexpf(1.f, shift);
+    for (int k = 0; k < kPoseFeat; ++k) {
+        const float* row = pd + (size_t)k * V * 3;
+        for (int v = 0; v < V; ++v)
+            for (int c = 0; c < 3; ++c) {
+                const float x = row[(size_t)v * 3 + c] * s;
+                const uint16_t h = f2h(x);
+                const size_t i = posedirs_t_index(v, c, k);
+                hi[i] = h;
+                lo[i] = f2h(x - h2f(h));
+            }
+    }
+}
+// ... and from a forward plane (what amuse_body_enable_grad does: the context keeps no dense copy of posedirs; the halfs are the forward image's, bit for bit)
+inline void transpose_posedirs_plane(const uint16_t* fwd, int V, std::vector<uint16_t>& out) {
+    out.assign(posedirs_t_plane_halfs(V), 0);
+    for (int v = 0; v < V; ++v)
+        for (int c = 0; c < 3; ++c)
+            for (int k = 0; k < kPoseFeat; ++k) out[posedirs_t_index(v, c, k)] = fwd[posedirs_index(v, c, k)];
+}
+
+// chunks of vertex-group pairs per frame tile (grid.y of the backward skinning kernel): one 8-wave workgroup per CU fits, so ~2 per CU, at least one pair per wave
+inline int bwd_chunks(int tiles, int pairs) {
+    int c = (512 + tiles - 1) / tiles, cmax = pairs / 8;
+    if (c > cmax) c = cmax;
+    return c < 1 ? 1 : c;
+}
+inline size_t bwd_partial_workgroups(size_t frames16) { return frames16 / 16 + 512; }   // tiles * bwd_chunks(tiles, .) <= tiles + 511
+
 // chunks of vertex groups per frame tile (grid.y of the skinning kernel): enough workgroups to fill the chip, each with at least one group per wave
 inline int skin_chunks(int tiles, int groups) {
     int c = (1024 + tiles - 1) / tiles, cmax = groups / 8;

@@ -136,6 +136,8 @@ def train_gesture_entry(args, dirname: Path, config: dict):
             raise SystemExit(f"train_gesture: TRAIN_PARAM.wav_dtw_mfcc.ablation_version is {version!r}: the vertex-displacement terms know the dataset versions "
                              "v0 (male / female body model by the actor) and v1 (neutral), as latent_losses.py:184-199 does")
         argv += ["--smplx-models", str(smplx_dir), "--dataset-version", version]
+        if args.vtex_grad:
+            argv += ["--vtex-grad"]
     print(f"Experiment init: AMUSE, fn: train_gesture, time: {time.asctime()}")
     try:
         return train_gesture.main(argv)
@@ -214,12 +216,17 @@ def main(argv=None):
     ap.add_argument("--iters-per-epoch", type=int, default=None, help="train_gesture --synthetic: iterations per epoch")
     ap.add_argument("--skip-vtex-loss", action="store_true", help="train_gesture: train without the two vertex-displacement loss terms when the "
                                                                   "configuration asks for them (they need the SMPL-X body models)")
+    ap.add_argument("--vtex-grad", action="store_true", help="train_gesture: the vertex-displacement terms carry gradient to the decoder (needs --smplx-models); a "
+                                                             "deviation from the reference, whose vertices are computed under no_grad (latent_losses.py:173)")
     ap.add_argument("--smplx-models", default=None, help="train_gesture: directory holding SMPLX_MALE.npz, SMPLX_FEMALE.npz, SMPLX_NEUTRAL.npz for the vertex-displacement "
                                                          "loss terms (default: <root>/body_models/codebase/models/smplx, the reference's path)")
     args = ap.parse_args(argv)
     fn = args.fn[0]
     if fn not in ("infer_gesture", "edit_gesture", "train_gesture"):
         raise SystemExit(f"--fn {fn}: infer_gesture, edit_gesture and train_gesture run on this path")
+    if args.vtex_grad and (fn != "train_gesture" or not args.smplx_models):
+        raise SystemExit("--vtex-grad belongs to --fn train_gesture and needs --smplx-models DIR: the vertex-displacement terms it differentiates are built from the "
+                         "SMPL-X body models")
     tic = time.time()
     dirname = Path(args.root) if args.root else Path.cwd().parent
     config, ldm_cfg = load_config(dirname, fn, args.cfg)

@@ -77,16 +77,20 @@ class LatentPriorLosses:
     """Stage / version / lambdas of the loss config select the terms exactly as latent_losses.py:36-98 does; update()
     returns the weighted total of one iteration and accumulates the un-weighted terms, compute() averages them."""
 
-    def __init__(self, cfg: Optional[dict] = None, device="cpu", body=None):
+    def __init__(self, cfg: Optional[dict] = None, device="cpu", body=None, vtex_grad: bool = False):
         """body: amuse_amd.body.BodyLosses (the SMPL-X models the reference's trainer loads, trainer.py:94-104) - needed by vtex_displacement: True, which adds
         rec_vtex_displacement / gen_vtex_displacement as latent_losses.py:135-146 does: SmoothL1 on the vertices of (reconstruction, batch) and (generation, batch),
         weight LAMBDA_REC, part of `total`, NO gradient (_get_vertices runs under no_grad).  Deviation, stated: the vertices are posed from the 6D feature rows
-        the trainer already has, not from their matrix -> axis-angle -> matrix round trip (identity up to fp32 rounding; tests/test_body_host_cpu.py)."""
+        the trainer already has, not from their matrix -> axis-angle -> matrix round trip (identity up to fp32 rounding; tests/test_body_host_cpu.py).
+        vtex_grad: OPT-IN DEVIATION from the reference - the two vertex terms carry gradient (to m_rst; to gen_m_rst where that requires grad) through the
+        skinning backward pass (body.VertexLossFn on a GPU, autograd of the float64 twin on the CPU), so the term shapes the motion prior instead of adding a
+        constant to `total`.  Off: the reference's no_grad values, bit for bit as before."""
         c = dict(LOSS_CFG)
         c.update((cfg or {}).get("losses", cfg or {}))
         if c.get("vtex_displacement") and body is None:
             raise NotImplementedError("vertex-displacement losses need the SMPL-X body models (trainer.py:91-104): pass body=amuse_amd.body.BodyLosses(...)")
         self.body = body if c.get("vtex_displacement") else None
+        self.vtex_grad = bool(vtex_grad) and self.body is not None
         if self.body is not None and c["stage"] != "vae_diffusion":
             raise ValueError(f"vtex_displacement loss is only in vae_diffusion, but {c['stage']}")   # latent_losses.py:33
         self.cfg, self.d = c, device
@@ -150,9 +154,14 @@ class LatentPriorLosses:
             else:
                 total = total + self._update_loss("latent_feature", rs_set["lat_rm"], rs_set["lat_m"])
             if self.body is not None:       # values only; accumulated in place on the device (a captured step replays these launches)
-                rec, gen = self.body.terms(rs_set["m_ref"], rs_set["m_rst"], rs_set.get("gen_m_rst"), rs_set.get("attr"), rs_set.get("subjects"))
-                self.sums["rec_vtex_displacement"] += rec
-                self.sums["gen_vtex_displacement"] += gen
+                if self.vtex_grad:          # opt-in: the terms carry gradient (see __init__)
+                    rec, gen = self.body.terms(rs_set["m_ref"], rs_set["m_rst"], rs_set.get("gen_m_rst"), rs_set.get("attr"), rs_set.get("subjects"), grad=True)
+                    self.sums["rec_vtex_displacement"] += rec.detach()
+                    self.sums["gen_vtex_displacement"] += gen.detach()
+                else:
+                    rec, gen = self.body.terms(rs_set["m_ref"], rs_set["m_rst"], rs_set.get("gen_m_rst"), rs_set.get("attr"), rs_set.get("subjects"))
+                    self.sums["rec_vtex_displacement"] += rec
+                    self.sums["gen_vtex_displacement"] += gen
                 total = total + self.cfg["LAMBDA_REC"] * (rec + gen)
         self.sums["total"] += total.detach()
         self.count += 1
@@ -209,7 +218,8 @@ class GestureTrainer:
 
     def __init__(self, prior: MotionPrior, ldm: LatentDiffusionTrainModule, device, lr: float = 1e-4, loss_cfg: Optional[dict] = None,
                  inner_sampler: Optional[Callable] = None, process_group=None, world: int = 1, kind: Optional[str] = None,
-                 grads_mode: str = "steal", sampler_stream: bool = True, optimizer: str = "flat", denoiser_stream: bool = True, body=None):
+                 grads_mode: str = "steal", sampler_stream: bool = True, optimizer: str = "flat", denoiser_stream: bool = True, body=None,
+                 vtex_grad: bool = False):
         self.model = {"prior": prior.to(device), "ldm": ldm.to(device)}
         # torch.distributions.Normal validates its arguments with blocking device -> host reads (6 per iteration: the host then waits for the previous
         # iteration's backward + optimizer step before it dispatches anything of the next, tools/probes/train_host/sync_points.py).  Off on the GPU
@@ -217,7 +227,7 @@ class GestureTrainer:
         if torch.device(device).type == "cuda" and os.environ.get("AMUSE_TRAIN_VALIDATE", "0") != "1":
             prior.validate_args = False
         self.device = torch.device(device)
-        self.lpdm_losses = LatentPriorLosses(loss_cfg, self.device, body=body)
+        self.lpdm_losses = LatentPriorLosses(loss_cfg, self.device, body=body, vtex_grad=vtex_grad)
         self.inner_sampler = inner_sampler      # (con, emo, sty, bsz) -> noise2feats (B,300,333) or None
         self.world, self.pg = world, process_group
         self.kind = kind                        # ablation variant of the LMDB id (trainer.py:393-399): full / emotion / identity
@@ -406,6 +416,10 @@ class GestureTrainer:
         static["ld_attr"] = batch.get("ld_attr")
         if self.lpdm_losses.body is not None:        # the gendered split as device data: a replay follows the new batch's actors
             static["ld_subjects"] = self.lpdm_losses.body.subjects(batch["ld_attr"])
+            if self.lpdm_losses.vtex_grad:           # the transposed posedirs image and the backward partials exist before the capture begins
+                for e in self.lpdm_losses.body.engines.values():
+                    e.enable_grad()
+                    e.reserve(int(static["ld_motion"].shape[0]) * int(static["ld_motion"].shape[1]))
         lib = train_ops._st(self.device)["lib"]
         self.lpdm_opt.push_step()
         count0 = self.lpdm_losses.count
@@ -717,7 +731,7 @@ def ablation_kind(lmdb_id: Optional[str]) -> Optional[str]:
 def build_trainer(device, rank: int = 0, world: int = 1, process_group=None, seed: int = 0, use_hip_sampler: bool = True,
                   dropout: float = 0.1, sampler_refresh: int = 1, ldm_cfg: Optional[dict] = None, lr: float = 1e-4,
                   kind: Optional[str] = None, inner: Optional[str] = None, grads_mode: str = "steal", sampler_stream: bool = True,
-                  optimizer: str = "flat", denoiser_stream: bool = True, body=None) -> GestureTrainer:
+                  optimizer: str = "flat", denoiser_stream: bool = True, body=None, vtex_grad: bool = False) -> GestureTrainer:
     """Random-init prior + ldm (the deterministic weights of amuse_amd/weights.py, identical on every rank - what DDP's
     initial broadcast gives the reference's DataParallel-less single-GPU run) and the trainer around them.
     lr = TRAIN_PARAM.latent_diffusion.lr_base (trainer.py:181-184); ldm_cfg = configs/<arch>.json merged with diff_o.yaml (its
@@ -735,7 +749,7 @@ def build_trainer(device, rank: int = 0, world: int = 1, process_group=None, see
         loss_cfg = dict(loss_cfg or LOSS_CFG, vtex_displacement=True)
     tr = GestureTrainer(prior, ldm, device, lr=lr, loss_cfg=loss_cfg, inner_sampler=None, process_group=process_group,
                         world=world, kind=None if kind == "full" else kind, grads_mode=grads_mode, sampler_stream=sampler_stream, optimizer=optimizer, denoiser_stream=denoiser_stream,
-                        body=body)
+                        body=body, vtex_grad=vtex_grad)
     inner = inner or os.environ.get("AMUSE_TRAIN_INNER", "eval")
     if inner not in ("eval", "train", "train-hip", "train-hip-decode"):
         raise ValueError(f"inner sampler {inner!r}: 'eval' (the persistent HIP sampler kernel, default), 'train' (the reference's train-mode semantics, dropout "
@@ -883,7 +897,12 @@ def main(argv=None):
                                                          "loss terms (TRAIN_PARAM.latent_diffusion.vtex_displacement); default: without them")
     ap.add_argument("--dataset-version", default="v0", choices=["v0", "v1"], help="wav_dtw_mfcc.ablation_version: v0 poses every clip through the male / female body "
                                                                                   "model of its actor, v1 through the neutral one (only with --smplx-models)")
+    ap.add_argument("--vtex-grad", action="store_true", help="let the two vertex-displacement terms carry GRADIENT to the decoder through the skinning backward pass "
+                                                             "(needs --smplx-models).  A deviation from the reference, which computes its vertices under no_grad "
+                                                             "(latent_losses.py:173): there the terms only add a constant to the total")
     args = ap.parse_args(argv)
+    if args.vtex_grad and not args.smplx_models:
+        raise SystemExit("--vtex-grad needs --smplx-models DIR: the vertex-displacement terms it differentiates are built from the SMPL-X body models")
     from . import launch
     if args.gpus > 1 and not launch.launched_by_torchrun():
         return launch.run_ranks("amuse_amd.train_gesture", list(sys.argv[1:] if argv is None else argv), args.gpus, module=True)
@@ -914,11 +933,14 @@ def main(argv=None):
     body = None
     if args.smplx_models:
         from . import body as body_mod
-        body = body_mod.BodyLosses(body_mod.load_models(args.smplx_models), device, version=args.dataset_version)
+        body = body_mod.BodyLosses(body_mod.load_models(args.smplx_models), device, version=args.dataset_version, grad=args.vtex_grad)
         if rank == 0:
             print(f"[LPDM-T] vertex-displacement losses ON: SMPL-X models from {args.smplx_models} (V = {body.V}, dataset version {args.dataset_version})", flush=True)
+            if args.vtex_grad:
+                print("[LPDM-T] --vtex-grad: the vertex-displacement terms CARRY GRADIENT to the decoder (skinning backward pass).  This DEVIATES from the reference, "
+                      "which computes its vertices under no_grad (latent_losses.py:173)", flush=True)
     tr = build_trainer(device, rank, world, process_group=pg, use_hip_sampler=device.type == "cuda", ldm_cfg=ldm_cfg, lr=args.lr, kind=kind,
-                       inner=args.inner_sampler, body=body)
+                       inner=args.inner_sampler, body=body, vtex_grad=args.vtex_grad)
     tr.use_graph = device.type == "cuda" and not args.no_graph
     if rank == 0:
         lc = tr.lpdm_losses.cfg

@@ -570,7 +570,7 @@ int amuse_train_linear_fwd(const float* x, const float* W, const float* b, long 
 int amuse_train_linear_bwd(const float* dy, const float* x, const float* W, long rows, int K, int N, float* dW, float* db, float* dx,
                            int accumulate_dx, float* ws, void* stream);
 
-/* ------------------------------------------------------------------ SMPL-X body model (csrc/amuse_body.hip, k_body.hip; amuse_amd/body.py)
+/* ------------------------------------------------------------------ SMPL-X body model (csrc/amuse_body.hip, k_body.hip, amuse_body_grad.hip, k_body_bwd.hip; amuse_amd/body.py)
  * Replaces what the reference gets from the `smplx` package in LatentPriorLosses._get_vertices (models/latent_diffusion/utils/latent_losses.py:135-146,173-250):
  * SMPLX(num_betas = n_betas, use_pca=False, flat_hand_mean=True) called with expression = 0 - linear blend skinning, generic in the vertex count - and the two
  * vertex-displacement terms built on it.  A context of its own, independent of amuse_ctx; the arrays are what a user loads from their own SMPLX_*.npz.
@@ -623,7 +623,29 @@ int amuse_body_forward(amuse_body_ctx* ctx, const float* rot, int rot_kind, cons
  * fp32 partials, then a fixed-order double sum in a second launch; no float atomics. */
 int amuse_body_vertex_loss(amuse_body_ctx* ctx, const float* ref, const float* a, const float* b, int rot_kind, const int* subject_dev, int N, int F,
                            int precision, double* sums_out, void* stream);
-/* diagnostics (host values): what = 0 V, 1 largest non-zero count of a skinning row, 2 the power-of-two pre-scale exponent of posedirs, 3 subjects set */
+/* Gradients of the vertex objective (csrc/amuse_body_grad.hip, k_body_bwd.hip).  OPT-IN: the reference computes its vertices under no_grad
+ * (latent_losses.py:173) and the calls above are its values; nothing of them changes when gradients are enabled.
+ * amuse_body_enable_grad builds and uploads a second packed image of posedirs, TRANSPOSED (512 feature rows x the padded vertex slots of a pair of vertex
+ * groups, hi | lo planes, the forward image's halfs bit for bit), which the backward pass's transposed pose-blend product reads: pairs x 65,536 bytes with
+ * pairs = ceil(ceil(V / 4) / 2), i.e. 85,852,160 bytes at V = 10,475.  A context that never calls it keeps the memory it had.  From then on the workspace
+ * (amuse_body_reserve, or a call's own sizing) also holds the backward kernels' per-workgroup partials: (frames16 / 16 + 512) x 75,264 bytes.
+ * Not stream-ordered (it copies synchronously and allocates): call it between the context's calls and BEFORE any capture.  Idempotent. */
+int amuse_body_enable_grad(amuse_body_ctx* ctx);
+/* d/d(a), d/d(b) of the SmoothL1 (beta 1) SUMS amuse_body_vertex_loss returns: grad_a / grad_b dev [N][F][333] = scale_a x dS_a/da, scale_b x dS_b/db (the
+ * 330 6D columns and the three translation columns); the reference motion gets no gradient.  b and grad_b are NULL together.  Rows of skipped clips (subject
+ * outside 0..S-1) are left untouched.  SmoothL1's derivative clamp(d, -1, 1) is continuous, so no input has to avoid |d| = 1.
+ * rot_kind must be AMUSE_BODY_ROT_6D: axis-angle rows return AMUSE_EINVAL, because the published Rodrigues form (angle = |r + 1e-8|) has no usable derivative
+ * at the zero vector, which rest poses contain.  AMUSE_ESTATE before amuse_body_enable_grad.
+ * The forward pass of the reference and one candidate per pass is recomputed (same fragments and precision as amuse_body_vertex_loss; `precision` also
+ * selects split-fp16 or one-product fp16 for the transposed product), no vertex is written.  Deterministic - the same inputs give the same bits: the skinning
+ * gradients accumulate as int64 fixed point (value x 2^38; integer sums do not depend on arrival order) in LDS, the matrix-core accumulators of a workgroup's
+ * waves are added in wave order, and a per-frame kernel adds the per-workgroup partials in index order in double.  No float atomics.
+ * Workspace rules as for amuse_body_reserve: after a reserve (made after amuse_body_enable_grad) that covers the call it allocates nothing and synchronises
+ * nothing; growing never frees what an earlier graph may replay into. */
+int amuse_body_vertex_loss_grad(amuse_body_ctx* ctx, const float* ref, const float* a, const float* b, int rot_kind, const int* subject_dev, int N, int F,
+                                int precision, float scale_a, float scale_b, float* grad_a, float* grad_b, void* stream);
+/* diagnostics (host values): what = 0 V, 1 largest non-zero count of a skinning row, 2 the power-of-two pre-scale exponent of posedirs, 3 subjects set,
+ * 4 gradients enabled (0 | 1) */
 int amuse_body_info(const amuse_body_ctx* ctx, int what);
 
 #ifdef __cplusplus

@@ -1,7 +1,8 @@
 """Cost of the SMPL-X body-model kernels on the GPU (csrc/k_body.hip) -> profiles/body_cost.txt.  HIP events, 20 calls per cell, precisions alternating:
   vertex_loss at the training shape (32 x 300 frames, three motion sets, synthetic V = 10,475 model) in fp32x and fp16, beside the pose-blend product's FLOPs
   forward, joints only, at 256 x 300 frames
-  train_gesture it/s with the vertex terms on against the same trainer without them, in the same job
+  vertex_loss_grad (the skinning backward pass, csrc/k_body_bwd.hip) at the training shape, reference + one candidate, beside the two-set loss call of the same run
+  train_gesture it/s with the vertex terms on, with them on AND carrying gradient (--vtex-grad), and without them, in the same job
 usage: python tools/gpu_body_cost.py [out file]"""
 import sys
 import time
@@ -68,6 +69,28 @@ def main():
     for p, k in (("fp32x", 3), ("fp16", 1)):
         a = np.array(t[p])
         lines.append(f"  {p:6s} {np.median(a):8.3f} ({a.min():.3f}) ms   {100 * k * flop / (np.median(a) * 1e-3) / PEAK16:.1f} % of the 16-bit MFMA peak")
+    # the gradient call: 6D feature rows, reference + one candidate (what the trainer's backward pass runs), beside the two-set loss call measured in the same loop
+    rows6 = [(0.1 * torch.randn(N, F, 333, generator=g)).to(DEV) for _ in range(2)]
+    for r in rows6:
+        r[..., 0:330:6] += 1.0   # near-identity 6D rows: a1 ~ x, a2 ~ y
+        r[..., 4:330:6] += 1.0
+    gout = (torch.zeros(N, F, 333, device=DEV), None)
+    for label, e in (("with the dense rows", eng), ("without the dense rows", eng2)):
+        e.enable_grad()
+        e.reserve(N * F)
+        for p in ("fp32x", "fp16"):
+            e.vertex_loss_grad(rows6[0], rows6[1], None, sub, out=gout, precision=p)
+            e.vertex_loss(rows6[0], rows6[1], None, sub, "6d", out=res, precision=p)
+        torch.cuda.synchronize()
+        tg, tl = {"fp32x": [], "fp16": []}, {"fp32x": [], "fp16": []}
+        for _ in range(20):
+            for p in tg:
+                tg[p].append(timed(lambda: e.vertex_loss_grad(rows6[0], rows6[1], None, sub, out=gout, precision=p), 1)[0])
+                tl[p].append(timed(lambda: e.vertex_loss(rows6[0], rows6[1], None, sub, "6d", out=res, precision=p), 1)[0])
+        lines.append(f"vertex_loss_grad  {N} x {F} frames, reference + 1 candidate, {label} (lists of {e.info()['skin_nnz']}); vertex_loss of the same two sets in the same loop:")
+        for p in tg:
+            a, b = np.array(tg[p]), np.array(tl[p])
+            lines.append(f"  {p:6s} grad {np.median(a):8.3f} ({a.min():.3f}) ms   loss {np.median(b):8.3f} ({b.min():.3f}) ms   grad / loss = {np.median(a) / np.median(b):.2f}")
     eng2.close()
     N2 = 256
     rot, tr = (0.3 * torch.randn(N2, F, 55, 3, generator=g)).to(DEV), torch.randn(N2, F, 3, generator=g).to(DEV)
@@ -79,9 +102,9 @@ def main():
     # the training step with and without the terms (graphs on, batch 32, synthetic data)
     from amuse_amd.train_gesture import build_trainer, synthetic_batch
     models = {k: model for k in ("male", "female")}
-    for label, with_body in (("vertex terms ON ", True), ("vertex terms off", False)):
-        bl = body.BodyLosses(models, DEV, "v0") if with_body else None
-        trn = build_trainer(DEV, body=bl)
+    for label, with_body, vg in (("vertex terms ON ", True, False), ("vertex terms ON, --vtex-grad", True, True), ("vertex terms off", False, False)):
+        bl = body.BodyLosses(models, DEV, "v0", grad=vg) if with_body else None
+        trn = build_trainer(DEV, body=bl, vtex_grad=vg)
         batches = [dict(synthetic_batch(32, i, DEV), ld_attr=[("scott", "male"), ("miranda", "female")] * 16) for i in range(4)]
         for i in range(4):
             trn.train_step(batches[i])

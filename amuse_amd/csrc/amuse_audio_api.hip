@@ -1,65 +1,68 @@
-// C ABI of the audio front-end (include/amuse_hip.h, "Audio front-end"): context, bf16 weight images, workspace and
-// the launch sequence of one AST encoder.  Host code only - kernels live in k_audio.hip.
+// C ABI of the audio front-end (include/amuse_hip.h, "Audio front-end"): the context, and the bf16 mode of the AST encoder described in amuse_audio_enc.hpp -
+// what it uploads for a parameter and how an operand becomes the arguments of the kernels of k_audio.hip / k_audio_gemm.hip.  Host code only.
 #include <hip/hip_runtime.h>
 
-#include <cstdio>
-#include <cstring>
 #include <vector>
 
-#include "../../include/amuse_hip.h"
-#include "amuse_audio.hpp"
+#include "amuse_audio_enc.hpp"
 #include "amuse_audio_tail.hpp"
 #include "amuse_audio_x.hpp"
 
 using namespace amuse;
 
-int amuse_fail_msg(int code, const char* msg);   // amuse_api.hip: the library's thread-local error slot
 // The parity mode (AMUSE_PREC_F32X) lives in amuse_audio_x.hip and is reached through this WEAK reference only: where that unit is not linked (the host-only
 // build of tests/host_asan, whose stub defines the bf16 launchers alone) the address is null and amuse_audio_set_precision refuses the mode.
-extern "C" const amuse::AudioXOps* amuse_audio_x_ops(void) __attribute__((weak));
+extern "C" const amuse::AudioModeOps* amuse_audio_x_ops(void) __attribute__((weak));
 // AST_EVP's tail (classifier heads, fusion, decoder: amuse_audio_tail.hip) is reached the same way: without that unit amuse_audio_set_tail, amuse_audio_reconstruct
 // and the labels of amuse_audio_encode_labels return AMUSE_ESTATE.
 extern "C" const amuse::AudioTailOps* amuse_audio_tail_ops(void) __attribute__((weak));
 
+#define HIP_TRY(expr) HIP_TRY_P("", expr)   // (this unit's messages carry no prefix)
+
 namespace {
 
-int failf(int code, const char* fmt, const char* a = "", long b = 0, long c = 0) {
-    char buf[400];
-    snprintf(buf, sizeof(buf), fmt, a, b, c);
-    return amuse_fail_msg(code, buf);
-}
-#define HIP_TRY(expr)                                                                            \
-    do {                                                                                         \
-        hipError_t e_ = (expr);                                                                  \
-        if (e_ != hipSuccess) return failf(AMUSE_EHIP, "%s (line %ld)", hipGetErrorString(e_), __LINE__); \
-    } while (0)
-
-unsigned short f2bf(float f) {  // round-to-nearest-even, as v_cvt_pk_bf16_f32
-    uint32_t x;
-    memcpy(&x, &f, 4);
-    if ((x & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((x >> 16) | 0x40);
-    x += 0x7fffu + ((x >> 16) & 1u);
-    return (unsigned short)(x >> 16);
+// torch Linear weight [N][K] fp32 -> the GEMM's fragment order (amuse_audio.hpp GemmArgs::W), bf16
+void pack_w(const float* W, int N, int K, unsigned short* out) {
+    for_each_fragment_lane(N, K, [&](size_t u, int lane, size_t s) {
+        for (int e = 0; e < 8; ++e) out[(u * 64 + lane) * 8 + e] = f2bf(W[s + e]);
+    });
 }
 
-struct Block {
-    float *n1w, *n1b, *n2w, *n2b, *qkv_b, *proj_b, *fc1_b, *fc2_b;
-    unsigned short *qkv_w, *proj_w, *fc1_w, *fc2_w;
+struct Bf16Mode {
+    static constexpr int planes = 1;
+    static constexpr const char* err_prefix = "";
+    struct Scratch { std::vector<unsigned short> img; };
+    // GEMM weights fragment-packed bf16, the feature head's weight plain bf16 [256][768]
+    static int put(AstState<Bf16Mode>* c, void* slot, const float* src, const AstParam& p) {
+        const size_t n = (size_t)p.rows * p.cols;
+        if (p.kind == PK_F32) return c->up.up(slot, src, n * 4);
+        std::vector<unsigned short>& h = c->scratch.img;
+        h.resize(n);
+        if (p.kind == PK_GEMM_W) pack_w(src, p.rows, p.cols, h.data());
+        else for (size_t i = 0; i < n; ++i) h[i] = f2bf(src[i]);
+        return c->up.up(slot, h.data(), n * 2);
+    }
+    static hipError_t im2col(const float* fbank, Operand P, int nb, hipStream_t st) { return launch_im2col(fbank, P.hi, nb, st); }
+    static hipError_t ln(const float* X, const float* gamma, const float* beta, float eps, Operand out, int M, hipStream_t st) {
+        return launch_ln_bf16(X, gamma, beta, eps, out.hi, M, st);
+    }
+    static hipError_t gemm(int epi, Operand A, const unsigned short* W, const float* bias, int M, int N, int K, Operand out, float* out_f32, const float* pos, Operand vt,
+                           hipStream_t st) {
+        GemmArgs g{};
+        g.A = A.hi; g.W = W; g.bias = bias; g.M = M; g.N = N; g.K = K; g.out_bf16 = out.hi; g.out_f32 = out_f32; g.pos = pos; g.vt = vt.hi;
+        return launch_gemm(g, epi, st);
+    }
+    static hipError_t attn(Operand QK, Operand Vt, Operand O, int nb, hipStream_t st) { return launch_ast_attn(QK.hi, Vt.hi, O.hi, nb, st); }
+    static hipError_t head(const float* pooled, int frame_based, const Encoder& E, float* out, int nb, hipStream_t st) {
+        return launch_ast_head(pooled, frame_based, E.fh_ln_w, E.fh_ln_b, static_cast<const unsigned short*>(E.fh_w), E.fh_b, out, nb, st);
+    }
 };
-struct Encoder {
-    float *cls, *dist, *pos, *patch_b, *norm_w, *norm_b, *fh_ln_w, *fh_ln_b, *fh_b;
-    unsigned short *patch_w, *fh_w;
-    Block blk[kAstLayers];
-};
+
 constexpr int kChunk = 32;   // clips per pass over the network (about 22 MB of workspace per clip)
-// amuse_audio_features runs the three encoders (independent networks over the same fbank) concurrently, each on its own
-// stream and workspace: at small batches one encoder's launches leave most of the chip idle (10 row tiles of 128 tokens per
-// clip against 512 persistent workgroup slots), at large ones the other encoders' work fills the tail of every launch.
-// activations of one encoder pass over `cap` clips
-struct Workspace {
-    int cap = 0;
-    float *X = nullptr, *pooled = nullptr;
-    unsigned short *H = nullptr, *QK = nullptr, *Vt = nullptr, *O = nullptr, *F = nullptr, *P = nullptr;
+// One mode of the encoders: its functions and what they built.  [0] bf16, built by amuse_audio_create; [1] fp32x, built on the first switch to AMUSE_PREC_F32X
+struct ModeSlot {
+    const AudioModeOps* ops = nullptr;
+    void* state = nullptr;
 };
 
 }  // namespace
@@ -70,17 +73,16 @@ struct amuse_audio_ctx {
     float norm_mean = 0.f, norm_std = 1.f;
     float *melw = nullptr, *window = nullptr;   // melw: the mel filter bank TRANSPOSED, [257 bins][128 filters]
     int* mel_range = nullptr;                   // [128][2]: first / end bin of each filter's support
-    Encoder enc[3];
-    std::vector<void*> owned;
-    Workspace ws[3];             // one per encoder stream (amuse_audio_encode uses [0])
+    Uploader consts;             // owns melw, window, mel_range
+    ModeSlot mode[2];
+    const ModeSlot& cur() const { return mode[precision == AMUSE_PREC_F32X]; }   // the mode of `precision`
     float* fbank = nullptr;      // fbanks of one chunk
     int fbank_cap = 0;
     hipStream_t side[2] = {nullptr, nullptr};
     hipEvent_t ev_fork = nullptr, ev_join[2] = {nullptr, nullptr};
-    // amuse_audio_set_precision: the mode, the parity mode's state (weight images + workspaces, built on the first switch to AMUSE_PREC_F32X) and, until then,
-    // a host copy of the three parameter arrays to build it from (the device holds bf16 images only)
+    // amuse_audio_set_precision: the mode and, until the parity mode is built, a host copy of the three parameter arrays to build it from (the device holds
+    // bf16 images only)
     int precision = AMUSE_PREC_BF16;
-    void* xstate = nullptr;
     std::vector<float> host_params[3];
     // amuse_audio_set_tail: the tail's state (amuse_audio_tail.hip) and the second pooling buffer of amuse_audio_encode_labels ((cls + dist) row sums of a chunk)
     void* tail = nullptr;
@@ -90,99 +92,6 @@ struct amuse_audio_ctx {
 
 namespace {
 
-int up_f32(amuse_audio_ctx* c, float** dst, const float* src, size_t n) {
-    HIP_TRY(hipMalloc((void**)dst, n * sizeof(float)));
-    c->owned.push_back(*dst);
-    HIP_TRY(hipMemcpy(*dst, src, n * sizeof(float), hipMemcpyHostToDevice));
-    return 0;
-}
-// torch Linear weight [N][K] fp32 -> the GEMM's fragment order (amuse_audio.hpp GemmArgs::W)
-std::vector<unsigned short> pack_w(const float* W, int N, int K) {
-    std::vector<unsigned short> out((size_t)N * K);
-    size_t o = 0;
-    for (int sp = 0; sp < N / 64; ++sp)
-        for (int x = 0; x < 4; ++x)
-            for (int ks = 0; ks < K / 32; ++ks)
-                for (int lane = 0; lane < 64; ++lane) {
-                    const int g = lane >> 4, i = lane & 15;
-                    const int f = 64 * sp + 32 * (x >> 1) + 8 * (i >> 2) + 4 * (x & 1) + (i & 3);
-                    for (int e = 0; e < 8; ++e) out[o++] = f2bf(W[(size_t)f * K + 32 * ks + 8 * g + e]);
-                }
-    return out;
-}
-int up_packed(amuse_audio_ctx* c, unsigned short** dst, const float* src, int N, int K) {
-    const std::vector<unsigned short> h = pack_w(src, N, K);
-    HIP_TRY(hipMalloc((void**)dst, h.size() * 2));
-    c->owned.push_back(*dst);
-    HIP_TRY(hipMemcpy(*dst, h.data(), h.size() * 2, hipMemcpyHostToDevice));
-    return 0;
-}
-int up_bf16(amuse_audio_ctx* c, unsigned short** dst, const float* src, size_t n) {
-    std::vector<unsigned short> h(n);
-    for (size_t i = 0; i < n; ++i) h[i] = f2bf(src[i]);
-    HIP_TRY(hipMalloc((void**)dst, n * 2));
-    c->owned.push_back(*dst);
-    HIP_TRY(hipMemcpy(*dst, h.data(), n * 2, hipMemcpyHostToDevice));
-    return 0;
-}
-
-int build_encoder(amuse_audio_ctx* c, Encoder& E, const float* p) {
-    const size_t D = kAstDim;
-    auto take = [&](size_t n) { const float* q = p; p += n; return q; };
-    if (up_f32(c, &E.cls, take(D), D) || up_f32(c, &E.dist, take(D), D) ||
-        up_f32(c, &E.pos, take((size_t)kAstTokens * D), (size_t)kAstTokens * D) ||
-        up_packed(c, &E.patch_w, take(D * 256), (int)D, 256) || up_f32(c, &E.patch_b, take(D), D))
-        return AMUSE_EHIP;
-    for (int l = 0; l < kAstLayers; ++l) {
-        Block& b = E.blk[l];
-        if (up_f32(c, &b.n1w, take(D), D) || up_f32(c, &b.n1b, take(D), D) ||
-            up_packed(c, &b.qkv_w, take(3 * D * D), (int)(3 * D), (int)D) || up_f32(c, &b.qkv_b, take(3 * D), 3 * D) ||
-            up_packed(c, &b.proj_w, take(D * D), (int)D, (int)D) || up_f32(c, &b.proj_b, take(D), D) ||
-            up_f32(c, &b.n2w, take(D), D) || up_f32(c, &b.n2b, take(D), D) ||
-            up_packed(c, &b.fc1_w, take((size_t)kAstMlp * D), kAstMlp, (int)D) || up_f32(c, &b.fc1_b, take(kAstMlp), kAstMlp) ||
-            up_packed(c, &b.fc2_w, take(D * kAstMlp), (int)D, kAstMlp) || up_f32(c, &b.fc2_b, take(D), D))
-            return AMUSE_EHIP;
-    }
-    if (up_f32(c, &E.norm_w, take(D), D) || up_f32(c, &E.norm_b, take(D), D) || up_f32(c, &E.fh_ln_w, take(D), D) ||
-        up_f32(c, &E.fh_ln_b, take(D), D) || up_bf16(c, &E.fh_w, take((size_t)kAstFeat * D), (size_t)kAstFeat * D) ||
-        up_f32(c, &E.fh_b, take(kAstFeat), kAstFeat))
-        return AMUSE_EHIP;
-    return 0;
-}
-
-size_t pad128(size_t m) { return (m + 127) / 128 * 128; }
-
-void free_ws(Workspace& w) {
-    void* old[] = {w.X, w.pooled, w.H, w.QK, w.Vt, w.O, w.F, w.P};
-    for (void* p : old)
-        if (p) (void)hipFree(p);
-    w = Workspace{};
-}
-int ensure_ws(Workspace& w, int nb) {
-    if (w.cap >= nb) return 0;
-    free_ws(w);
-    const size_t Mp = pad128((size_t)nb * kAstRows);
-    HIP_TRY(hipMalloc((void**)&w.X, Mp * kAstDim * 4));
-    HIP_TRY(hipMalloc((void**)&w.pooled, (size_t)nb * kAstPoolSplit * kAstDim * 4));
-    HIP_TRY(hipMalloc((void**)&w.H, Mp * kAstDim * 2));
-    HIP_TRY(hipMalloc((void**)&w.QK, Mp * 2 * kAstDim * 2));
-    HIP_TRY(hipMalloc((void**)&w.Vt, (size_t)nb * kAstDim * kAstKeysPad * 2));
-    HIP_TRY(hipMalloc((void**)&w.O, Mp * kAstDim * 2));
-    HIP_TRY(hipMalloc((void**)&w.F, Mp * kAstMlp * 2));
-    HIP_TRY(hipMalloc((void**)&w.P, pad128((size_t)nb * kAstPatches) * 256 * 2));
-    // every activation is tile-major (amuse_audio.hpp), rows padded to the GEMM's 128-token tile.  Pad rows are read by the GEMM
-    // tiles and the LayerNorm (their results stay in pad rows) and the V^T pad columns by the attention (masked): they only
-    // have to be finite
-    HIP_TRY(hipMemset(w.X, 0, Mp * kAstDim * 4));
-    HIP_TRY(hipMemset(w.H, 0, Mp * kAstDim * 2));
-    HIP_TRY(hipMemset(w.O, 0, Mp * kAstDim * 2));
-    HIP_TRY(hipMemset(w.F, 0, Mp * kAstMlp * 2));
-    HIP_TRY(hipMemset(w.P, 0, pad128((size_t)nb * kAstPatches) * 256 * 2));
-    HIP_TRY(hipMemset(w.Vt, 0, (size_t)nb * kAstDim * kAstKeysPad * 2));
-    HIP_TRY(hipMemset(w.QK, 0, Mp * 2 * kAstDim * 2));
-    w.cap = nb;
-    return 0;
-}
 int ensure_fbank(amuse_audio_ctx* c, int nb) {
     if (c->fbank_cap >= nb) return 0;
     if (c->fbank) HIP_TRY(hipFree(c->fbank));
@@ -201,59 +110,6 @@ int ensure_side_streams(amuse_audio_ctx* c) {
     return 0;
 }
 
-// one encoder over nb <= cap clips whose fbanks are at `fbank`
-int run_encoder(const Workspace& w, const Encoder& E, int frame_based, const float* fbank, int nb, float* feat_out,
-                float* hidden_out, int tap_block, hipStream_t st) {
-    const int M = nb * kAstRows;   // a clip owns 1216 rows: 1214 tokens + 2 pad rows
-    HIP_TRY(launch_im2col(fbank, w.P, nb, st));
-    GemmArgs g{};
-    g.A = w.P; g.W = E.patch_w; g.bias = E.patch_b; g.M = nb * kAstPatches; g.N = kAstDim; g.K = 256;
-    g.out_f32 = w.X; g.pos = E.pos;
-    HIP_TRY(launch_gemm(g, EPI_PATCH, st));
-    HIP_TRY(launch_ast_tokens(E.cls, E.dist, E.pos, w.X, nb, st));
-    for (int l = 0; l < kAstLayers; ++l) {
-        const Block& b = E.blk[l];
-        HIP_TRY(launch_ln_bf16(w.X, b.n1w, b.n1b, 1e-6f, w.H, M, st));
-        g = GemmArgs{};
-        g.A = w.H; g.W = b.qkv_w; g.bias = b.qkv_b; g.M = M; g.N = 3 * kAstDim; g.K = kAstDim; g.out_bf16 = w.QK; g.vt = w.Vt;
-        HIP_TRY(launch_gemm(g, EPI_QKV, st));
-        HIP_TRY(launch_ast_attn(w.QK, w.Vt, w.O, nb, st));
-        g = GemmArgs{};
-        g.A = w.O; g.W = b.proj_w; g.bias = b.proj_b; g.M = M; g.N = kAstDim; g.K = kAstDim; g.out_f32 = w.X;
-        HIP_TRY(launch_gemm(g, EPI_RESID_F32, st));
-        HIP_TRY(launch_ln_bf16(w.X, b.n2w, b.n2b, 1e-6f, w.H, M, st));
-        g = GemmArgs{};
-        g.A = w.H; g.W = b.fc1_w; g.bias = b.fc1_b; g.M = M; g.N = kAstMlp; g.K = kAstDim; g.out_bf16 = w.F;
-        HIP_TRY(launch_gemm(g, EPI_GELU_BF16, st));
-        g = GemmArgs{};
-        g.A = w.F; g.W = b.fc2_w; g.bias = b.fc2_b; g.M = M; g.N = kAstDim; g.K = kAstMlp; g.out_f32 = w.X;
-        HIP_TRY(launch_gemm(g, EPI_RESID_F32, st));
-        if (hidden_out && l == tap_block)
-            HIP_TRY(launch_untile_f32(w.X, hidden_out, M, kAstDim, kAstRows, kAstTokens, st));
-    }
-    HIP_TRY(launch_ast_pool(w.X, E.norm_w, E.norm_b, frame_based, w.pooled, nb, st));
-    HIP_TRY(launch_ast_head(w.pooled, frame_based, E.fh_ln_w, E.fh_ln_b, E.fh_w, E.fh_b, feat_out, nb, st));
-    return 0;
-}
-
-// the two modes behind one pair of calls: workspace `slot` for nb clips / encoder `which` over nb clips on workspace `slot`
-int mode_ensure_ws(amuse_audio_ctx* c, int slot, int nb) {
-    if (c->precision == AMUSE_PREC_F32X) return amuse_audio_x_ops()->ensure_ws(c->xstate, slot, nb);
-    return ensure_ws(c->ws[slot], nb);
-}
-int mode_run_encoder(const amuse_audio_ctx* c, int slot, int which, int frame_based, const float* fbank, int nb, float* feat_out, float* hidden_out, int tap_block,
-                     hipStream_t st) {
-    if (c->precision == AMUSE_PREC_F32X)
-        return amuse_audio_x_ops()->run_encoder(c->xstate, slot, which, frame_based, fbank, nb, feat_out, hidden_out, tap_block, st);
-    return run_encoder(c->ws[slot], c->enc[which], frame_based, fbank, nb, feat_out, hidden_out, tap_block, st);
-}
-// the OTHER pooling of the residual stream the last mode_run_encoder left in workspace `slot`: v.norm, then the (cls + dist) row sums (k_ast_pool, frame_based 0)
-int mode_pool_cls(const amuse_audio_ctx* c, int slot, int which, float* pooled, int nb, hipStream_t st) {
-    if (c->precision == AMUSE_PREC_F32X) return amuse_audio_x_ops()->pool(c->xstate, slot, which, 0, pooled, nb, st);
-    const Encoder& E = c->enc[which];
-    HIP_TRY(launch_ast_pool(c->ws[slot].X, E.norm_w, E.norm_b, 0, pooled, nb, st));
-    return 0;
-}
 int ensure_pooled2(amuse_audio_ctx* c, int nb) {
     if (c->pooled2_cap >= nb) return 0;
     if (c->pooled2) HIP_TRY(hipFree(c->pooled2));
@@ -305,14 +161,9 @@ amuse_audio_ctx* amuse_audio_create(int device, const float* con_params, const f
         mel_rng[2 * m] = k0 < k1 ? k0 : 0;
         mel_rng[2 * m + 1] = k0 < k1 ? k1 : 0;
     }
-    int rc = up_f32(c, &c->melw, mel_t.data(), mel_t.size()) || up_f32(c, &c->window, window, 400);
-    if (!rc) {
-        float* rng = nullptr;   // (ints travel through the float uploader bit for bit)
-        static_assert(sizeof(int) == sizeof(float), "");
-        rc = up_f32(c, &rng, reinterpret_cast<const float*>(mel_rng.data()), mel_rng.size());
-        c->mel_range = reinterpret_cast<int*>(rng);
-    }
-    for (int e = 0; e < 3 && !rc; ++e) rc = build_encoder(c, c->enc[e], ps[e]);
+    c->mode[0].ops = &kAudioModeOps<Bf16Mode>;
+    int rc = c->consts.up(&c->melw, mel_t.data(), mel_t.size() * 4) || c->consts.up(&c->window, window, 400 * 4) ||
+             c->consts.up(&c->mel_range, mel_rng.data(), mel_rng.size() * 4) || c->mode[0].ops->create(&c->mode[0].state, ps);
     if (!rc && amuse_audio_x_ops)   // (a link without the parity mode never needs them)
         for (int e = 0; e < 3; ++e) c->host_params[e].assign(ps[e], ps[e] + n_each);
     if (rc) {
@@ -325,9 +176,9 @@ amuse_audio_ctx* amuse_audio_create(int device, const float* con_params, const f
 void amuse_audio_destroy(amuse_audio_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    for (void* p : c->owned) (void)hipFree(p);
-    for (Workspace& w : c->ws) free_ws(w);
-    if (c->xstate) amuse_audio_x_ops()->destroy(c->xstate);
+    c->consts.free_all();
+    for (ModeSlot& m : c->mode)
+        if (m.state) m.ops->destroy(m.state);
     if (c->tail) amuse_audio_tail_ops()->destroy(c->tail);
     if (c->pooled2) (void)hipFree(c->pooled2);
     if (c->fbank) (void)hipFree(c->fbank);
@@ -354,22 +205,27 @@ int amuse_audio_encode(amuse_audio_ctx* c, int which, const float* fbank, int B,
     if (B < 1) return failf(AMUSE_EINVAL, "%sB must be >= 1, got %ld", "", B);
     if (hidden_out && (tap_block < 0 || tap_block >= kAstLayers)) return failf(AMUSE_EINVAL, "%stap_block %ld not in 0..11", "", tap_block);
     HIP_TRY(hipSetDevice(c->device));
+    const ModeSlot& m = c->cur();
     const int chunk = B < kChunk ? B : kChunk;
-    if (int e = mode_ensure_ws(c, 0, chunk)) return e;
+    if (int e = m.ops->ensure_ws(m.state, 0, chunk)) return e;
     for (int b0 = 0; b0 < B; b0 += chunk) {
         const int nb = (B - b0) < chunk ? (B - b0) : chunk;
-        if (int e = mode_run_encoder(c, 0, which, c->frame_based, fbank + (size_t)b0 * kAstFrames * kAstMel, nb, feat_out + (size_t)b0 * kAstFeat,
+        if (int e = m.ops->run_encoder(m.state, 0, which, c->frame_based, fbank + (size_t)b0 * kAstFrames * kAstMel, nb, feat_out + (size_t)b0 * kAstFeat,
                                 hidden_out ? hidden_out + (size_t)b0 * kAstTokens * kAstDim : nullptr, tap_block, (hipStream_t)stream))
             return e;
     }
     return 0;
 }
 
+// amuse_audio_features runs the three encoders (independent networks over the same fbank) concurrently, each on its own
+// stream and workspace: at small batches one encoder's launches leave most of the chip idle (10 row tiles of 128 tokens per
+// clip against 512 persistent workgroup slots), at large ones the other encoders' work fills the tail of every launch.
 int amuse_audio_features(amuse_audio_ctx* c, const float* waves, int n_samples, int B, float* con_out, float* emo_out,
                          float* sty_out, void* stream) {
     if (!c || !waves) return failf(AMUSE_EINVAL, "NULL argument%s");
     if (B < 1 || n_samples < 1) return failf(AMUSE_EINVAL, "%sB and n_samples must be >= 1 (got %ld, %ld)", "", B, n_samples);
     HIP_TRY(hipSetDevice(c->device));
+    const ModeSlot& m = c->cur();
     hipStream_t st = (hipStream_t)stream;
     const int chunk = B < kChunk ? B : kChunk;
     float* outs[3] = {con_out, emo_out, sty_out};
@@ -377,7 +233,7 @@ int amuse_audio_features(amuse_audio_ctx* c, const float* waves, int n_samples, 
     if (int e = ensure_side_streams(c)) return e;
     for (int e = 0; e < 3; ++e)
         if (outs[e])
-            if (int rc = mode_ensure_ws(c, e, chunk)) return rc;
+            if (int rc = m.ops->ensure_ws(m.state, e, chunk)) return rc;
     // per chunk: fbank on `st`, then a fork-join over two side streams (stream-ordered with `st` through events, so the
     // call stays asynchronous and capturable): encoder e on stream e with workspace e
     for (int b0 = 0; b0 < B; b0 += chunk) {
@@ -387,11 +243,11 @@ int amuse_audio_features(amuse_audio_ctx* c, const float* waves, int n_samples, 
         for (int e = 1; e < 3; ++e) {
             if (!outs[e]) continue;
             HIP_TRY(hipStreamWaitEvent(c->side[e - 1], c->ev_fork, 0));
-            if (int rc = mode_run_encoder(c, e, e, c->frame_based, c->fbank, nb, outs[e] + (size_t)b0 * kAstFeat, nullptr, 0, c->side[e - 1])) return rc;
+            if (int rc = m.ops->run_encoder(m.state, e, e, c->frame_based, c->fbank, nb, outs[e] + (size_t)b0 * kAstFeat, nullptr, 0, c->side[e - 1])) return rc;
             HIP_TRY(hipEventRecord(c->ev_join[e - 1], c->side[e - 1]));
         }
         if (outs[0])
-            if (int rc = mode_run_encoder(c, 0, 0, c->frame_based, c->fbank, nb, outs[0] + (size_t)b0 * kAstFeat, nullptr, 0, st)) return rc;
+            if (int rc = m.ops->run_encoder(m.state, 0, 0, c->frame_based, c->fbank, nb, outs[0] + (size_t)b0 * kAstFeat, nullptr, 0, st)) return rc;
         for (int e = 1; e < 3; ++e)
             if (outs[e]) HIP_TRY(hipStreamWaitEvent(st, c->ev_join[e - 1], 0));   // (also: the next chunk's fbank overwrites c->fbank)
     }
@@ -420,19 +276,21 @@ int amuse_audio_encode_labels(amuse_audio_ctx* c, int which, int frame_based, co
     const int fb = frame_based < 0 ? c->frame_based : (frame_based ? 1 : 0);
     const int L = which == AMUSE_AUDIO_EMO ? kTailLabelsEmo : kTailLabelsSty;
     HIP_TRY(hipSetDevice(c->device));
+    const ModeSlot& m = c->cur();
     hipStream_t st = (hipStream_t)stream;
     const int chunk = B < kChunk ? B : kChunk;
-    if (int e = mode_ensure_ws(c, 0, chunk)) return e;
+    if (int e = m.ops->ensure_ws(m.state, 0, chunk)) return e;
     if (logits_out && fb)
         if (int e = ensure_pooled2(c, chunk)) return e;
     for (int b0 = 0; b0 < B; b0 += chunk) {
         const int nb = (B - b0) < chunk ? (B - b0) : chunk;
         float* feat = feat_out + (size_t)b0 * kAstFeat;
-        if (int e = mode_run_encoder(c, 0, which, fb, fbank + (size_t)b0 * kAstFrames * kAstMel, nb, feat, nullptr, 0, st)) return e;
+        if (int e = m.ops->run_encoder(m.state, 0, which, fb, fbank + (size_t)b0 * kAstFrames * kAstMel, nb, feat, nullptr, 0, st)) return e;
         if (!logits_out) continue;
-        // frame-based: the labels come from (cls + dist) / 2 of the final norm - the pooling the features did NOT take: a second launch_ast_pool into a second buffer
+        // frame-based: the labels come from (cls + dist) / 2 of the final norm - the pooling the features did NOT take: v.norm and k_ast_pool (frame_based 0) again,
+        // over the residual stream run_encoder left in the workspace, into a second buffer
         if (fb)
-            if (int e = mode_pool_cls(c, 0, which, c->pooled2, nb, st)) return e;
+            if (int e = m.ops->pool(m.state, 0, which, 0, c->pooled2, nb, st)) return e;
         if (int e = amuse_audio_tail_ops()->labels(c->tail, which, fb, fb ? c->pooled2 : feat, nb, logits_out + (size_t)b0 * L, st)) return e;
     }
     return 0;
@@ -463,12 +321,14 @@ int amuse_audio_set_precision(amuse_audio_ctx* c, int precision) {
     if (!c) return failf(AMUSE_EINVAL, "NULL argument%s");
     if (precision != AMUSE_PREC_BF16 && precision != AMUSE_PREC_F32X)
         return failf(AMUSE_EINVAL, "%saudio precision %ld is neither AMUSE_PREC_BF16 nor AMUSE_PREC_F32X", "", precision);
-    if (precision == AMUSE_PREC_F32X && !c->xstate) {
+    ModeSlot& x = c->mode[1];
+    if (precision == AMUSE_PREC_F32X && !x.state) {
         if (!amuse_audio_x_ops)
             return failf(AMUSE_ESTATE, "the audio front-end's AMUSE_PREC_F32X mode (amuse_audio_x) is not linked into this build%s");
         HIP_TRY(hipSetDevice(c->device));
         const float* const ps[3] = {c->host_params[0].data(), c->host_params[1].data(), c->host_params[2].data()};
-        if (int e = amuse_audio_x_ops()->create(&c->xstate, ps)) return e;
+        if (int e = amuse_audio_x_ops()->create(&x.state, ps)) return e;
+        x.ops = amuse_audio_x_ops();
         for (std::vector<float>& v : c->host_params) std::vector<float>().swap(v);   // the images are built once: the host copy is done
     }
     c->precision = precision;

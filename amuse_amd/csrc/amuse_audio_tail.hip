@@ -1,41 +1,20 @@
 // Host side of AST_EVP's tail (include/amuse_hip.h "Audio model metrics": amuse_audio_set_tail / amuse_audio_reconstruct / the labels of
 // amuse_audio_encode_labels): the device images of the classifier heads, FusionBlock and DecoderBlock, the packer of the last Linear's weight stream and the
 // launch sequence on the kernels of k_audio_tail.hip.  A translation unit of its own, reached from amuse_audio_api.hip through amuse_audio_tail_ops() only
-// (amuse_audio_tail.hpp): a link without it has the encoders and refuses the tail's calls.  Host code only.
+// (amuse_audio_tail.hpp): a link without it has the encoders and refuses the tail's calls.  Error reporting (failf, HIP_TRY_P) and f2bf are those of
+// amuse_audio_enc.hpp, shared with the encoders' units.  Host code only.
 #include <hip/hip_runtime.h>
 
-#include <cstdio>
-#include <cstring>
 #include <vector>
 
-#include "../../include/amuse_hip.h"
-#include "amuse_audio.hpp"
+#include "amuse_audio_enc.hpp"
 #include "amuse_audio_tail.hpp"
 
 using namespace amuse;
 
-int amuse_fail_msg(int code, const char* msg);   // amuse_api.hip: the library's thread-local error slot
+#define HIP_TRY(expr) HIP_TRY_P("audio tail: ", expr)
 
 namespace {
-
-int failf(int code, const char* fmt, const char* a = "", long b = 0, long c = 0) {
-    char buf[400];
-    snprintf(buf, sizeof(buf), fmt, a, b, c);
-    return amuse_fail_msg(code, buf);
-}
-#define HIP_TRY(expr)                                                                                              \
-    do {                                                                                                           \
-        hipError_t e_ = (expr);                                                                                    \
-        if (e_ != hipSuccess) return failf(AMUSE_EHIP, "audio tail: %s (line %ld)", hipGetErrorString(e_), __LINE__); \
-    } while (0)
-
-unsigned short f2bf(float f) {  // round-to-nearest-even, as v_cvt_pk_bf16_f32
-    uint32_t x;
-    memcpy(&x, &f, 4);
-    if ((x & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((x >> 16) | 0x40);
-    x += 0x7fffu + ((x >> 16) & 1u);
-    return (unsigned short)(x >> 16);
-}
 
 // torch Linear weight [N][K] fp32 -> the skinny GEMM's unit order (amuse_audio_tail.hpp tail_pack_index / tail_pack_index_x); out: N * K (bf16) or 2 * N * K (hi | lo) x 16 bit
 int pack_tail(const float* W, int N, int K, int precision, unsigned short* out) {

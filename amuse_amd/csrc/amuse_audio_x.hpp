@@ -1,5 +1,5 @@
 // Parity mode of the audio front-end (include/amuse_hip.h amuse_audio_set_precision, AMUSE_PREC_F32X): argument blocks + launchers of its
-// kernels (k_audio_gemm_x.hip, k_audio_x.hip) and the table through which amuse_audio_api.hip reaches its host side (amuse_audio_x.hip).
+// kernels (k_audio_gemm_x.hip, k_audio_x.hip) and the function through which amuse_audio_api.hip reaches its host side (amuse_audio_x.hip).
 //
 // amuse_audio_api.hip holds only a WEAK reference to amuse_audio_x_ops: a link without amuse_audio_x.o (the host-only build of
 // tests/host_asan, whose runtime stub defines the bf16 launchers and nothing else) still links, and amuse_audio_set_precision refuses the
@@ -38,21 +38,9 @@ hipError_t launch_ast_attn_x(const unsigned short* qk_hi, const unsigned short* 
 hipError_t launch_ast_head_x(const float* pooled, int frame_based, const float* gamma, const float* beta, const float* Wt, const float* bias, float* out,
                              int B, hipStream_t s);
 
-// ---- host side of the mode (amuse_audio_x.hip), as amuse_audio_api.hip sees it.  All functions return an AMUSE_* code and leave the message in amuse_last_error.
-struct AudioXOps {
-    // the three encoders' device images (split weights, fp32 small parameters) from the flat fp32 parameter arrays of amuse_audio_create (host memory)
-    int (*create)(void** state, const float* const params[3]);
-    void (*destroy)(void* state);
-    // workspace `slot` (0..2, one per encoder stream) holds at least nb clips
-    int (*ensure_ws)(void* state, int slot, int nb);
-    // one encoder over nb <= capacity clips whose fbanks are at `fbank` (the contract of amuse_audio_api.hip run_encoder)
-    int (*run_encoder)(void* state, int slot, int which, int frame_based, const float* fbank, int nb, float* feat_out, float* hidden_out, int tap_block,
-                       hipStream_t st);
-    // v.norm + k_ast_pool with the given pooling over the residual stream the last run_encoder left in workspace `slot`, into `pooled` [nb][kAstPoolSplit][768]
-    // (amuse_audio_encode_labels: the labels' pooling where it differs from the features')
-    int (*pool)(void* state, int slot, int which, int frame_based, float* pooled, int nb, hipStream_t st);
-};
+// ---- host side of the mode (amuse_audio_x.hip), as amuse_audio_api.hip sees it: the table of amuse_audio_enc.hpp that the bf16 mode fills too
+struct AudioModeOps;
 
 }  // namespace amuse
 
-extern "C" const amuse::AudioXOps* amuse_audio_x_ops(void);
+extern "C" const amuse::AudioModeOps* amuse_audio_x_ops(void);

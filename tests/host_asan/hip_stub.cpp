@@ -12,6 +12,7 @@
 // event and stream.  Pointers are printed so that the text is the same on any machine: `0`, `dev#<n>+<offset>/<block size>` inside the process's n-th hipMalloc block while it is live,
 // `<name>+<offset>` inside a buffer the driver registered (amuse_stub_name), `host` otherwise; streams and events by their order of creation; weight streams also
 // by image digest, stage tables as digests.  That pins what the image log leaves open: workspace carving, chunk offsets, the hoist launches and launch order.
+// The audio front-end's launchers print into the launch log only (tests/test_audio_launch_args_cpu.py); the line itself, struct Line, is in stub_log.hpp.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -22,6 +23,7 @@
 
 #include "../../amuse_amd/csrc/amuse_audio.hpp"
 #include "../../amuse_amd/csrc/amuse_kernels.hpp"
+#include "stub_log.hpp"
 
 static long g_live = 0;
 long amuse_stub_live_allocations() { return g_live; }
@@ -81,23 +83,11 @@ static std::string handle_text(const std::map<const void*, int>& ids, const void
     const auto it = ids.find(h);
     return it == ids.end() ? "?" : "#" + std::to_string(it->second);
 }
-// one line of the launch log: `name key=value ...`, printed when it goes out of scope
-struct Line {
-    std::string s;
-    explicit Line(const char* name) : s(name) {}
-    ~Line() { puts(s.c_str()); }
-    Line& kv(const char* k, const std::string& v) { s += ' '; s += k; s += '='; s += v; return *this; }
-    Line& p(const char* k, const void* v) { return kv(k, ptr_text(v)); }
-    Line& i(const char* k, long long v) { return kv(k, std::to_string(v)); }
-    Line& u(const char* k, unsigned long long v) { return kv(k, std::to_string(v)); }
-    Line& f(const char* k, float v) { char b[40]; snprintf(b, sizeof(b), "%a", (double)v); return kv(k, b); }   // (hex float: exact)
-    Line& x(const char* k, unsigned long long v) { char b[24]; snprintf(b, sizeof(b), "%016llx", v); return kv(k, b); }
-    Line& st(hipStream_t v) { return kv("stream", handle_text(g_streams, v)); }
-    Line& w(const void* v) { return p("wstream", v).x("image", image_of(v)); }
-};
-#define P_(f) p(#f, a.f)
-#define I_(f) i(#f, (long long)a.f)
-#define U_(f) u(#f, (unsigned long long)a.f)
+// one line of the launch log: struct Line of stub_log.hpp, which reads this file's tables through these four
+int amuse_stub_log_level() { return g_level; }
+std::string amuse_stub_ptr_text(const void* p) { return ptr_text(p); }
+std::string amuse_stub_stream_text(hipStream_t s) { return handle_text(g_streams, s); }
+unsigned long long amuse_stub_image_of(const void* p) { return image_of(p); }
 static const char* kind_text(hipMemcpyKind k) {
     return k == hipMemcpyHostToDevice ? "h2d" : k == hipMemcpyDeviceToHost ? "d2h" : k == hipMemcpyDeviceToDevice ? "d2d" : k == hipMemcpyHostToHost ? "h2h" : "default";
 }
@@ -290,17 +280,53 @@ hipError_t launch_vae_ca(const float* z, const float* wv_t, const float* bv, con
     if (g_level == 2) Line("launch_vae_ca").st(st).p("z", z).p("wv_t", wv_t).p("bv", bv).p("wo_t", wo_t).p("bo", bo).p("ca", ca).i("B", B);
     return hipSuccess;
 }
-hipError_t launch_gemm(const GemmArgs&, int, hipStream_t) { return hipSuccess; }
-hipError_t launch_fbank(const float*, int, int, const float*, const float*, const int*, float, float, float*, hipStream_t) { return hipSuccess; }
-hipError_t launch_im2col(const float*, unsigned short*, int, hipStream_t) { return hipSuccess; }
-hipError_t launch_ast_tokens(const float*, const float*, const float*, float*, int, hipStream_t) { return hipSuccess; }
-hipError_t launch_ln_bf16(const float*, const float*, const float*, float, unsigned short*, int, hipStream_t) { return hipSuccess; }
-hipError_t launch_tile_bf16(const unsigned short*, unsigned short*, int, int, hipStream_t) { return hipSuccess; }
-hipError_t launch_untile_bf16(const unsigned short*, unsigned short*, int, int, hipStream_t) { return hipSuccess; }
-hipError_t launch_untile_f32(const float*, float*, int, int, int, int, hipStream_t) { return hipSuccess; }
-hipError_t launch_ast_attn(const unsigned short*, const unsigned short*, unsigned short*, int, hipStream_t) { return hipSuccess; }
-hipError_t launch_ast_pool(const float*, const float*, const float*, int, float*, int, hipStream_t) { return hipSuccess; }
-hipError_t launch_ast_head(const float*, int, const float*, const float*, const unsigned short*, const float*, float*, int, hipStream_t) { return hipSuccess; }
+// ---- the audio front-end's launchers (amuse_audio.hpp): launch log only.  Weight pointers (GemmArgs::W, the head's W) also print the digest of their image
+hipError_t launch_gemm(const GemmArgs& a, int epi, hipStream_t st) {
+    if (g_level == 2) Line("launch_gemm").i("epi", epi).st(st).P_(A).wp("W", a.W).P_(bias).I_(M).I_(N).I_(K).P_(out_bf16).P_(out_f32).P_(pos).P_(vt);
+    return hipSuccess;
+}
+hipError_t launch_fbank(const float* wave, int n_samples, int B, const float* window, const float* melw_t, const int* mel_range, float mean, float std, float* out, hipStream_t st) {
+    if (g_level == 2)
+        Line("launch_fbank").st(st).p("wave", wave).i("n_samples", n_samples).i("B", B).p("window", window).p("melw_t", melw_t).p("mel_range", mel_range).f("mean", mean).f("std", std).p("out", out);
+    return hipSuccess;
+}
+hipError_t launch_im2col(const float* fbank, unsigned short* patches, int B, hipStream_t st) {
+    if (g_level == 2) Line("launch_im2col").st(st).p("fbank", fbank).p("patches", patches).i("B", B);
+    return hipSuccess;
+}
+hipError_t launch_ast_tokens(const float* cls, const float* dist, const float* pos, float* X, int B, hipStream_t st) {
+    if (g_level == 2) Line("launch_ast_tokens").st(st).p("cls", cls).p("dist", dist).p("pos", pos).p("X", X).i("B", B);
+    return hipSuccess;
+}
+hipError_t launch_ln_bf16(const float* X, const float* gamma, const float* beta, float eps, unsigned short* out, int M, hipStream_t st) {
+    if (g_level == 2) Line("launch_ln_bf16").st(st).p("X", X).p("gamma", gamma).p("beta", beta).f("eps", eps).p("out", out).i("M", M);
+    return hipSuccess;
+}
+hipError_t launch_tile_bf16(const unsigned short* src, unsigned short* dst, int M, int F, hipStream_t st) {
+    if (g_level == 2) Line("launch_tile_bf16").st(st).p("src", src).p("dst", dst).i("M", M).i("F", F);
+    return hipSuccess;
+}
+hipError_t launch_untile_bf16(const unsigned short* src, unsigned short* dst, int M, int F, hipStream_t st) {
+    if (g_level == 2) Line("launch_untile_bf16").st(st).p("src", src).p("dst", dst).i("M", M).i("F", F);
+    return hipSuccess;
+}
+hipError_t launch_untile_f32(const float* src, float* dst, int M, int F, int rows_in, int rows_out, hipStream_t st) {
+    if (g_level == 2) Line("launch_untile_f32").st(st).p("src", src).p("dst", dst).i("M", M).i("F", F).i("rows_in", rows_in).i("rows_out", rows_out);
+    return hipSuccess;
+}
+hipError_t launch_ast_attn(const unsigned short* QK, const unsigned short* Vt, unsigned short* O, int B, hipStream_t st) {
+    if (g_level == 2) Line("launch_ast_attn").st(st).p("QK", QK).p("Vt", Vt).p("O", O).i("B", B);
+    return hipSuccess;
+}
+hipError_t launch_ast_pool(const float* X, const float* gamma, const float* beta, int frame_based, float* pooled, int B, hipStream_t st) {
+    if (g_level == 2) Line("launch_ast_pool").st(st).p("X", X).p("gamma", gamma).p("beta", beta).i("frame_based", frame_based).p("pooled", pooled).i("B", B);
+    return hipSuccess;
+}
+hipError_t launch_ast_head(const float* pooled, int frame_based, const float* gamma, const float* beta, const unsigned short* W, const float* bias, float* out, int B, hipStream_t st) {
+    if (g_level == 2)
+        Line("launch_ast_head").st(st).p("pooled", pooled).i("frame_based", frame_based).p("gamma", gamma).p("beta", beta).wp("W", W).p("bias", bias).p("out", out).i("B", B);
+    return hipSuccess;
+}
 }  // namespace amuse
 // a second stream for drivers that do not include the HIP headers (tests/host_asan/launch_args.cpp)
 void* amuse_stub_stream_create() { hipStream_t s = nullptr; (void)hipStreamCreateWithFlags(&s, 0); return s; }

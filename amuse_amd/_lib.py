@@ -34,6 +34,7 @@ EXPORTS = [
     "amuse_train_layer_fwd", "amuse_train_layer_bwd", "amuse_train_linear_fwd", "amuse_train_linear_bwd", "amuse_train_adamw", "amuse_train_adamw_dev", "amuse_train_epoch_advance", "amuse_train_epoch_set", "amuse_train_attn_fwd", "amuse_train_attn_bwd",
     "amuse_body_create", "amuse_body_destroy", "amuse_body_set_subjects", "amuse_body_reserve", "amuse_body_forward", "amuse_body_vertex_loss", "amuse_body_info",
     "amuse_body_enable_grad", "amuse_body_vertex_loss_grad",
+    "amuse_longform_plan", "amuse_stitch_windows",
 ]
 BODY_ROT_AA, BODY_ROT_6D = 0, 1   # include/amuse_hip.h AMUSE_BODY_ROT_*
 
@@ -204,6 +205,10 @@ def load() -> C.CDLL:
     for n in ("amuse_body_set_subjects", "amuse_body_reserve", "amuse_body_forward", "amuse_body_vertex_loss", "amuse_body_info", "amuse_body_enable_grad",
               "amuse_body_vertex_loss_grad"):
         getattr(lib, n).restype = C.c_int
+    # long-form inference (csrc/amuse_stitch.hip): the window plan and the join, both context-free
+    lib.amuse_longform_plan.argtypes = [C.c_longlong, C.c_int, ip, ip, ip]
+    lib.amuse_stitch_windows.argtypes = [fp, fp, C.c_int, ip, ip, C.c_int, C.c_int, fp, fp, fp, vp]
+    lib.amuse_longform_plan.restype = lib.amuse_stitch_windows.restype = C.c_int
     if lib.amuse_abi_version() != ABI_VERSION:
         raise AmuseHipError(f"ABI mismatch: library {lib.amuse_abi_version()} vs binding {ABI_VERSION}")
     _lib = lib

@@ -13,6 +13,9 @@ What is mirrored                                   reference
   process_single_seq(wave)                          infer_ldm.py:180-193 (kaldi fbank + 3 x AST on the HIP path,
                                                     amuse_amd/audio.py, when an AST checkpoint is present; an injected
                                                     `audio_encoder` callable takes precedence)
+Beyond the reference
+  infer_long(waves, hop_frames)                     waveforms of any length as overlapping 10 s windows, one batch through
+                                                    the front-end and the sampler, joined by amuse_amd/longform.py's crossfade
 """
 from __future__ import annotations
 
@@ -248,6 +251,36 @@ class PretrainedLPDM_v1:
             return [self.process_single_seq(c, framerate, baseline) for c in chunks]
         con, emo, sty = self.audio_engine.features_ragged(chunks)
         return [(con[k:k + 1], emo[k:k + 1], sty[k:k + 1]) for k in range(len(chunks))]
+
+    def infer_long(self, waves, hop_frames: int = 270, framerate=16000, baseline=False):
+        """AN EXTENSION (the reference has no such path: it asks for 10 s WAVs, scripts/trainer.py:506): waveforms of ANY length -> [{"poses": (L, 55, 3),
+        "trans": (L, 3)}, ...] with L = max(300, floor(3 n / 1600)) frames each (amuse_amd/longform.py).  `waves`: a list of (C, n) or (n,) 16 kHz waveforms.
+        The mean of the WHOLE waveform is removed once (trainer.py:521), the waveform is cut into the plan's windows (stride hop_frames, the last one short),
+        all windows of all waveforms are embedded as one batch (process_seq_list) and sampled by ONE diffusion_backward - one clip index per window from the
+        clip counter, in waveform order and then window order - and ONE stitch joins them.  The windows are sampled independently; the crossfade over the
+        frames two neighbouring windows share hides the seam, it does not make them agree.  A waveform of at most 160,000 samples is one window: bitwise
+        process_single_seq + diffusion_backward."""
+        from . import longform
+        if self.diffusion_only:
+            raise NotImplementedError("infer_long is wired for the latent Denoiser; longform.stitch joins the pose-space variants' output as well")
+        chunks, windows, frames = [], [], []
+        for wave in waves:
+            a = torch.as_tensor(wave)
+            if a.dim() == 1:
+                a = a[None]
+            a = a - a.mean()
+            p = longform.plan(a.shape[1], hop_frames)
+            chunks += [a[:, s:e] for s, e in longform.window_slices(a.shape[1], hop_frames)]
+            windows.append(p["windows"])
+            frames.append(p["frames"])
+        if not chunks:
+            return []
+        embs = self.process_seq_list(chunks, framerate=framerate, baseline=baseline)
+        cat = lambda k: torch.cat([torch.as_tensor(e[k]).to(self.device, torch.float32).reshape(1, -1) for e in embs])
+        out = self.diffusion_backward(len(chunks), cat(0), cat(1), cat(2))
+        poses, trans = longform.stitch(out["poses"], out["trans"], windows, frames, hop_frames, F=self.seq_len)
+        offs = np.concatenate([[0], np.cumsum(frames)]).astype(int)
+        return [{"poses": poses[offs[k]:offs[k + 1]], "trans": trans[offs[k]:offs[k + 1]]} for k in range(len(frames))]
 
     def motion_to_latent(self, motion, sample: bool = True, clip_index0: Optional[int] = None):
         """The motion half of _loader_helper_v1 (infer_ldm.py:453-465): `motion` (frames, 168) = 55 x 3 SMPL-X

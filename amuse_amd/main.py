@@ -23,6 +23,9 @@ random-init weights (no checkpoint ships with the reference) so that the path ca
 Outputs: <renders>/Custom_audios_<stamp>_E<epoch>/rep<i>/rst_<k>/seq_<n>/<actor>_seq_<n>_<rand6>_motion_smplx.npz
 (trainer.py:534-538, visualizer.py:307-364).  Blender / ffmpeg rendering, wandb and the BEAT dataset objects
 (dm.dm, LMDB) are out of scope; dataset-driven edit tasks take the dict `process_loader` receives via --eval-data.
+
+Beyond the reference (which asks for 10 s WAVs, trainer.py:506): `--fn infer_gesture --long-form [--hop-frames 270]` turns a WAV of any length into ONE NPZ of
+floor(30 x seconds) frames - overlapping 10 s windows, sampled independently, crossfaded where they overlap (amuse_amd/longform.py).  Off by default.
 """
 from __future__ import annotations
 
@@ -220,6 +223,13 @@ def main(argv=None):
                                                              "deviation from the reference, whose vertices are computed under no_grad (latent_losses.py:173)")
     ap.add_argument("--smplx-models", default=None, help="train_gesture: directory holding SMPLX_MALE.npz, SMPLX_FEMALE.npz, SMPLX_NEUTRAL.npz for the vertex-displacement "
                                                          "loss terms (default: <root>/body_models/codebase/models/smplx, the reference's path)")
+    ap.add_argument("--long-form", action="store_true",
+                    help="infer_gesture: a WAV of ANY length becomes one motion of floor(30 x seconds) frames - an extension, the reference asks for 10 s WAVs. "
+                         "The waveform is cut into overlapping 10 s windows, every window is sampled as a clip of its own (independently: nothing is shared "
+                         "between windows) and the frames two neighbouring windows both produced are crossfaded, which hides the seam but does not make the "
+                         "windows agree.  A WAV of at most 160,000 samples gives the bytes it gives without the switch")
+    ap.add_argument("--hop-frames", type=int, default=270, help="--long-form: frames between window starts, a multiple of 3 in 150..300 (default 270: one second "
+                                                                "of overlap; 300: plain concatenation)")
     args = ap.parse_args(argv)
     fn = args.fn[0]
     if fn not in ("infer_gesture", "edit_gesture", "train_gesture"):
@@ -227,6 +237,14 @@ def main(argv=None):
     if args.vtex_grad and (fn != "train_gesture" or not args.smplx_models):
         raise SystemExit("--vtex-grad belongs to --fn train_gesture and needs --smplx-models DIR: the vertex-displacement terms it differentiates are built from the "
                          "SMPL-X body models")
+    if args.long_form and fn != "infer_gesture":
+        raise SystemExit("--long-form belongs to --fn infer_gesture: it joins the windows of one WAV into one motion; the edit tasks work on 10 s clips")
+    if args.long_form:
+        from . import _lib, longform
+        try:
+            longform.plan(0, args.hop_frames)      # the library's own check of the hop, before anything is loaded
+        except _lib.AmuseHipError as e:
+            raise SystemExit(f"--hop-frames {args.hop_frames}: {e}")
     tic = time.time()
     dirname = Path(args.root) if args.root else Path.cwd().parent
     config, ldm_cfg = load_config(dirname, fn, args.cfg)
@@ -293,6 +311,8 @@ def main(argv=None):
         model = PretrainedLPDM_v1(None)
         ldm_epoch = model.setup(config, device, processed, None, False, baseline, verbose=False, diffonly=diffonly)
     tp["test"]["audio_metrics"] = bool(args.audio_metrics)
+    if args.long_form:       # (the keys are this path's own; without the switch the configuration is left as it is)
+        tp["test"]["long_form"], tp["test"]["hop_frames"] = True, int(args.hop_frames)
     model.precision = args.precision
     print(f"[amuse_amd] sampler / decoder precision: {args.precision}; audio front-end precision: {args.audio_precision}"
           + (" (split-fp16 AST encoders: with --precision fp32 / fp32x the run is in parity from the waveform)" if args.audio_precision == "fp32x"

@@ -70,6 +70,34 @@ def load_wav(path) -> torch.Tensor:
     return torch.from_numpy(np.ascontiguousarray(x.T))
 
 
+def wav_samples(path) -> int:
+    """Samples per channel of a WAV, from its RIFF header alone (the "fmt " chunk's block size and the "data" chunk's byte count): what the long-form job list
+    needs of every file before any audio is decoded.  A data chunk that claims more bytes than the file holds counts what is there, as the decoder does."""
+    import struct
+    with open(path, "rb") as f:
+        head = f.read(12)
+        if len(head) < 12 or head[:4] not in (b"RIFF", b"RIFX") or head[8:12] != b"WAVE":
+            raise ValueError(f"{path}: not a RIFF / WAVE file")
+        end = "<" if head[:4] == b"RIFF" else ">"
+        block = None
+        while True:
+            h = f.read(8)
+            if len(h) < 8:
+                raise ValueError(f"{path}: no data chunk")
+            size = struct.unpack(end + "I", h[4:])[0]
+            if h[:4] == b"fmt ":
+                fmt = f.read(size + (size & 1))
+                block = struct.unpack(end + "H", fmt[12:14])[0]
+            elif h[:4] == b"data":
+                if not block:
+                    raise ValueError(f"{path}: data chunk before a usable fmt chunk")
+                pos = f.tell()
+                f.seek(0, 2)
+                return min(size, f.tell() - pos) // block
+            else:
+                f.seek(size + (size & 1), 1)
+
+
 def _dist_ready() -> bool:
     import torch.distributed as dist
     return dist.is_available() and dist.is_initialized()
@@ -213,6 +241,8 @@ def style_Xemo_transfer_jobs(data: Dict, actors: str, emotion: str) -> List[dict
 def run_jobs(model, jobs: List[dict], return_latents: bool = False, batched: bool = True, rank: int = 0, world: int = 1) -> List[Optional[dict]]:
     """Sample every job; returns, per job and in job order, the reference's `rst` entry
     {"feats": (bsz,300,168), "audio", "info"[, "swap_info"]} (trainer.py:884-890) [+ "latents"].
+    A job that carries "long_form": {"frames": L, "hop": h} is ONE waveform cut into bsz overlapping windows (an extension, amuse_amd/longform.py): its rows
+    are sampled like any job's - one clip index per window - and joined before they are packed, so it yields feats (1, L, 168).
     batched=True: ONE diffusion_backward per group of jobs that share the set of condition tokens (a missing z_emo /
     z_sty drops a token, denoiser.py:159-171, which changes the kernel's tile shape); clip indices are assigned in job
     order exactly as the sequential calls would have drawn them.  batched=False: the reference's call pattern.
@@ -234,6 +264,10 @@ def run_jobs(model, jobs: List[dict], return_latents: bool = False, batched: boo
     offs = np.concatenate([[0], np.cumsum([j["bsz"] for j in jobs])]).astype(int)
 
     def finish(j, poses, trans, lat):
+        lf = jobs[j].get("long_form")
+        if lf is not None:      # the job's rows are the windows of ONE waveform (amuse_amd/longform.py): joined into one motion of lf["frames"] frames
+            from . import longform
+            poses, trans = (t[None] for t in longform.stitch(poses, trans, [jobs[j]["bsz"]], [lf["frames"]], lf["hop"], F=poses.shape[1]))
         r = {"feats": pack_feats(poses, trans), "audio": jobs[j]["audio"], "info": jobs[j]["info"]}
         if jobs[j].get("swap_info") is not None:
             r["swap_info"] = jobs[j]["swap_info"]
@@ -393,6 +427,43 @@ class trainer:
             out[k] = e
         return out
 
+    def _long_form_jobs(self, audios, baseline=False):
+        """TRAIN_PARAM.test.long_form (amuse_amd.main --long-form; an extension, amuse_amd/longform.py): every WAV is ONE job of bsz = W windows at a stride
+        of TRAIN_PARAM.test.hop_frames frames, which run_jobs joins into one motion of L frames.  The job list needs every W before the front-end runs: the
+        sample counts come from the files' headers, no audio is decoded for it.  A WAV's windows are one job, and ranks take whole jobs (shard.job_range), so
+        they stay on one rank.  This rank's WAVs are loaded, their mean is removed ONCE over the whole waveform (trainer.py:521), and all their windows go
+        through the front-end as one batch.  A WAV of at most 160,000 samples is one window holding the whole waveform: the job the default path builds."""
+        from . import longform
+        hop = int(self.config["TRAIN_PARAM"]["test"].get("hop_frames", longform.DEFAULT_HOP))
+        n = [wav_samples(a) for a in audios]
+        plans = [longform.plan(k, hop) for k in n]
+        mine = local_jobs([(p["windows"], False, False) for p in plans], self.rank, self.world)
+        chunks = []
+        for k, a in enumerate(audios):
+            if mine[k]:
+                w = load_wav(a)
+                if w.shape[1] != n[k]:
+                    raise ValueError(f"{a}: the header announces {n[k]} samples, the decoder returned {w.shape[1]}")
+                w = w - w.mean()
+                chunks += [w[:, s:e] for s, e in longform.window_slices(n[k], hop)]
+        many = getattr(self.model, "process_seq_list", None)
+        if not chunks:
+            embs = []
+        elif many is not None:
+            embs = many(chunks, framerate=16000, baseline=baseline)
+        else:
+            embs = [self.model.process_single_seq(c, framerate=16000, baseline=baseline) for c in chunks]
+        jobs, pos = [], 0
+        for k, a in enumerate(audios):
+            W, lf = plans[k]["windows"], {"frames": plans[k]["frames"], "hop": hop}
+            if not mine[k]:
+                jobs.append(_remote_job("scott", a.stem, W, "scott", long_form=lf))
+                continue
+            con, emo, sty = (torch.cat([torch.as_tensor(e[i]).reshape(1, -1) for e in embs[pos:pos + W]]) for i in range(3))
+            pos += W
+            jobs.append(_job("scott", a.stem, con, emo, sty, W, "scott", None, None, None, long_form=lf))
+        return jobs, mine
+
     # ------------------------------------------------------------------ infer_gesture
     def _infer_prior_latdiff_from_audio_v1(self, baseline, ldm_epoch, audio_list, short_audio_list, modelversion, ammetric):
         start_time = time.time()
@@ -414,10 +485,13 @@ class trainer:
             # it (seq_0/<actor>_seq_0_<rand6>_motion_smplx.npz, told apart only by the random tag).  Same layout
             # here; the embeddings of all audios are computed first and the clips are sampled as one launch.
             # More than one rank: the plan first (which jobs are this rank's), then only this rank's audios through the front-end.
-            mine = local_jobs([(1, False, False)] * len(audios), self.rank, self.world)
-            embs = self._embed_all(audios, baseline, needed=[k for k, m in enumerate(mine) if m])
-            jobs = [_job("scott", a.stem, *embs[k], 1, "scott", None, None, None) if mine[k] else _remote_job("scott", a.stem, 1, "scott")
-                    for k, a in enumerate(audios)]
+            if self.config["TRAIN_PARAM"]["test"].get("long_form", False):
+                jobs, mine = self._long_form_jobs(audios, baseline)
+            else:
+                mine = local_jobs([(1, False, False)] * len(audios), self.rank, self.world)
+                embs = self._embed_all(audios, baseline, needed=[k for k, m in enumerate(mine) if m])
+                jobs = [_job("scott", a.stem, *embs[k], 1, "scott", None, None, None) if mine[k] else _remote_job("scott", a.stem, 1, "scott")
+                        for k, a in enumerate(audios)]
             rst_all = run_jobs(self.model, jobs, batched=self.batched, rank=self.rank, world=self.world)
             video_dump_r = target_path / f"Custom_audios_{self.stamp}_E{ldm_epoch}" / f"rep{rep_i}"
             assert self.viz_type in ["CaMN"], "[LDM EVAL] Invalid viz type: [%s]" % self.viz_type

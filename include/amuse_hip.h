@@ -648,6 +648,39 @@ int amuse_body_vertex_loss_grad(amuse_body_ctx* ctx, const float* ref, const flo
  * 4 gradients enabled (0 | 1) */
 int amuse_body_info(const amuse_body_ctx* ctx, int what);
 
+/* ------------------------------------------------------------------ long-form inference (csrc/amuse_stitch_host.hpp, amuse_stitch.hip, k_stitch.hip; amuse_amd/longform.py)
+ * AN EXTENSION: the reference has no such path - it asks for 10 s WAVs ("Make sure each audio is a 10 sec wav file", scripts/trainer.py:506).  A longer waveform is
+ * cut into overlapping windows of the model's clip (F = 300 frames = 160,000 samples: 16 kHz audio, 30 fps motion, the rates the reference assumes of every file;
+ * nothing resamples), every window is embedded and sampled as a clip of its own - INDEPENDENTLY: the Denoiser's state is one latent per clip, nothing is shared
+ * between windows - and the frames two neighbouring windows both produced are crossfaded.  The crossfade hides the seam; it does not make the windows agree.
+ *
+ * The window plan, stated once; needs no GPU and no context.  hop_frames h: the stride between window starts, a multiple of 3 (so that the hop is the whole
+ * number h / 3 * 1600 of samples) with 150 <= h <= 300 (so that at most two windows cover a frame); the product's default is 270, one second of overlap.
+ *   *frames       L = max(300, floor(3 n / 1600))
+ *   *windows      W = 1 if L <= 300, else ceil((L - 300) / h) + 1
+ *   *hop_samples  hs = h / 3 * 1600
+ * Window w reads the samples [w hs, min(w hs + 160000, n)) and yields the frames [w h, w h + 300) of the sequence, cut at L.  The last window may be short: it
+ * goes through the front-end's pad path, as a short WAV does.  By this arithmetic the last window of W > 1 always holds MORE than 300 - h frames of audio
+ * ((W - 1) h < L - 300 + h and n >= 1600 L / 3), i.e. every frame past the last overlap comes from audio, never from padding alone.  n <= 160,000 gives W = 1,
+ * L = 300: one clip, as without the plan.  Any output pointer may be NULL.  AMUSE_EINVAL for n < 0 (or beyond an int of frames) and for a bad h. */
+int amuse_longform_plan(long long n_samples, int hop_frames, int* windows, int* frames, int* hop_samples);
+/* The join.  Context-free and stream-ordered; no allocation, no copy, no host synchronisation: it can be captured.  The per-sequence offsets travel by value in
+ * the kernel arguments, 32 sequences per launch; a call with more sequences takes ceil(S / 32) launches.
+ *   poses dev [sum W_s][F][55][3] axis-angle, trans dev [sum W_s][F][3]: the windows of S sequences back to back, as amuse_diffusion_backward writes them
+ *   windows / frames: HOST int [S], W_s and L_s;  blend dev [F - hop] (may be NULL when hop == F);  poses_out dev [sum L_s][55][3], trans_out dev [sum L_s][3]
+ *   trans and trans_out are NULL together (poses only).
+ * Output frame f of a sequence, with k = min(f / hop, W - 1), i = f - k hop, O = F - hop:
+ *   k == 0 or i >= O   a BITWISE copy of window k's row i (rotations beyond pi stay as they are)
+ *   otherwise          window k - 1's row i + hop (a) and window k's row i (b) at weight w = blend[i]: translation (1 - w) a + w b; each joint in fp32: axis-angle
+ *                      -> unit quaternion; q_b negated where q_a . q_b = d < 0; Omega = atan2(|q_b - d q_a|, d); (sin((1 - w) Omega) q_a + sin(w Omega) q_b) /
+ *                      sin Omega (the linear form (1 - w) q_a + w q_b where sin Omega < 1e-4), normalised, negated if its real part is negative, -> axis-angle
+ *                      by the arithmetic of the decode tail.  Blended rows therefore carry angles <= pi.
+ * The product's weights are 0.5 - 0.5 cos(pi (i + 1) / (O + 1)), i = 0 .. O - 1, computed in double and rounded to fp32 (amuse_amd/longform.py blend_weights).
+ * Checked before any HIP call, AMUSE_EINVAL otherwise: S >= 1; F >= 2 (the product passes 300); F / 2 <= hop <= F; for every s, W_s >= 1 and
+ * (W_s - 1) hop < L_s <= (W_s - 1) hop + F; the pointers above non-NULL; the call's window rows and 56 x its output frames within an int. */
+int amuse_stitch_windows(const float* poses, const float* trans, int S, const int* windows, const int* frames, int F, int hop, const float* blend,
+                         float* poses_out, float* trans_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,7 +35,9 @@ EXPORTS = [
     "amuse_body_create", "amuse_body_destroy", "amuse_body_set_subjects", "amuse_body_reserve", "amuse_body_forward", "amuse_body_vertex_loss", "amuse_body_info",
     "amuse_body_enable_grad", "amuse_body_vertex_loss_grad",
     "amuse_longform_plan", "amuse_stitch_windows",
+    "amuse_resample_plan", "amuse_resampler_create", "amuse_resampler_destroy", "amuse_resample", "amuse_debug_resample_bank",
 ]
+PCM_U8, PCM_S16, PCM_S32, PCM_F32 = 0, 1, 2, 3   # include/amuse_hip.h AMUSE_PCM_*
 BODY_ROT_AA, BODY_ROT_6D = 0, 1   # include/amuse_hip.h AMUSE_BODY_ROT_*
 
 
@@ -209,6 +211,15 @@ def load() -> C.CDLL:
     lib.amuse_longform_plan.argtypes = [C.c_longlong, C.c_int, ip, ip, ip]
     lib.amuse_stitch_windows.argtypes = [fp, fp, C.c_int, ip, ip, C.c_int, C.c_int, fp, fp, fp, vp]
     lib.amuse_longform_plan.restype = lib.amuse_stitch_windows.restype = C.c_int
+    # sample-rate conversion (csrc/amuse_resample.hip): the plan and the bank need no GPU; one resampler per (GPU, rate pair)
+    lib.amuse_resample_plan.argtypes = [C.c_int, C.c_int, C.c_longlong, ip, ip, ip, C.POINTER(C.c_longlong)]
+    lib.amuse_resampler_create.restype = vp
+    lib.amuse_resampler_create.argtypes = [C.c_int, C.c_int, C.c_int]
+    lib.amuse_resampler_destroy.restype = None
+    lib.amuse_resampler_destroy.argtypes = [vp]
+    lib.amuse_resample.argtypes = [vp, vp, C.c_int, C.c_int, C.c_longlong, fp, C.c_longlong, vp]
+    lib.amuse_debug_resample_bank.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_float)]
+    lib.amuse_resample_plan.restype = lib.amuse_resample.restype = lib.amuse_debug_resample_bank.restype = C.c_int
     if lib.amuse_abi_version() != ABI_VERSION:
         raise AmuseHipError(f"ABI mismatch: library {lib.amuse_abi_version()} vs binding {ABI_VERSION}")
     _lib = lib

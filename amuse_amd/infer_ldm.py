@@ -252,14 +252,17 @@ class PretrainedLPDM_v1:
         con, emo, sty = self.audio_engine.features_ragged(chunks)
         return [(con[k:k + 1], emo[k:k + 1], sty[k:k + 1]) for k in range(len(chunks))]
 
-    def infer_long(self, waves, hop_frames: int = 270, framerate=16000, baseline=False):
+    def infer_long(self, waves, hop_frames: int = 270, framerate=16000, baseline=False, sample_rate=None):
         """AN EXTENSION (the reference has no such path: it asks for 10 s WAVs, scripts/trainer.py:506): waveforms of ANY length -> [{"poses": (L, 55, 3),
         "trans": (L, 3)}, ...] with L = max(300, floor(3 n / 1600)) frames each (amuse_amd/longform.py).  `waves`: a list of (C, n) or (n,) 16 kHz waveforms.
         The mean of the WHOLE waveform is removed once (trainer.py:521), the waveform is cut into the plan's windows (stride hop_frames, the last one short),
         all windows of all waveforms are embedded as one batch (process_seq_list) and sampled by ONE diffusion_backward - one clip index per window from the
         clip counter, in waveform order and then window order - and ONE stitch joins them.  The windows are sampled independently; the crossfade over the
         frames two neighbouring windows share hides the seam, it does not make them agree.  A waveform of at most 160,000 samples is one window: bitwise
-        process_single_seq + diffusion_backward."""
+        process_single_seq + diffusion_backward.
+        sample_rate (an extension of its own, amuse_amd/resample.py): the rate of `waves` in Hz.  None or 16000: the waveforms are read as 16 kHz, as everywhere
+        on this path.  Another rate: channel 0 of every waveform goes through the HIP resampler first and everything above applies to its output.  (`framerate`
+        is NOT this: it mirrors the reference's argument, which nothing reads.)"""
         from . import longform
         if self.diffusion_only:
             raise NotImplementedError("infer_long is wired for the latent Denoiser; longform.stitch joins the pose-space variants' output as well")
@@ -268,6 +271,9 @@ class PretrainedLPDM_v1:
             a = torch.as_tensor(wave)
             if a.dim() == 1:
                 a = a[None]
+            if sample_rate is not None and int(sample_rate) != 16000 and a.shape[1] > 0:
+                from . import resample
+                a = resample.resample(a, int(sample_rate), device=self.device).cpu()
             a = a - a.mean()
             p = longform.plan(a.shape[1], hop_frames)
             chunks += [a[:, s:e] for s, e in longform.window_slices(a.shape[1], hop_frames)]

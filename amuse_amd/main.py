@@ -26,6 +26,8 @@ Outputs: <renders>/Custom_audios_<stamp>_E<epoch>/rep<i>/rst_<k>/seq_<n>/<actor>
 
 Beyond the reference (which asks for 10 s WAVs, trainer.py:506): `--fn infer_gesture --long-form [--hop-frames 270]` turns a WAV of any length into ONE NPZ of
 floor(30 x seconds) frames - overlapping 10 s windows, sampled independently, crossfaded where they overlap (amuse_amd/longform.py).  Off by default.
+`--fn infer_gesture | edit_gesture --resample` converts a WAV of another rate to the 16 kHz the front-end is built for, in a HIP kernel
+(amuse_amd/resample.py); the reference reads every file as 16 kHz whatever its header says.  Off by default.
 """
 from __future__ import annotations
 
@@ -230,6 +232,11 @@ def main(argv=None):
                          "windows agree.  A WAV of at most 160,000 samples gives the bytes it gives without the switch")
     ap.add_argument("--hop-frames", type=int, default=270, help="--long-form: frames between window starts, a multiple of 3 in 150..300 (default 270: one second "
                                                                 "of overlap; 300: plain concatenation)")
+    ap.add_argument("--resample", action="store_true",
+                    help="infer_gesture / edit_gesture: a WAV whose header states another rate than 16,000 Hz is converted to 16 kHz on the GPU before the "
+                         "front-end reads it - an extension, the reference drops the rate and reads every file as 16 kHz (so a 48 kHz recording is animated as "
+                         "speech slowed three times).  The filter is a Hann-windowed sinc written down from memory of torchaudio's defaults, pinned against no "
+                         "other implementation.  A 16 kHz file gives the bytes it gives without the switch; works with --long-form and --audio-metrics")
     args = ap.parse_args(argv)
     fn = args.fn[0]
     if fn not in ("infer_gesture", "edit_gesture", "train_gesture"):
@@ -237,6 +244,8 @@ def main(argv=None):
     if args.vtex_grad and (fn != "train_gesture" or not args.smplx_models):
         raise SystemExit("--vtex-grad belongs to --fn train_gesture and needs --smplx-models DIR: the vertex-displacement terms it differentiates are built from the "
                          "SMPL-X body models")
+    if args.resample and fn == "train_gesture":
+        raise SystemExit("--resample belongs to --fn infer_gesture / edit_gesture: it converts the WAVs those read; the training reader is left as it is")
     if args.long_form and fn != "infer_gesture":
         raise SystemExit("--long-form belongs to --fn infer_gesture: it joins the windows of one WAV into one motion; the edit tasks work on 10 s clips")
     if args.long_form:
@@ -311,6 +320,8 @@ def main(argv=None):
         model = PretrainedLPDM_v1(None)
         ldm_epoch = model.setup(config, device, processed, None, False, baseline, verbose=False, diffonly=diffonly)
     tp["test"]["audio_metrics"] = bool(args.audio_metrics)
+    if args.resample:        # (as below: the key is this path's own; without the switch the configuration is left as it is)
+        tp["test"]["resample"] = True
     if args.long_form:       # (the keys are this path's own; without the switch the configuration is left as it is)
         tp["test"]["long_form"], tp["test"]["hop_frames"] = True, int(args.hop_frames)
     model.precision = args.precision

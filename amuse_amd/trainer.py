@@ -30,6 +30,7 @@ from __future__ import annotations
 import os
 import random
 import string
+import sys
 import time
 from datetime import datetime
 from pathlib import Path
@@ -47,6 +48,9 @@ SUBJECTS = ["wayne", "scott", "solomon", "lawrence", "stewart", "nidal", "zhao",
             "goto", "reamey", "yingqing", "tiffnay", "hanieh", "katya"]
 
 
+_RATE_NOTICED = set()      # WAVs whose non-16 kHz rate has been named on stderr (_load_wave)
+
+
 def subject_of(info: str) -> str:
     """visualizer.py:303: subject = [x for x in self.subjects if x in attr][0]."""
     return [x for x in SUBJECTS if x in info][0]
@@ -55,8 +59,14 @@ def subject_of(info: str) -> str:
 def load_wav(path) -> torch.Tensor:
     """torchaudio.load semantics (trainer.py:519): (channels, samples) float32 in [-1, 1), native sample rate - the
     reference does not resample, it feeds whatever rate the file has to a 16 kHz fbank."""
+    return load_wav_rate(path)[0]
+
+
+def load_wav_rate(path):
+    """load_wav and the rate the file's header states: ((channels, samples) float32, rate in Hz).  The rate is what TRAIN_PARAM.test.resample
+    (amuse_amd/resample.py, an extension) needs; the reference drops it (trainer.py:520)."""
     from scipy.io import wavfile
-    _, data = wavfile.read(str(path))
+    rate, data = wavfile.read(str(path))
     if data.ndim == 1:
         data = data[:, None]
     if data.dtype == np.int16:
@@ -67,19 +77,24 @@ def load_wav(path) -> torch.Tensor:
         x = (data.astype(np.float32) - 128.0) / 128.0
     else:
         x = data.astype(np.float32)
-    return torch.from_numpy(np.ascontiguousarray(x.T))
+    return torch.from_numpy(np.ascontiguousarray(x.T)), int(rate)
 
 
 def wav_samples(path) -> int:
     """Samples per channel of a WAV, from its RIFF header alone (the "fmt " chunk's block size and the "data" chunk's byte count): what the long-form job list
     needs of every file before any audio is decoded.  A data chunk that claims more bytes than the file holds counts what is there, as the decoder does."""
+    return wav_header(path)[0]
+
+
+def wav_header(path):
+    """wav_samples and the sample rate of the "fmt " chunk: (samples per channel, rate in Hz), from the RIFF header alone."""
     import struct
     with open(path, "rb") as f:
         head = f.read(12)
         if len(head) < 12 or head[:4] not in (b"RIFF", b"RIFX") or head[8:12] != b"WAVE":
             raise ValueError(f"{path}: not a RIFF / WAVE file")
         end = "<" if head[:4] == b"RIFF" else ">"
-        block = None
+        block = rate = None
         while True:
             h = f.read(8)
             if len(h) < 8:
@@ -88,12 +103,13 @@ def wav_samples(path) -> int:
             if h[:4] == b"fmt ":
                 fmt = f.read(size + (size & 1))
                 block = struct.unpack(end + "H", fmt[12:14])[0]
+                rate = struct.unpack(end + "I", fmt[4:8])[0]
             elif h[:4] == b"data":
                 if not block:
                     raise ValueError(f"{path}: data chunk before a usable fmt chunk")
                 pos = f.tell()
                 f.seek(0, 2)
-                return min(size, f.tell() - pos) // block
+                return min(size, f.tell() - pos) // block, int(rate)
             else:
                 f.seek(size + (size & 1), 1)
 
@@ -376,10 +392,28 @@ class trainer:
     def _embed(self, path, baseline=False):
         return self._embed_all([path], baseline)[0]
 
+    def _resample_on(self) -> bool:
+        return bool(self.config["TRAIN_PARAM"]["test"].get("resample", False))
+
+    def _load_wave(self, path):
+        """load_wav - and, under TRAIN_PARAM.test.resample (amuse_amd.main --resample; an extension, amuse_amd/resample.py), a file whose header states another
+        rate than 16,000 Hz goes through the HIP resampler first: channel 0 at 16 kHz, (1, n_out), back on the host so that everything behind it - the removal of
+        the mean included - is the code a 16 kHz file runs.  A 16 kHz file never reaches the resampler.  With the switch off the rate is only named, once per file."""
+        wave, rate = load_wav_rate(path)
+        if rate == 16000 or wave.shape[1] == 0:      # (an empty file has nothing to convert: the front-end pads it, as it does today)
+            return wave
+        if not self._resample_on():
+            if str(path) not in _RATE_NOTICED:
+                _RATE_NOTICED.add(str(path))
+                print(f"[amuse_amd] {path}: {rate} Hz is read as 16,000 Hz, as the reference reads it (--resample converts it)", file=sys.stderr)
+            return wave
+        from . import resample
+        return resample.resample(wave, rate, device=self.device).cpu()
+
     def _embed_some(self, paths, baseline=False):
         waves = []
         for path in paths:
-            a = load_wav(path)
+            a = self._load_wave(path)
             waves.append(a - a.mean())
         many = getattr(self.model, "process_seq_list", None)
         if many is not None:
@@ -427,6 +461,15 @@ class trainer:
             out[k] = e
         return out
 
+    def _long_form_samples(self, audios):
+        """Samples per WAV as the front-end will see them, from the headers alone: the file's own count - or, under TRAIN_PARAM.test.resample, the count
+        amuse_resample_plan gives a file of another rate at 16 kHz (nothing here restates its arithmetic)."""
+        heads = [wav_header(a) for a in audios]
+        if not self._resample_on():
+            return [n for n, _ in heads]
+        from . import resample
+        return [n if rate == 16000 or n == 0 else resample.plan(rate, 16000, n)["n_out"] for n, rate in heads]
+
     def _long_form_jobs(self, audios, baseline=False):
         """TRAIN_PARAM.test.long_form (amuse_amd.main --long-form; an extension, amuse_amd/longform.py): every WAV is ONE job of bsz = W windows at a stride
         of TRAIN_PARAM.test.hop_frames frames, which run_jobs joins into one motion of L frames.  The job list needs every W before the front-end runs: the
@@ -435,15 +478,15 @@ class trainer:
         through the front-end as one batch.  A WAV of at most 160,000 samples is one window holding the whole waveform: the job the default path builds."""
         from . import longform
         hop = int(self.config["TRAIN_PARAM"]["test"].get("hop_frames", longform.DEFAULT_HOP))
-        n = [wav_samples(a) for a in audios]
+        n = self._long_form_samples(audios)
         plans = [longform.plan(k, hop) for k in n]
         mine = local_jobs([(p["windows"], False, False) for p in plans], self.rank, self.world)
         chunks = []
         for k, a in enumerate(audios):
             if mine[k]:
-                w = load_wav(a)
+                w = self._load_wave(a)
                 if w.shape[1] != n[k]:
-                    raise ValueError(f"{a}: the header announces {n[k]} samples, the decoder returned {w.shape[1]}")
+                    raise ValueError(f"{a}: the header announces {n[k]} samples{' at 16 kHz' if self._resample_on() else ''}, the decoder returned {w.shape[1]}")
                 w = w - w.mean()
                 chunks += [w[:, s:e] for s, e in longform.window_slices(n[k], hop)]
         many = getattr(self.model, "process_seq_list", None)
@@ -506,7 +549,7 @@ class trainer:
             if self.config["TRAIN_PARAM"]["test"].get("audio_metrics", False):
                 for k, a in enumerate(audios):
                     if mine[k]:
-                        wave = load_wav(a)
+                        wave = self._load_wave(a)
                         self.model.collect_audio_metrics(wave - wave.mean(), framerate=16000, baseline=baseline, tgtpath=video_dump_r / "rst_0" / a.stem)
         print(f"[LDM EVAL] Audio list inference done, total time elapsed: {time.time() - start_time:.4f} s")
 

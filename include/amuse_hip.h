@@ -681,6 +681,36 @@ int amuse_longform_plan(long long n_samples, int hop_frames, int* windows, int* 
 int amuse_stitch_windows(const float* poses, const float* trans, int S, const int* windows, const int* frames, int F, int hop, const float* blend,
                          float* poses_out, float* trans_out, void* stream);
 
+/* ------------------------------------------------------------------ sample-rate conversion (csrc/amuse_resample_host.hpp, amuse_resample.hip, k_resample.hip; amuse_amd/resample.py)
+ * AN EXTENSION, off by default: the reference never resamples - scripts/trainer.py:520 drops the file's rate and feeds whatever samples it holds to a 16 kHz fbank.
+ * The filter is a band-limited, Hann-windowed sinc in polyphase form.  Its constants (6 zero crossings, roll-off 0.99) are a RECOLLECTION of
+ * torchaudio.functional.resample's defaults; torchaudio is pinned nowhere in this project, the filter is checked against its own float64 restatement
+ * (tests/resample_ref.py) and scipy.signal.upfirdn only.
+ *
+ * For integer rates r_in -> r_out: g = gcd, M = r_in / g, L = r_out / g, base = 0.99 min(M, L), lpw = 6, Hw = ceil(lpw M / base), K = 2 Hw + 2,
+ * n_out = ceil(n_in L / M).  Output sample m, with phase i = m mod L and j0 = floor(m M / L) - Hw (64-bit integers; no index comes from a float):
+ *   y[m] = sum over k = 0 .. K - 1, in that order, in fp32, of h[i][k] x[j0 + k]        (x is zero outside 0 .. n_in - 1)
+ *   h[i][k] = (base / M) sinc(pi t) cos^2(pi t / (2 lpw)) where |t| < lpw, else 0;  t = base ((floor(i M / L) - Hw + k) / M - i / L);  sinc(0) = 1
+ * The bank h is computed once on the host in double and rounded to fp32.  EQUAL rates are the identity: M = L = 1, Hw = 0, K = 1, h = {1}, and the output is
+ * the format conversion of channel 0, bitwise.
+ *
+ * amuse_resample_plan: the plan, stated once; needs no GPU and no context.  *up = L, *down = M, *taps = K, *n_out as above; any output pointer may be NULL.
+ * AMUSE_EINVAL for rates outside 4,000..384,000 Hz, for a bank L x K x 4 bytes above 2 MiB (44101 -> 16000 Hz: 16000 phases), for n_in < 1 and for n_in or
+ * n_out beyond an int. */
+enum { AMUSE_PCM_U8 = 0, AMUSE_PCM_S16 = 1, AMUSE_PCM_S32 = 2, AMUSE_PCM_F32 = 3 };
+typedef struct amuse_resampler amuse_resampler;
+int amuse_resample_plan(int rate_in, int rate_out, long long n_in, int* up, int* down, int* taps, long long* n_out);
+/* One resampler per (GPU, rate pair): builds the bank and uploads it (L x K floats of device memory).  NULL on failure (amuse_last_error). */
+amuse_resampler* amuse_resampler_create(int device, int rate_in, int rate_out);
+void amuse_resampler_destroy(amuse_resampler* r);
+/* One waveform.  pcm dev [n_in][channels]: interleaved frames as a WAV's data chunk holds them, `format` one of AMUSE_PCM_*; CHANNEL 0 ONLY is read (as the
+ * front-end and kaldi read it), converted as the WAV loader converts it: U8 (x - 128) / 128, S16 x / 32768, S32 float(x) / 2^31, F32 as it is.
+ * out dev fp32 [out_capacity], the first n_out written.  Stream-ordered; allocates nothing, copies nothing, never synchronises: it can be captured.
+ * Checked before any HIP call, AMUSE_EINVAL otherwise: what amuse_resample_plan checks; channels in 1..8; a known format; out_capacity >= n_out; pointers non-NULL. */
+int amuse_resample(amuse_resampler* r, const void* pcm, int format, int channels, long long n_in, float* out, long long out_capacity, void* stream);
+/* tests: the fp32 bank of a rate pair into HOST memory, [up][taps] (sizes from amuse_resample_plan); no GPU needed */
+int amuse_debug_resample_bank(int rate_in, int rate_out, float* bank_out_host);
+
 #ifdef __cplusplus
 }
 #endif

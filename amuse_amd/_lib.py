@@ -36,6 +36,7 @@ EXPORTS = [
     "amuse_body_enable_grad", "amuse_body_vertex_loss_grad",
     "amuse_longform_plan", "amuse_stitch_windows",
     "amuse_resample_plan", "amuse_resampler_create", "amuse_resampler_destroy", "amuse_resample", "amuse_debug_resample_bank",
+    "amuse_render_plan", "amuse_renderer_create", "amuse_renderer_destroy", "amuse_render", "amuse_debug_render_raster",
 ]
 PCM_U8, PCM_S16, PCM_S32, PCM_F32 = 0, 1, 2, 3   # include/amuse_hip.h AMUSE_PCM_*
 BODY_ROT_AA, BODY_ROT_6D = 0, 1   # include/amuse_hip.h AMUSE_BODY_ROT_*
@@ -61,6 +62,17 @@ class BodyModelC(C.Structure):
     """include/amuse_hip.h `amuse_body_model` (host arrays)."""
     _fields_ = [("V", C.c_int), ("n_betas", C.c_int), ("v_template", C.POINTER(C.c_float)), ("shapedirs", C.POINTER(C.c_float)), ("posedirs", C.POINTER(C.c_float)),
                 ("J_regressor", C.POINTER(C.c_float)), ("weights", C.POINTER(C.c_float)), ("parents", C.POINTER(C.c_int))]
+
+
+class CameraC(C.Structure):
+    """include/amuse_hip.h `amuse_camera`."""
+    _fields_ = [("R", C.c_float * 9), ("t", C.c_float * 3), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("near_z", C.c_float), ("far_z", C.c_float)]
+
+
+class ShadingC(C.Structure):
+    """include/amuse_hip.h `amuse_shading`."""
+    _fields_ = [("light", C.c_float * 3), ("ambient", C.c_float), ("body_rgb", C.c_ubyte * 3), ("bg_rgb", C.c_ubyte * 3)]
 
 
 class Schedule(C.Structure):
@@ -220,6 +232,15 @@ def load() -> C.CDLL:
     lib.amuse_resample.argtypes = [vp, vp, C.c_int, C.c_int, C.c_longlong, fp, C.c_longlong, vp]
     lib.amuse_debug_resample_bank.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_float)]
     lib.amuse_resample_plan.restype = lib.amuse_resample.restype = lib.amuse_debug_resample_bank.restype = C.c_int
+    # preview rendering (csrc/amuse_render.hip): the plan needs no GPU; one renderer per (GPU, topology, image size)
+    lib.amuse_render_plan.argtypes = [C.c_int] * 6 + [ip, ip, ip, C.POINTER(C.c_size_t)]
+    lib.amuse_renderer_create.restype = vp
+    lib.amuse_renderer_create.argtypes = [C.c_int, ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+    lib.amuse_renderer_destroy.restype = None
+    lib.amuse_renderer_destroy.argtypes = [vp]
+    lib.amuse_render.argtypes = [vp, fp, C.c_int, C.POINTER(CameraC), C.POINTER(ShadingC), vp, vp, vp, vp]
+    lib.amuse_debug_render_raster.argtypes = [vp, vp, C.c_int, vp, vp]
+    lib.amuse_render_plan.restype = lib.amuse_render.restype = lib.amuse_debug_render_raster.restype = C.c_int
     if lib.amuse_abi_version() != ABI_VERSION:
         raise AmuseHipError(f"ABI mismatch: library {lib.amuse_abi_version()} vs binding {ABI_VERSION}")
     _lib = lib

@@ -20,9 +20,10 @@ NPZ_KEYS = ("v_template", "shapedirs", "posedirs", "J_regressor", "weights", "ki
 
 
 class BodyModel:
-    """v_template [V,3], shapedirs [V,3,B], posedirs [486,V*3], J_regressor [55,V], weights [V,55] (float32), parents [55] (int32, parents[0] = -1)."""
+    """v_template [V,3], shapedirs [V,3,B], posedirs [486,V*3], J_regressor [55,V], weights [V,55] (float32), parents [55] (int32, parents[0] = -1);
+    faces [T,3] (int32, optional: the mesh's triangles, which only the preview renderer reads - amuse_amd/render.py)."""
 
-    def __init__(self, v_template, shapedirs, posedirs, J_regressor, weights, parents):
+    def __init__(self, v_template, shapedirs, posedirs, J_regressor, weights, parents, faces=None):
         f = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float32))
         self.v_template, self.shapedirs, self.posedirs = f(v_template), f(shapedirs), f(posedirs)
         self.J_regressor, self.weights = f(J_regressor), f(weights)
@@ -35,10 +36,16 @@ class BodyModel:
                 raise ValueError(f"BodyModel: {k} has shape {tuple(getattr(self, k).shape)}, expected {shp}")
         if self.parents[0] != -1 or any(not (0 <= self.parents[j] < j) for j in range(1, NJ)):
             raise ValueError("BodyModel: parents must have parents[0] = -1 and 0 <= parents[j] < j")
+        self.faces = None
+        if faces is not None:
+            fc = np.asarray(faces)
+            if fc.ndim != 2 or fc.shape[1] != 3 or fc.shape[0] < 1 or int(fc.min()) < 0 or int(fc.max()) >= V:
+                raise ValueError(f"BodyModel: faces has shape {tuple(fc.shape)}: expected [T, 3] vertex indices in 0..{V - 1}")
+            self.faces = np.ascontiguousarray(fc.astype(np.int64).astype(np.int32))
 
     @classmethod
     def from_dict(cls, d: dict) -> "BodyModel":
-        return cls(d["v_template"], d["shapedirs"], d["posedirs"], d["J_regressor"], d["weights"], d["parents"])
+        return cls(d["v_template"], d["shapedirs"], d["posedirs"], d["J_regressor"], d["weights"], d["parents"], d.get("faces"))
 
     @classmethod
     def from_npz(cls, path, num_betas: int = 300) -> "BodyModel":
@@ -49,17 +56,19 @@ class BodyModel:
                 if k not in z.files:
                     raise KeyError(f"{path}: SMPL-X model file lacks the key '{k}' (needs {', '.join(NPZ_KEYS)})")
             d = {k: np.asarray(z[k]) for k in NPZ_KEYS}
+            faces = np.asarray(z["f"]) if "f" in z.files else None   # the triangles: optional, the preview renderer's only
         V = d["v_template"].shape[0]
         parents = d["kintree_table"][0].astype(np.int64)[:NJ].copy()
         parents[0] = -1   # stored as 2^32 - 1
         posedirs = np.asarray(d["posedirs"], np.float32).reshape(V * 3, -1).T
-        return cls(d["v_template"], np.asarray(d["shapedirs"])[:, :, :num_betas], posedirs, np.asarray(d["J_regressor"])[:NJ], np.asarray(d["weights"])[:, :NJ], parents)
+        return cls(d["v_template"], np.asarray(d["shapedirs"])[:, :, :num_betas], posedirs, np.asarray(d["J_regressor"])[:NJ], np.asarray(d["weights"])[:, :NJ], parents, faces)
 
     def to_npz(self, path) -> None:
         """the file layout from_npz reads (tests; a user's own models)"""
         kt = np.stack([self.parents.astype(np.int64) % (1 << 32), np.arange(NJ)]).astype(np.uint32)
+        extra = {} if self.faces is None else {"f": self.faces.astype(np.uint32)}     # written only when set: a file without it keeps its bytes
         np.savez(str(path), v_template=self.v_template, shapedirs=self.shapedirs, posedirs=self.posedirs.T.reshape(self.V, 3, 486), J_regressor=self.J_regressor,
-                 weights=self.weights, kintree_table=kt)
+                 weights=self.weights, kintree_table=kt, **extra)
 
 
 # ------------------------------------------------------------------ the float64 torch twin

@@ -28,6 +28,9 @@ Beyond the reference (which asks for 10 s WAVs, trainer.py:506): `--fn infer_ges
 floor(30 x seconds) frames - overlapping 10 s windows, sampled independently, crossfaded where they overlap (amuse_amd/longform.py).  Off by default.
 `--fn infer_gesture | edit_gesture --resample` converts a WAV of another rate to the 16 kHz the front-end is built for, in a HIP kernel
 (amuse_amd/resample.py); the reference reads every file as 16 kHz whatever its header says.  Off by default.
+`--fn infer_gesture | edit_gesture --preview --smplx-models DIR [--preview-size 512] [--preview-stride 10] [--preview-frames]` writes, beside every
+*_motion_smplx.npz, *_preview.png - a contact sheet of the posed SMPL-X mesh, rasterised in HIP (amuse_amd/render.py) - and with --preview-frames
+*_preview/frame_%04d.png.  A flat-shaded preview from a fixed front camera, not the reference's Blender render; the NPZ files keep their bytes.  Off by default.
 """
 from __future__ import annotations
 
@@ -237,6 +240,13 @@ def main(argv=None):
                          "front-end reads it - an extension, the reference drops the rate and reads every file as 16 kHz (so a 48 kHz recording is animated as "
                          "speech slowed three times).  The filter is a Hann-windowed sinc written down from memory of torchaudio's defaults, pinned against no "
                          "other implementation.  A 16 kHz file gives the bytes it gives without the switch; works with --long-form and --audio-metrics")
+    ap.add_argument("--preview", action="store_true",
+                    help="infer_gesture / edit_gesture: beside every *_motion_smplx.npz write *_preview.png, a contact sheet of the posed SMPL-X mesh rasterised in a "
+                         "HIP kernel (amuse_amd/render.py) - an extension: a flat-shaded preview from a fixed front camera, not the reference's Blender render.  Needs "
+                         "the SMPL-X model files with their triangles (--smplx-models DIR).  The NPZ files keep their bytes; works with --long-form, --resample, --gpus N")
+    ap.add_argument("--preview-size", type=int, default=512, help="--preview: pixels per side of a frame")
+    ap.add_argument("--preview-stride", type=int, default=10, help="--preview: every stride-th frame goes on the sheet")
+    ap.add_argument("--preview-frames", action="store_true", help="--preview: also write *_preview/frame_%%04d.png for every frame")
     args = ap.parse_args(argv)
     fn = args.fn[0]
     if fn not in ("infer_gesture", "edit_gesture", "train_gesture"):
@@ -246,6 +256,10 @@ def main(argv=None):
                          "SMPL-X body models")
     if args.resample and fn == "train_gesture":
         raise SystemExit("--resample belongs to --fn infer_gesture / edit_gesture: it converts the WAVs those read; the training reader is left as it is")
+    if (args.preview or args.preview_frames) and fn == "train_gesture":
+        raise SystemExit("--preview belongs to --fn infer_gesture / edit_gesture: it draws the NPZ files those write")
+    if args.preview_frames and not args.preview:
+        raise SystemExit("--preview-frames belongs to --preview")
     if args.long_form and fn != "infer_gesture":
         raise SystemExit("--long-form belongs to --fn infer_gesture: it joins the windows of one WAV into one motion; the edit tasks work on 10 s clips")
     if args.long_form:
@@ -261,6 +275,13 @@ def main(argv=None):
     if fn == "train_gesture":
         config["_ldm_cfg"] = ldm_cfg
         return train_gesture_entry(args, dirname, config)
+    preview_models = None
+    if args.preview:          # checked before anything is loaded or sampled: the model files, and their triangles
+        from . import render
+        preview_models = render.load_preview_models(Path(args.smplx_models) if args.smplx_models else dirname / "body_models" / "codebase" / "models" / "smplx")
+        if args.preview_size < 1 or args.preview_size > 1024 or args.preview_stride < 1:
+            raise SystemExit(f"--preview-size {args.preview_size} (1..1024: the renderer takes 2048 samples per axis at 2 x supersampling) / --preview-stride "
+                             f"{args.preview_stride} (>= 1)")
     from . import launch
     if args.gpus > 1 and not launch.launched_by_torchrun():
         return _launch_ranks(args, argv, dirname)
@@ -337,6 +358,14 @@ def main(argv=None):
     written = tr.eval_prior_latdiff_forward_backward_v1(baseline, ldm_epoch, audio_list, short_audio_list,
                                                         modelversion=modelversion, ammetric=True)
     torch.cuda.synchronize()
+    if preview_models is not None:      # this rank's own files: what the NPZ holds (lower body frozen, zero translation), as the reference renders the NPZ
+        from . import render
+        pv = render.Previewer(preview_models, device, args.preview_size, args.preview_stride, args.preview_frames)
+        try:
+            n_png = sum(len(pv.preview(p)) for p in written)
+        finally:
+            pv.close()
+        print(f"[amuse_amd] --preview: {n_png} PNG files beside {len(written)} NPZ files")
     print(f"AMUSE: ({fn}) completed in: {(time.time() - tic) / 3600} hrs; {len(written)} NPZ files" + (f" on rank {rank} of {world}" if world > 1 else ""))
     if world > 1 and os.environ.get("AMUSE_MANIFEST_DIR"):      # the launcher collects what the ranks wrote
         Path(os.environ["AMUSE_MANIFEST_DIR"], f"rank{rank}.json").write_text(json.dumps([str(p) for p in written]))

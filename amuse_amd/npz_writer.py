@@ -1,5 +1,6 @@
 """SMPL-X NPZ output of the reference (models/diffusion/viz/visualizer.py:344-364) and the output
-packing of its call sites (scripts/trainer.py:524-526).  Rendering (Blender / ffmpeg) is out of scope."""
+packing of its call sites (scripts/trainer.py:524-526).  Rendering (Blender / ffmpeg) is out of scope; amuse_amd/render.py
+draws a preview of what these files hold (poses, trans, betas, gender), opt-in."""
 from __future__ import annotations
 
 import os

@@ -15,6 +15,7 @@ clip axis and sampled in one launch; job j's clips get the global clip indices t
 handed out had the calls been made one by one, so the batched result is the sequential one (bitwise up to 128 clips per
 launch: one clip per workgroup tile in both cases).  Rendering (Blender / ffmpeg, wav export) is out of scope: outputs
 stop at the `*_motion_smplx.npz` files `CaMNVisualizer.animate_ldm_sample_v1/v2` write first (npz_writer.write_sample).
+(`main.py --preview` draws those files afterwards - amuse_amd/render.py, a flat-shaded preview rasterised in HIP; nothing here calls it.)
 
 More than one GPU (`main.py --fn infer_gesture | edit_gesture --gpus N`; the reference refuses multi-GPU inference,
 models/audio/infer_pretrained_ast_evp.py:45): one process per GPU, every rank builds the SAME job list and takes a contiguous

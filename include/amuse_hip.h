@@ -711,6 +711,51 @@ int amuse_resample(amuse_resampler* r, const void* pcm, int format, int channels
 /* tests: the fp32 bank of a rate pair into HOST memory, [up][taps] (sizes from amuse_resample_plan); no GPU needed */
 int amuse_debug_resample_bank(int rate_in, int rate_out, float* bank_out_host);
 
+/* ------------------------------------------------------------------ preview rendering (csrc/amuse_render_host.hpp, amuse_render.hip, k_render.hip; amuse_amd/render.py)
+ * AN EXTENSION, off by default: the reference hands its NPZ to Blender and ffmpeg; this is a PREVIEW - the posed mesh flat-shaded from one fixed camera -
+ * and matches no other renderer's image.  Once the vertices are snapped to the sub-sample grid, coverage and depth are integer arithmetic, so the winning
+ * triangle of every sample is a pure function of the snapped vertices (tests/render_ref.py restates it in numpy int64, bit for bit).
+ *
+ * Camera: x_cam = R x + t (R row-major), looking down +z; u = fx x / z + cx, v = cy - fy y / z; near_z, far_z bound the depth range.
+ * Screen record of a vertex, int32 (X, Y, Zq), with ss in {1, 2} the supersampling factor per axis:
+ *   X = rint(16 ss u), Y = rint(16 ss v): fp32, round half to even (4 sub-sample bits); the view-space position is fp32 fma chains, t added first
+ *   Zq = floor(zndc (2^24 - 1) + 0.5), zndc = far (z - near) / (z (far - near)) - linear in screen space - computed in DOUBLE from the fp32 vertex (with its own
+ *        double z): 24 bits of depth do not survive fp32 roundings
+ *   invalid - stored as (0, 0, -1) - for z < near, z > far, a non-finite coordinate, or X / Y outside [-32768, 65535] (the guard band).  A caller-made record
+ *   (amuse_debug_render_raster) is invalid when Zq is outside 0 .. 2^24 - 1 or X / Y outside the guard band.
+ * Triangle t (vertices a, b, c): skipped when a vertex is invalid or the doubled area A2 = (Xb - Xa)(Yc - Ya) - (Yb - Ya)(Xc - Xa) is 0; b and c are swapped
+ * when A2 < 0 (two-sided: no culling).  Sample (sx, sy) has its centre at P = (16 sx + 8, 16 sy + 8).  Edge functions, int64, for the edge p -> q:
+ * E(P) = (Xq - Xp)(Py - Yp) - (Yq - Yp)(Px - Xp); w_c = E_ab, w_a = E_bc, w_b = E_ca, w_a + w_b + w_c = A2.  Covered: all three >= 0, and where one is 0 its
+ * edge must be a top edge (Yq == Yp, Xq > Xp) or a left edge (Yq < Yp) - the D3D11 top-left rule in a y-down frame.
+ *   zpix = (w_a Zq_a + w_b Zq_b + w_c Zq_c) div A2 (floor, int64: A2 < 2^35 inside the guard band, so the numerator stays below 2^59)
+ *   key = (zpix << 32) | t;  the sample's winner is the MINIMUM key (nearest, ties to the lower index); an empty sample holds all ones.
+ * Shading of a sample, fp32: n = (p_b - p_a) x (p_c - p_a) of the winner's view-space positions, c = ambient + (1 - ambient) |n . l| / |n| (c = ambient when
+ * |n| = 0), l the unit light direction; channel = floor(body_rgb c + 0.5); an empty sample is bg_rgb.  ss = 2: pixel = (s00 + s01 + s10 + s11 + 2) >> 2 per
+ * channel on the uint8 samples.  Defaults (shading NULL): light (0, 0, -1) - a headlight -, ambient 0.25, body (200, 200, 208), background (32, 32, 36).
+ * Limits: width ss and height ss in 1 .. 2048, V >= 1, T >= 1 (an int: below 2^32).
+ *
+ * amuse_render_plan: the plan, stated once; needs no GPU.  Tiles of 32 x 32 samples: *tiles_x = ceil(width ss / 32), *tiles_y = ceil(height ss / 32).  A call's
+ * frames are processed *chunk_frames at a time: min(frames, 256, max(1, floor(16 MiB / (24 V)))); *workspace_bytes = the records and view positions of one chunk
+ * (2 x chunk_frames x 12 V bytes, each rounded up to 256).  Any output pointer may be NULL. */
+typedef struct amuse_renderer amuse_renderer;
+typedef struct { float R[9], t[3], fx, fy, cx, cy, near_z, far_z; } amuse_camera;
+typedef struct { float light[3], ambient; unsigned char body_rgb[3], bg_rgb[3]; } amuse_shading;
+int amuse_render_plan(int width, int height, int ss, int V, int T, int frames, int* tiles_x, int* tiles_y, int* chunk_frames, size_t* workspace_bytes);
+/* One renderer per (GPU, mesh topology, image size): uploads the faces (host int [T][3], every index in 0 .. V - 1).  NULL on failure (amuse_last_error). */
+amuse_renderer* amuse_renderer_create(int device, const int* faces, int T, int V, int width, int height, int ss);
+void amuse_renderer_destroy(amuse_renderer* r);
+/* M frames.  vertices dev [M][V][3] (amuse_body_forward's vertices_out, flattened over clips); rgb_out dev uint8 [M][height][width][3]; keys_out (nullable) dev
+ * [M][height ss][width ss] the winning keys; screen_out (nullable) dev int [M][V][3] the screen records.  shading NULL = the defaults above.
+ * The workspace follows amuse_body_reserve's rules: sized on first use, grows only, nothing freed before destroy; after the first call of a given M (beyond
+ * chunk_frames all sizes are one) a call is stream-ordered, allocates nothing and synchronises nothing.  One workspace per renderer: its calls must not overlap
+ * on two streams.  Bitwise reproducible: no float atomics, the minimum of packed integers does not depend on arrival order.
+ * Checked before any HIP call, AMUSE_EINVAL otherwise: r, vertices, camera, rgb_out non-NULL; M >= 1; 0 < near_z < far_z and every camera number finite;
+ * a light direction of non-zero finite length and 0 <= ambient <= 1 when shading is given. */
+int amuse_render(amuse_renderer* r, const float* vertices_dev, int M, const amuse_camera* camera, const amuse_shading* shading, unsigned char* rgb_out_dev,
+                 unsigned long long* keys_out_dev, int* screen_out_dev, void* stream);
+/* tests: the raster stage alone, from caller-made screen records dev int [M][V][3]: keys only, dev [M][height ss][width ss].  Uses no workspace. */
+int amuse_debug_render_raster(amuse_renderer* r, const int* screen_dev, int M, unsigned long long* keys_out_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

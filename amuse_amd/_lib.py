@@ -37,6 +37,7 @@ EXPORTS = [
     "amuse_longform_plan", "amuse_stitch_windows",
     "amuse_resample_plan", "amuse_resampler_create", "amuse_resampler_destroy", "amuse_resample", "amuse_debug_resample_bank",
     "amuse_render_plan", "amuse_renderer_create", "amuse_renderer_destroy", "amuse_render", "amuse_debug_render_raster",
+    "amuse_motion_metrics_row", "amuse_motion_metrics",
 ]
 PCM_U8, PCM_S16, PCM_S32, PCM_F32 = 0, 1, 2, 3   # include/amuse_hip.h AMUSE_PCM_*
 BODY_ROT_AA, BODY_ROT_6D = 0, 1   # include/amuse_hip.h AMUSE_BODY_ROT_*
@@ -241,6 +242,10 @@ def load() -> C.CDLL:
     lib.amuse_render.argtypes = [vp, fp, C.c_int, C.POINTER(CameraC), C.POINTER(ShadingC), vp, vp, vp, vp]
     lib.amuse_debug_render_raster.argtypes = [vp, vp, C.c_int, vp, vp]
     lib.amuse_render_plan.restype = lib.amuse_render.restype = lib.amuse_debug_render_raster.restype = C.c_int
+    # motion metrics (csrc/amuse_motion_metrics.hip): context-free, one launch
+    lib.amuse_motion_metrics_row.argtypes = []
+    lib.amuse_motion_metrics.argtypes = [fp, fp, vp, C.c_int, C.c_int, vp, vp]
+    lib.amuse_motion_metrics_row.restype = lib.amuse_motion_metrics.restype = C.c_int
     if lib.amuse_abi_version() != ABI_VERSION:
         raise AmuseHipError(f"ABI mismatch: library {lib.amuse_abi_version()} vs binding {ABI_VERSION}")
     _lib = lib

@@ -247,6 +247,12 @@ def main(argv=None):
     ap.add_argument("--preview-size", type=int, default=512, help="--preview: pixels per side of a frame")
     ap.add_argument("--preview-stride", type=int, default=10, help="--preview: every stride-th frame goes on the sheet")
     ap.add_argument("--preview-frames", action="store_true", help="--preview: also write *_preview/frame_%%04d.png for every frame")
+    ap.add_argument("--motion-metrics", action="store_true",
+                    help="edit tasks on the dataset (--eval-data): after every task, APE / AVE / velocity / acceleration on posed SMPL-X joints (summed per clip in a HIP "
+                         "kernel) and FID / Diversity on the motion prior's latents, between every generated motion and its source motion, written to "
+                         "<model_path>/viz/motion_metrics_<stamp>_E<epoch>.json (amuse_amd/motion_metrics.py) - an extension: the reference's val_metrics.py cannot "
+                         "run and its trainer passes metricsmodel=None.  Needs the SMPL-X model files (--smplx-models DIR); works under metrics_only: True")
+    ap.add_argument("--metrics-diversity-times", type=int, default=300, help="--motion-metrics: clips per index set of the Diversity draw (it needs more clips than this)")
     args = ap.parse_args(argv)
     fn = args.fn[0]
     if fn not in ("infer_gesture", "edit_gesture", "train_gesture"):
@@ -260,6 +266,17 @@ def main(argv=None):
         raise SystemExit("--preview belongs to --fn infer_gesture / edit_gesture: it draws the NPZ files those write")
     if args.preview_frames and not args.preview:
         raise SystemExit("--preview-frames belongs to --preview")
+    if args.motion_metrics:
+        if fn == "train_gesture":
+            raise SystemExit("--motion-metrics belongs to --fn infer_gesture / edit_gesture: it evaluates the pairs the edit tasks collect")
+        if not args.smplx_models:
+            raise SystemExit("--motion-metrics needs --smplx-models DIR: APE / AVE are taken on the joints the SMPL-X body models pose")
+        from . import body
+        if not body.models_present(args.smplx_models):      # checked before anything is loaded or sampled
+            raise SystemExit(f"--motion-metrics: {', '.join(body.SMPLX_FILES.values())} were not all found in {args.smplx_models} (--smplx-models DIR names the "
+                             "directory)")
+        if args.metrics_diversity_times < 1:
+            raise SystemExit(f"--metrics-diversity-times {args.metrics_diversity_times}: at least 1")
     if args.long_form and fn != "infer_gesture":
         raise SystemExit("--long-form belongs to --fn infer_gesture: it joins the windows of one WAV into one motion; the edit tasks work on 10 s clips")
     if args.long_form:
@@ -295,7 +312,7 @@ def main(argv=None):
     if args.all_pairs:
         tp["test"].setdefault("emotion_control_list", {})["all_pairs"] = True
     pg = False
-    if world > 1 and fn == "edit_gesture" and tp["test"].get("emotion_control_list", {}).get("all_pairs"):
+    if world > 1 and (args.motion_metrics or (fn == "edit_gesture" and tp["test"].get("emotion_control_list", {}).get("all_pairs"))):
         # the ONE exchange of the inference path: S sources x T targets - every rank's jobs read most WAVs, so each rank embeds a share and
         # the embeddings (3 x 256 floats per WAV) are all-gathered.  RCCL between the GPUs; gloo when the ranks share a device (tests).
         import torch.distributed as dist
@@ -345,6 +362,11 @@ def main(argv=None):
         tp["test"]["resample"] = True
     if args.long_form:       # (the keys are this path's own; without the switch the configuration is left as it is)
         tp["test"]["long_form"], tp["test"]["hop_frames"] = True, int(args.hop_frames)
+    metric_models = None
+    if args.motion_metrics:  # (the keys are this path's own; without the switch the configuration is left as it is)
+        from . import body
+        tp["test"]["motion_metrics"], tp["test"]["metrics_diversity_times"] = True, int(args.metrics_diversity_times)
+        metric_models = body.load_models(args.smplx_models)
     model.precision = args.precision
     print(f"[amuse_amd] sampler / decoder precision: {args.precision}; audio front-end precision: {args.audio_precision}"
           + (" (split-fp16 AST encoders: with --precision fp32 / fp32x the run is in parity from the waveform)" if args.audio_precision == "fp32x"
@@ -354,7 +376,7 @@ def main(argv=None):
     eval_loader = torch.load(args.eval_data, weights_only=False) if args.eval_data else None
     tr = trainer(config, device, train_loader=eval_loader, model_path=model_path, tag="LPDM_infer", logger_cfg=None,
                  model=model, processed=processed, metricsmodel=None, b_path=None, EXEC_ON_CLUSTER=False,
-                 debug=tp.get("debug", True), pretrained_infer=True, rank=rank, world=world)
+                 debug=tp.get("debug", True), pretrained_infer=True, rank=rank, world=world, body_models=metric_models)
     written = tr.eval_prior_latdiff_forward_backward_v1(baseline, ldm_epoch, audio_list, short_audio_list,
                                                         modelversion=modelversion, ammetric=True)
     torch.cuda.synchronize()

@@ -339,7 +339,7 @@ class trainer:
     def __init__(self, config, device, train_loader=None, val_loader=None, model_path=None, tag="LPDM_infer",
                  logger_cfg=None, model=None, processed=None, metricsmodel=None, b_path=None, EXEC_ON_CLUSTER=False,
                  debug=False, pretrained_infer=True, batched=True, rank: Optional[int] = None, world: Optional[int] = None,
-                 stamp: Optional[str] = None):
+                 stamp: Optional[str] = None, body_models: Optional[dict] = None):
         if tag != "LPDM_infer" or not pretrained_infer:
             raise NotImplementedError("amuse_amd.trainer mirrors the evaluation entry points (tag LPDM_infer); training: "
                                       "amuse_amd/train_gesture.py")
@@ -378,6 +378,9 @@ class trainer:
             self.style_Xemo_transfer_emotion = test["style_Xemo_transfer"]["emotion"]
         self.demo_emotion_control = use("emotion_control_list")
         self.written: List[Path] = []
+        # TRAIN_PARAM.test.motion_metrics (amuse_amd.main --motion-metrics; an extension, amuse_amd/motion_metrics.py): the SMPL-X models the joint half poses
+        self.body_models = body_models
+        self._mm_body, self._mm_tasks, self.motion_metrics_path = None, {}, None
 
     # ------------------------------------------------------------------ visualizer stand-in
     def _animate(self, sample_dict, video_dump, n_clips: int = 1):
@@ -508,6 +511,51 @@ class trainer:
             jobs.append(_job("scott", a.stem, con, emo, sty, W, "scott", None, None, None, long_form=lf))
         return jobs, mine
 
+    # ------------------------------------------------------------------ motion metrics (opt-in)
+    def _motion_metrics_on(self) -> bool:
+        return bool(self.config["TRAIN_PARAM"]["test"].get("motion_metrics", False)) and self.body_models is not None
+
+    def _motion_metrics_task(self, name: str) -> None:
+        """TRAIN_PARAM.test.motion_metrics: what the reference's metricsmodel=None never does - the pairs run_jobs just collected in self.metrics[name] that carry
+        a src_motion go through amuse_amd.motion_metrics.MotionMetrics (joints of both motions -> APE / AVE / velocity / acceleration sums in HIP; mu of both ->
+        FID / Diversity).  One accumulator per task, kept across replication_times.  Reads self.metrics, changes nothing in it."""
+        from . import body, motion_metrics as mm
+        if self._mm_body is None:
+            ver = self.config["TRAIN_PARAM"]["test"].get("metrics_dataset_version", "v0")
+            self._mm_body = body.BodyLosses(self.body_models, self.device, version=ver)
+        if name not in self._mm_tasks:
+            self._mm_tasks[name] = mm.MotionMetrics(self.model, self._mm_body)
+        for m in self.metrics.get(name, []):
+            if m["src_motion"] is None:
+                continue
+            rst = torch.as_tensor(m["rst_motion"])
+            src = torch.as_tensor(m["src_motion"])[:rst.shape[0]]
+            n = min(int(src.shape[0]), int(rst.shape[0]))
+            if n:
+                self._mm_tasks[name].update(rst[:n], src[:n], [(m["actor"],)] * n)
+
+    def _motion_metrics_write(self, ldm_epoch) -> Optional[Path]:
+        """<model_path>/viz/motion_metrics_<stamp>_E<epoch>.json.  More than one rank: the additive states are all-gathered and rank 0 writes; ranks that run
+        without a process group each write their own share, named by rank."""
+        from . import motion_metrics as mm
+        states = {name: ev.state() for name, ev in self._mm_tasks.items()}
+        suffix = ""
+        if self.world > 1:
+            if _dist_ready():
+                import torch.distributed as dist
+                parts = [None] * self.world
+                dist.all_gather_object(parts, states)
+                if self.rank != 0:
+                    return None
+                states = {name: mm.merge_states([p[name] for p in parts if name in p]) for name in sorted({k for p in parts for k in p})}
+            else:
+                suffix = f"_rank{self.rank}"
+        path = self.model_path / "viz" / f"motion_metrics_{self.stamp}_E{ldm_epoch}{suffix}.json"
+        times = int(self.config["TRAIN_PARAM"]["test"].get("metrics_diversity_times", 300))
+        self.motion_metrics_path = mm.write_report(path, states, str(getattr(self.model, "precision", "")), times, seed=self.config["TRAIN_PARAM"].get("seed", 0))
+        print(f"[amuse_amd] motion metrics: {self.motion_metrics_path}")
+        return self.motion_metrics_path
+
     # ------------------------------------------------------------------ infer_gesture
     def _infer_prior_latdiff_from_audio_v1(self, baseline, ldm_epoch, audio_list, short_audio_list, modelversion, ammetric):
         start_time = time.time()
@@ -589,6 +637,8 @@ class trainer:
                                            "rst_info": j["info"], "src_motion": j["src_motion"], "rst_motion": r["feats"],
                                            "audio": j["audio"], "z_con": j["z_con"], "z_emo": j["z_emo"], "z_sty": j["z_sty"]}
                                           for j, r in zip(jobs, rst) if r is not None]
+                    if self._motion_metrics_on():
+                        self._motion_metrics_task(name)
                     if not metrics_only:
                         video_dump_r = self.model_path / "viz" / f"{name}_{run_info}_{self.stamp}_E{ldm_epoch}" / f"rep{rep_i}"
                         assert self.viz_type in ["CaMN"], "[LDM EVAL] Invalid viz type: [%s]" % self.viz_type
@@ -629,4 +679,9 @@ class trainer:
                         print(f"VISUALIZATION: LIST AUDIOS {i} =====>")
                     self._animate(sample_dict, video_dump_r / f"rst_{i}")
                 print(f"END VISUALIZATION: DEMO EMOTION CONTROL {rep_i + 1}/{reps} =====>")
+        if self._motion_metrics_on():
+            self._motion_metrics_write(ldm_epoch)
+            if self._mm_body is not None:
+                self._mm_body.close()
+                self._mm_body = None
         return self.written

@@ -756,6 +756,38 @@ int amuse_render(amuse_renderer* r, const float* vertices_dev, int M, const amus
 /* tests: the raster stage alone, from caller-made screen records dev int [M][V][3]: keys only, dev [M][height ss][width ss].  Uses no workspace. */
 int amuse_debug_render_raster(amuse_renderer* r, const int* screen_dev, int M, unsigned long long* keys_out_dev, void* stream);
 
+/* ------------------------------------------------------------------ motion metrics (csrc/amuse_motion_metrics_host.hpp, amuse_motion_metrics.hip, k_motion_metrics.hip; amuse_amd/motion_metrics.py)
+ * AN EXTENSION, off by default: the reference states the intent (models/latent_diffusion/utils/val_metrics.py ComputeMetrics: APE / AVE on joints) in a file
+ * that cannot run - torchmetrics is absent and its helpers are defined nowhere - and passes metricsmodel=None.  The variance below is a RECOLLECTION of MLD's
+ * variance(x, T, dim=0), pinned only against its own float64 restatement (tests/motion_metrics_ref.py).  The velocity / acceleration sums are this project's
+ * addition: val_metrics.py has no jitter measure.
+ *
+ * Per clip n with L = lengths_dev[n] frames, G / R the generated / reference joints [F][55][3] as amuse_body_forward writes joints_out (metres, y up), root =
+ * joint 0, traj = components (0, 2) of the root, local[f][j] = X[f][j] - X[f][0].  ONLY frames f < L are read into any result; frames at or beyond L may hold
+ * anything, NaN included.  var(x) = sum_f (x_f - mean)^2 / (L - 1) per coordinate, two-pass (the mean first, then the deviations).  |.| is the L2 norm.
+ * One row of amuse_motion_metrics_row() = 442 doubles per clip:
+ *   offset  length  block
+ *        0       1  ape_root    sum_{f<L} |G[f][0] - R[f][0]|
+ *        1       1  ape_traj    the same on traj (2 components)
+ *        2      54  ape_pose    sum_f |local_G[f][j] - local_R[f][j]|, j = 1..54
+ *       56      55  ape_joints  sum_f |G[f][j] - R[f][j]|, j = 0..54
+ *      111       1  ave_root    |var(G[:][0]) - var(R[:][0])| (3 components)
+ *      112       1  ave_traj    the same on traj
+ *      113      54  ave_pose    |var(local_G[:][j]) - var(local_R[:][j])|, j = 1..54
+ *      167      55  ave_joints  |var(G[:][j]) - var(R[:][j])|
+ *      222      55  vel_gen     sum_{f=1}^{L-1} |G[f][j] - G[f-1][j]|
+ *      277      55  vel_ref     the same on R
+ *      332      55  acc_gen     sum_{f=1}^{L-2} |G[f+1][j] - 2 G[f][j] + G[f-1][j]| (0 when L = 2)
+ *      387      55  acc_ref     the same on R
+ * Inputs are fp32; every operation after the load is double.  One workgroup per clip, no atomics; the order of every sum depends on L alone, so a clip's row
+ * does not depend on N or on the clip's position in the batch: same clip, same bits.
+ * Context-free and stream-ordered; no allocation, no copy, no host synchronisation: it can be captured.
+ * Checked before any HIP call, AMUSE_EINVAL otherwise: every pointer non-NULL; N >= 1; F >= 2; N F and 442 N within an int.
+ * The lengths live on the DEVICE - the host cannot see them without a synchronisation - so they are checked there: a clip whose length lies outside 2..F gets
+ * a row of 442 NaN, reads nothing and harms no other clip. */
+int amuse_motion_metrics_row(void);
+int amuse_motion_metrics(const float* joints_gen, const float* joints_ref, const int* lengths_dev, int N, int F, double* rows_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

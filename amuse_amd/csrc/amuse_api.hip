@@ -401,7 +401,7 @@ int amuse_set_clips_per_group(amuse_ctx* c, int g) {
 int amuse_set_sample_dropout(amuse_ctx* c, float p, uint64_t seed) {
     if (!(p >= 0.f) || p >= 1.f) return fail(AMUSE_EINVAL, "dropout probability %g outside [0, 1)", (double)p);
     if (!c) return fail(AMUSE_EINVAL, "ctx is NULL");
-    c->drop_thr = (uint32_t)(p * 16777216.0f);   // k_train.hip drop_args
+    c->drop_thr = (uint32_t)(p * 16777216.0f);   // amuse_train.hip drop_args
     c->drop_scale = 1.0f / (1.0f - p);
     c->drop_seed = seed;
     return 0;
@@ -410,7 +410,7 @@ int amuse_set_sample_dropout(amuse_ctx* c, float p, uint64_t seed) {
 int amuse_set_decode_dropout(amuse_ctx* c, float p, uint64_t seed, uint64_t clip_index0) {
     if (!(p >= 0.f) || p >= 1.f) return fail(AMUSE_EINVAL, "dropout probability %g outside [0, 1)", (double)p);
     if (!c) return fail(AMUSE_EINVAL, "ctx is NULL");
-    c->dec_drop_thr = (uint32_t)(p * 16777216.0f);   // k_train.hip drop_args
+    c->dec_drop_thr = (uint32_t)(p * 16777216.0f);   // amuse_train.hip drop_args
     c->dec_drop_scale = 1.0f / (1.0f - p);
     c->dec_drop_seed = seed;
     c->dec_drop_clip0 = clip_index0;

@@ -307,13 +307,61 @@ struct DenFusedArgs {
 hipError_t launch_den_fused(const DenFusedArgs& a, hipStream_t stream);
 hipError_t launch_den_fusedh(const DenFusedArgs& a, hipStream_t stream);   // fp16 operands (k_den_fusedh.hip)
 // feats[row][0:330] = first two rows of R(axis-angle) per joint, feats[row][330:333] = trans   (infer_ldm.py:459-464)
-// training step (k_train.hip): the per-device dropout epoch word every mask-drawing kernel reads (0 unless a captured step advances it)
+// training step (amuse_train.hip's per-device state): the dropout epoch word every mask-drawing kernel reads (0 unless a captured step advances it); null: none could be made
 uint32_t* train_epoch_ptr();
+// ... and the split-k workspace of launch_train_gemm_any (`floats` of it, allocated on the first call) of the current device and the calling thread's lane
+hipError_t train_splitk_ws(size_t floats, float** ws);
 // training step (k_train_gemm.hip): out[M][N] = (bias | accumulate: out) + a[M][K] . (tb ? b[N][K]^T : b[K][N]) for the tall fp32 projections it takes
 bool train_gemm_tall_takes(long M, long N, long K, bool tb, bool bias);
 // ... and for every other shape / transpose of the step (the 333-wide layers, 32- and 160-row projections, weight gradients): the same file's generic kernel
 hipError_t launch_train_gemm_any(const float* a, const float* b, const float* bias, float* out, long M, long N, long K, bool ta, bool tb, bool accumulate, hipStream_t stream);
 hipError_t launch_train_gemm_tall(const float* a, const float* b, const float* bias, float* out, long M, long N, long K, bool tb, bool accumulate, hipStream_t stream);
+// training step (k_train.hip): one launcher per kernel, the only place that states the kernel's grid, block and clamp.  Each returns an AMUSE_* code (0 = launched); the
+// mask-drawing ones (thr = p 2^24, scale = 1 / (1 - p)) hand the kernel the epoch word and return AMUSE_EHIP when there is none.
+constexpr int kTrainWgs = 256;                            // workgroups (at most) of the kernels with column sums = rows of their partial-sum workspace
+constexpr size_t kTrainWsRegion = (size_t)kTrainWgs * 1024;   // floats of one reduction's partial sums (amuse_train_ws_floats: 8 regions)
+constexpr int kWgradMaxChunks = 64;                       // partial blocks of a weight gradient (a workgroup takes every 64th chunk beyond that)
+constexpr int kWgradRows = 192;                           // rows per chunk (48 k-steps of the fp32 MFMA; 304-row chunks - one wave per SIMD at 9,600 rows - measured slower: 22.9 against 21.9 us;
+                                                          // so did a workgroup's four waves taking four consecutive chunks of ONE block and adding them up through LDS - a quarter of the partials, but no
+                                                          // operand shared between the waves any more: 26.8 us)
+// what a layer's ONE summing launch adds up: column-sum jobs (a workgroup each) and weight gradients' chunk partials (workgroups blk0 .. of 256 float4 columns)
+struct FinJob {
+    const float* ws;
+    float* o[3];
+    int n, ncol, C;
+};
+struct WsumJob {
+    const float* part;
+    float* out;
+    int chunks;
+    unsigned n4, blk0;
+};
+struct TrainSums {
+    FinJob j[8];
+    WsumJob w[6];
+    int nj, nw;
+    unsigned blocks;   // of the weight-gradient jobs so far
+};
+int launch_train_ln_fwd(const float* x, const float* y, const float* bias, const float* gamma, const float* beta, uint32_t thr, float scale, uint64_t seed, uint64_t off,
+                        long rows, float* out, float* zhat, float* rstd, hipStream_t st);
+int launch_train_ln_bwd(const float* dout, const float* dout2, const float* zhat, const float* rstd, const float* gamma, uint32_t thr, float scale, uint64_t seed, uint64_t off,
+                        long rows, float* dx, float* dy, float* ws, int* wgs, hipStream_t st);
+int launch_train_finalize(const float* ws, int n, float* o0, float* o1, float* o2, int ncol, int C, hipStream_t st);
+int launch_train_layer_sums(const TrainSums& sums, hipStream_t st);
+int launch_train_bgd_fwd(const float* h, const float* b, uint32_t thr, float scale, uint64_t seed, uint64_t off, long rows, int F, float* out, hipStream_t st);
+int launch_train_bgd_bwd(const float* da, const float* h, const float* b, uint32_t thr, float scale, uint64_t seed, uint64_t off, long rows, int F, float* dh, float* ws, int* wgs,
+                         hipStream_t st);
+int launch_train_colsum(const float* x, long rows, int C, float* ws, int* wgs, hipStream_t st);
+int launch_train_colsum_any(const float* x, long rows, int C, float* out, float* ws, hipStream_t st);
+int launch_train_bias_rows(const float* bias, long rows, int C, float* out, hipStream_t st);
+int launch_train_vk(const float* c, uint32_t thr, float scale, uint64_t seed, uint64_t off, long rows, int S, int H, float* vk, hipStream_t st);
+int launch_train_dc(const float* dvk, uint32_t thr, float scale, uint64_t seed, uint64_t off, int B, int S, int H, float* dc, hipStream_t st);
+int launch_train_adamw(float* p, const float* g, float* m, float* v, size_t n, float step_size, float decay, float omb1, float b2, float omb2, float eps, float rbc2, hipStream_t st);
+int launch_train_adamw_scalars(long* step, double lr, double b1, double b2, float* scal, hipStream_t st);
+int launch_train_adamw_dev(float* p, const float* g, float* m, float* v, size_t n, const float* scal, float decay, float omb1, float b2, float omb2, float eps, hipStream_t st);
+int launch_train_epoch_set(uint32_t add, uint32_t set, int do_set, hipStream_t st);
+int launch_train_wgrad(const float* dy, const float* x, float* dst, long rows, long M, long N, long chunks, hipStream_t st);
+int launch_train_wgrad_sum(const float* part, int chunks, size_t n4, float* out, hipStream_t st);
 hipError_t launch_smplx_to_feats(const float* poses, const float* trans, size_t nrows, float* feats, hipStream_t stream);
 // mu = stats[b][0], std = exp(stats[b][1]) ** 0.5, latent = mu + std * eps   (vae.py:209-213)
 hipError_t launch_vae_latent(const float* stats, const float* eps, float* mu, float* std, float* latent, int B,

@@ -97,7 +97,7 @@ struct AttnArgs {
     int B, S;
     uint32_t thr, key;
     float drop_scale;
-    const uint32_t* epoch;   // the device-side dropout epoch (k_train.hip train_epoch_ptr): mixed into the key, fresh masks per replay of a captured step
+    const uint32_t* epoch;   // the device-side dropout epoch (amuse_train.hip train_epoch_ptr): mixed into the key, fresh masks per replay of a captured step
 };
 constexpr float kScaleLog2 = 0.17677669529663687f * 1.44269504088896340736f;   // 1 / sqrt(32) . log2 e
 
@@ -303,6 +303,15 @@ int attn_args(AttnArgs* a, const float* qkv, float* o, float* lse, const float* 
     if (!a->epoch) return fail(AMUSE_EHIP, "attention: no device word for the dropout epoch");
     return 0;
 }
+// both kernels' dynamic LDS sizes, once per device and entry point (each entry point keeps a DeviceOnce of its own)
+int attn_lds_once(DeviceOnce& once) {
+    int dev;
+    if (once.done(&dev)) return 0;
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn_fwd<false>), hipFuncAttributeMaxDynamicSharedMemorySize, kFwdLds));
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn_bwd), hipFuncAttributeMaxDynamicSharedMemorySize, kBwdLds));
+    once.set(dev);
+    return 0;
+}
 
 }  // namespace
 }  // namespace amuse
@@ -316,12 +325,7 @@ int amuse_train_attn_fwd(const float* qkv, int B, int S, float p, uint64_t seed,
     if (int e = attn_args(&a, qkv, o, lse, nullptr, nullptr, B, S, p, seed, offset)) return e;
     a.mask_out = mask_debug;
     static DeviceOnce once;
-    int dev_;
-    if (!once.done(&dev_)) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn_fwd<false>), hipFuncAttributeMaxDynamicSharedMemorySize, kFwdLds));
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn_bwd), hipFuncAttributeMaxDynamicSharedMemorySize, kBwdLds));
-        once.set(dev_);
-    }
+    if (int e = attn_lds_once(once)) return e;
     // two workgroups per (clip, head) while that fills the chip; eight waves each (two per SIMD: one's softmax under the other's MFMAs)
     const int parts = (S > 64 && B * 4 < 512) ? 2 : 1;
     if (mask_debug) {
@@ -340,12 +344,7 @@ int amuse_train_attn_bwd(const float* qkv, const float* o, const float* lse, con
     if (!dout || !dqkv) return fail(AMUSE_EINVAL, "amuse_train_attn_bwd: NULL argument");
     if (int e = attn_args(&a, qkv, const_cast<float*>(o), const_cast<float*>(lse), dout, dqkv, B, S, p, seed, offset)) return e;
     static DeviceOnce once;
-    int dev_;
-    if (!once.done(&dev_)) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn_fwd<false>), hipFuncAttributeMaxDynamicSharedMemorySize, kFwdLds));
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn_bwd), hipFuncAttributeMaxDynamicSharedMemorySize, kBwdLds));
-        once.set(dev_);
-    }
+    if (int e = attn_lds_once(once)) return e;
     hipLaunchKernelGGL(k_attn_bwd, dim3(2 * B * 4), dim3(512), kBwdLds, (hipStream_t)stream, a);
     HIP_TRY(hipGetLastError());
     return 0;

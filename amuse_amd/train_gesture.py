@@ -266,7 +266,7 @@ class GestureTrainer:
         # the multi-tensor ("fused") AdamW of torch on the GPU: the same update in a handful of launches instead of ~10 per
         # parameter group of the default foreach path (2.7 ms of device time and 4.8 ms of host time per iteration, section 4.6)
         # ... and on the GPU that update is ONE launch per contiguous run of optimizer parameters in the flat buffers (train_ops.FlatAdamW, csrc/k_train.hip);
-        # optimizer = "fused" / "foreach" select torch's own implementations (A/B: tools/gpu_train_variants.py)
+        # optimizer = "fused" / "foreach" select torch's own implementations (A/B: profiles/r02_train_variants.txt)
         opt_kind = optimizer if self.device.type == "cuda" else "foreach"
         opt_params = [p for p in self.params if id(p) not in unused]
         if opt_kind == "flat":

@@ -12,6 +12,11 @@
 // event and stream.  Pointers are printed so that the text is the same on any machine: `0`, `dev#<n>+<offset>/<block size>` inside the process's n-th hipMalloc block while it is live,
 // `<name>+<offset>` inside a buffer the driver registered (amuse_stub_name), `host` otherwise; streams and events by their order of creation; weight streams also
 // by image digest, stage tables as digests.  That pins what the image log leaves open: workspace carving, chunk offsets, the hoist launches and launch order.
+// The raw launch log (amuse_stub_log(3); tests/test_train_launch_args_cpu.py): the launch log, and beneath the launchers: the training step's translation units are
+// linked as they are, so their kernels register here (__hipRegisterFunction hands over each kernel's mangled name) and every <<< >>> arrives as hipLaunchKernel -
+// one line with the kernel's name, grid, block, dynamic LDS, stream and, through the driver's table of parameter letters (amuse_stub_kernel_params), its arguments.
+// Stream / event creation, hipFuncSetAttribute and hipDeviceSynchronize print a line at this level too.  amuse_stub_fail_at(n) makes the n-th of these calls and
+// launches fail (a failed launch is what the next hipGetLastError returns).
 // The audio front-end's launchers print into the launch log only (tests/test_audio_launch_args_cpu.py); the line itself, struct Line, is in stub_log.hpp.
 #include <hip/hip_runtime.h>
 
@@ -20,6 +25,7 @@
 #include <cstring>
 #include <map>
 #include <string>
+#include <vector>
 
 #include "../../amuse_amd/csrc/amuse_audio.hpp"
 #include "../../amuse_amd/csrc/amuse_kernels.hpp"
@@ -30,8 +36,9 @@ long amuse_stub_live_allocations() { return g_live; }
 
 static int g_level = 0;        // 0 off | 1 image log | 2 launch log
 static bool g_log = false;     // the image log's lines
+static bool g_raw = false;     // the raw launch log's lines (level 3: the launch log + raw launches, creations, function attributes)
 static std::map<const void*, uint64_t> g_image;   // "device" pointer -> digest of the last upload to it (while a log is on)
-void amuse_stub_log(int on) { g_level = on; g_log = on == 1; }
+void amuse_stub_log(int on) { g_level = on == 3 ? 2 : on; g_log = on == 1; g_raw = on == 3; }
 static uint64_t fnv1a(const void* p, size_t n) {
     const unsigned char* b = static_cast<const unsigned char*>(p);
     uint64_t h = 0xcbf29ce484222325ull;
@@ -93,8 +100,39 @@ static const char* kind_text(hipMemcpyKind k) {
 }
 static void log_copy(const char* name, void* d, const void* s, size_t n, hipMemcpyKind k) { Line(name).kv("kind", kind_text(k)).u("bytes", n).p("dst", d).p("src", s); }
 
+// ---- failure injection: the n-th runtime call / launch after amuse_stub_fail_at(n) fails (n = 0: none); amuse_stub_steps() = how many there have been since
+static long g_fail_at = 0, g_steps = 0;
+static hipError_t g_last_error = hipSuccess;
+void amuse_stub_fail_at(long n) { g_fail_at = n; g_steps = 0; }
+long amuse_stub_steps() { return g_steps; }
+static std::vector<std::string>* g_capture_lines = nullptr;
+void amuse_stub_capture(std::vector<std::string>* lines) { g_capture_lines = lines; }
+void amuse_stub_emit(const std::string& line) {
+    puts(line.c_str());
+    if (g_capture_lines) g_capture_lines->push_back(line);
+}
+static bool step_fails() {
+    if (++g_steps != g_fail_at) return false;
+    amuse_stub_emit("-- injected failure");
+    return true;
+}
+// ---- kernels by host handle (filled during static initialisation, hence created on first use) and the driver's parameter letters
+static std::map<const void*, std::string>& kernels() {
+    static std::map<const void*, std::string>* m = new std::map<const void*, std::string>;
+    return *m;
+}
+static const char* (*g_params)(const char*) = nullptr;
+void amuse_stub_kernel_params(const char* (*lookup)(const char* mangled)) { g_params = lookup; }
+static std::string kernel_text(const void* f) {
+    const auto it = kernels().find(f);
+    return it == kernels().end() ? "?" : it->second;
+}
+struct CallConfig { dim3 grid, block; size_t lds; hipStream_t stream; };
+static thread_local CallConfig g_config;
+
 extern "C" {
 hipError_t hipMalloc(void** p, size_t n) {
+    if (step_fails()) { *p = nullptr; if (g_level == 2) Line("hipMalloc").u("bytes", n).kv("ptr", "failed"); return hipErrorOutOfMemory; }
     *p = malloc(n ? n : 1);
     ++g_live;
     if (*p) g_blocks[static_cast<const char*>(*p)] = {n, ++g_nblocks};
@@ -124,6 +162,7 @@ hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind k, hip
 }
 hipError_t hipMemset(void* d, int v, size_t n) {
     if (g_level == 2) Line("hipMemset").i("value", v).u("bytes", n).p("dst", d);
+    if (step_fails()) return hipErrorUnknown;
     memset(d, v, n);
     return hipSuccess;
 }
@@ -133,19 +172,78 @@ hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t st) {
     return hipSuccess;
 }
 hipError_t hipSetDevice(int) { return hipSuccess; }
-hipError_t hipGetLastError(void) { return hipSuccess; }
+hipError_t hipGetDevice(int* d) { *d = 0; return hipSuccess; }
+hipError_t hipGetLastError(void) { const hipError_t e = g_last_error; g_last_error = hipSuccess; return e; }
+hipError_t hipDeviceSynchronize(void) {
+    if (g_raw) Line("hipDeviceSynchronize");
+    return step_fails() ? hipErrorUnknown : hipSuccess;
+}
+hipError_t hipFuncSetAttribute(const void* f, hipFuncAttribute attr, int value) {
+    if (g_raw) Line("hipFuncSetAttribute").kv("kernel", kernel_text(f)).i("attr", (int)attr).i("value", value);
+    return step_fails() ? hipErrorUnknown : hipSuccess;
+}
 const char* hipGetErrorString(hipError_t) { return "stub"; }
-hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { *s = reinterpret_cast<hipStream_t>(malloc(8)); ++g_live; g_streams[*s] = ++g_nstreams; return hipSuccess; }
+hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned flags) {
+    if (step_fails()) { if (g_raw) Line("hipStreamCreateWithFlags").u("flags", flags).kv("stream", "failed"); return hipErrorUnknown; }
+    *s = reinterpret_cast<hipStream_t>(malloc(8)); ++g_live; g_streams[*s] = ++g_nstreams;
+    if (g_raw) Line("hipStreamCreateWithFlags").u("flags", flags).st(*s);
+    return hipSuccess;
+}
 hipError_t hipStreamDestroy(hipStream_t s) { g_streams.erase(s); free(s); --g_live; return hipSuccess; }
 hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
 hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned) {
     if (g_level == 2) Line("hipStreamWaitEvent").kv("event", handle_text(g_events, e)).st(s);
+    return step_fails() ? hipErrorUnknown : hipSuccess;
+}
+hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned flags) {
+    if (step_fails()) { if (g_raw) Line("hipEventCreateWithFlags").u("flags", flags).kv("event", "failed"); return hipErrorUnknown; }
+    *e = reinterpret_cast<hipEvent_t>(malloc(8)); ++g_live; g_events[*e] = ++g_nevents;
+    if (g_raw) Line("hipEventCreateWithFlags").u("flags", flags).kv("event", handle_text(g_events, *e));
     return hipSuccess;
 }
-hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { *e = reinterpret_cast<hipEvent_t>(malloc(8)); ++g_live; g_events[*e] = ++g_nevents; return hipSuccess; }
 hipError_t hipEventDestroy(hipEvent_t e) { g_events.erase(e); free(e); --g_live; return hipSuccess; }
 hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) {
     if (g_level == 2) Line("hipEventRecord").kv("event", handle_text(g_events, e)).st(s);
+    return step_fails() ? hipErrorUnknown : hipSuccess;
+}
+// ---- the raw launch level: what the compiler's host code of a kernel and of a <<< >>> calls
+void** __hipRegisterFatBinary(const void*) { static void* module = nullptr; return &module; }
+void __hipUnregisterFatBinary(void**) {}
+void __hipRegisterFunction(void**, const void* host, char*, const char* name, unsigned, uint3*, uint3*, dim3*, dim3*, int*) { kernels()[host] = name; }
+hipError_t __hipPushCallConfiguration(dim3 grid, dim3 block, size_t lds, hipStream_t st) { g_config = {grid, block, lds, st}; return hipSuccess; }
+hipError_t __hipPopCallConfiguration(dim3* grid, dim3* block, size_t* lds, hipStream_t* st) {
+    *grid = g_config.grid; *block = g_config.block; *lds = g_config.lds; *st = g_config.stream;
+    return hipSuccess;
+}
+// arguments by the driver's letters, one per parameter: p pointer, i int, l long, u uint32, U uint64, z size_t, f float, d double, S a struct by value (skipped)
+hipError_t hipLaunchKernel(const void* f, dim3 grid, dim3 block, void** args, size_t lds, hipStream_t st) {
+    const std::string name = kernel_text(f);
+    if (g_raw) {
+        Line l("launch");
+        char buf[96];
+        snprintf(buf, sizeof(buf), "%u,%u,%u", grid.x, grid.y, grid.z);
+        l.kv("kernel", name).kv("grid", buf);
+        snprintf(buf, sizeof(buf), "%u,%u,%u", block.x, block.y, block.z);
+        l.kv("block", buf).u("lds", lds).st(st);
+        const char* sig = g_params ? g_params(name.c_str()) : nullptr;
+        if (!sig) l.kv("args", "unknown");
+        for (int i = 0; sig && sig[i]; ++i) {
+            const std::string k = "a" + std::to_string(i);
+            const void* a = args[i];
+            switch (sig[i]) {
+                case 'p': l.p(k.c_str(), *static_cast<void* const*>(a)); break;
+                case 'i': l.i(k.c_str(), *static_cast<const int*>(a)); break;
+                case 'l': l.i(k.c_str(), *static_cast<const long*>(a)); break;
+                case 'u': l.u(k.c_str(), *static_cast<const uint32_t*>(a)); break;
+                case 'U': l.u(k.c_str(), *static_cast<const uint64_t*>(a)); break;
+                case 'z': l.u(k.c_str(), *static_cast<const size_t*>(a)); break;
+                case 'f': l.f(k.c_str(), *static_cast<const float*>(a)); break;
+                case 'd': { char b[48]; snprintf(b, sizeof(b), "%a", *static_cast<const double*>(a)); l.kv(k.c_str(), b); break; }
+                default: l.kv(k.c_str(), "skipped(struct)"); break;
+            }
+        }
+    }
+    if (step_fails()) { g_last_error = hipErrorLaunchFailure; return hipErrorLaunchFailure; }
     return hipSuccess;
 }
 }

@@ -10,12 +10,13 @@ int amuse_stub_log_level();                                  // 0 off | 1 image 
 std::string amuse_stub_ptr_text(const void* p);              // `0`, `dev#<n>+<offset>/<block size>`, `<name>+<offset>` or `host`
 std::string amuse_stub_stream_text(hipStream_t s);           // `0` or `#<order of creation>`
 unsigned long long amuse_stub_image_of(const void* p);       // digest of the last upload to exactly this pointer, 0 if none
+void amuse_stub_emit(const std::string& line);               // prints the line (and hands it to amuse_stub_capture's vector, if one is set)
 
 // one line of the launch log: `name key=value ...`, printed when it goes out of scope
 struct Line {
     std::string s;
     explicit Line(const char* name) : s(name) {}
-    ~Line() { puts(s.c_str()); }
+    ~Line() { amuse_stub_emit(s); }
     Line& kv(const char* k, const std::string& v) { s += ' '; s += k; s += '='; s += v; return *this; }
     Line& p(const char* k, const void* v) { return kv(k, amuse_stub_ptr_text(v)); }
     Line& i(const char* k, long long v) { return kv(k, std::to_string(v)); }

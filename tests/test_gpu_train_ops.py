@@ -525,3 +525,61 @@ def test_two_layer_chains_on_two_streams_do_not_share_scratch():
                     assert torch.equal(ta, tb)
     finally:
         train_ops._LANES.clear()
+
+
+def test_refused_layer_backward_touches_nothing_and_the_next_call_is_right(eager_switch, monkeypatch):
+    """A decoder layer at B = 2, S = 8, self-attention inside the call.  amuse_train_layer_bwd without its dqkv buffer is refused BEFORE its first launch: dx, dWv
+    and dmem, filled with a sentinel, are bit-for-bit what they were after a stream synchronise.  The next, valid call on the same buffers - and the call the
+    autograd function itself makes - give the eager layer's gradients at this file's bars (test_fused_layer_equals_the_eager_layer_in_eval_mode)."""
+    import ctypes as C
+
+    from amuse_amd import _lib, train_ops
+    B, S = 2, 8
+    m = _layers("dec", 1).eval()
+    g = torch.Generator(device=DEV).manual_seed(2)
+    x, mem, dout = (torch.randn(B, n, 128, device=DEV, generator=g) for n in (S, 1, S))
+
+    def run(on):
+        eager_switch(on)
+        xr, mr = x.clone().requires_grad_(True), mem.clone().requires_grad_(True)
+        m.zero_grad(set_to_none=True)
+        m(xr, mr).backward(dout)
+        return xr.grad, mr.grad, {n: p.grad.clone() for n, p in m.named_parameters() if p.grad is not None}
+
+    dx0, dm0, g0 = run(False)
+    st = train_ops._st(x.device)
+    real = st["lib"]
+    sizes = {"dx": B * S * 128, "dWv": 128 * 128, "dmem": B * 128}
+    sentinel = torch.full((max(sizes.values()),), 0x5A5A5A5A, device=DEV, dtype=torch.int32)
+    mine = {n: sentinel[:k].clone() for n, k in sizes.items()}
+    assert all(t.numel() == sizes[n] for n, t in mine.items())
+    seen = {}
+
+    class Lib:
+        def __getattr__(self, name):
+            return getattr(real, name)
+
+        def amuse_train_layer_bwd(self, ref, stream):
+            L = _lib.TrainLayer.from_buffer_copy(ref._obj)
+            for n, t in mine.items():
+                setattr(L, n, t.data_ptr())
+            dqkv, L.dqkv = L.dqkv, None
+            seen["rc"] = real.amuse_train_layer_bwd(C.byref(L), stream)
+            seen["error"] = real.amuse_last_error().decode()
+            torch.cuda.current_stream(DEV).synchronize()
+            seen["untouched"] = all(torch.equal(t, sentinel[:t.numel()]) for t in mine.values())
+            L.dqkv = dqkv
+            _lib.check(real.amuse_train_layer_bwd(C.byref(L), stream))
+            return real.amuse_train_layer_bwd(ref, stream)
+
+    monkeypatch.setitem(st, "lib", Lib())
+    dx1, dm1, g1 = run(True)
+    assert seen["rc"] != 0 and "self-attention buffers missing" in seen["error"], seen
+    assert seen["untouched"]
+    dWv0 = g0["multihead_attn.in_proj_weight"][256:]
+    for got, want in ((mine["dx"].view(torch.float32).view(B, S, 128), dx0), (mine["dmem"].view(torch.float32).view(B, 1, 128), dm0),
+                      (mine["dWv"].view(torch.float32).view(128, 128), dWv0), (dx1, dx0), (dm1, dm0)):
+        assert _rel(got, want) < 2e-4
+    assert set(g0) == set(g1)
+    for n in g0:
+        assert _rel(g1[n], g0[n]) < 2e-4, n

@@ -38,6 +38,8 @@ EXPORTS = [
     "amuse_resample_plan", "amuse_resampler_create", "amuse_resampler_destroy", "amuse_resample", "amuse_debug_resample_bank",
     "amuse_render_plan", "amuse_renderer_create", "amuse_renderer_destroy", "amuse_render", "amuse_debug_render_raster",
     "amuse_motion_metrics_row", "amuse_motion_metrics",
+    "amuse_beat_default_params", "amuse_beat_create", "amuse_beat_destroy", "amuse_beat_plan", "amuse_beat_reserve", "amuse_beat_onsets", "amuse_beat_pick",
+    "amuse_beat_align_row", "amuse_beat_align",
 ]
 PCM_U8, PCM_S16, PCM_S32, PCM_F32 = 0, 1, 2, 3   # include/amuse_hip.h AMUSE_PCM_*
 BODY_ROT_AA, BODY_ROT_6D = 0, 1   # include/amuse_hip.h AMUSE_BODY_ROT_*
@@ -74,6 +76,12 @@ class CameraC(C.Structure):
 class ShadingC(C.Structure):
     """include/amuse_hip.h `amuse_shading`."""
     _fields_ = [("light", C.c_float * 3), ("ambient", C.c_float), ("body_rgb", C.c_ubyte * 3), ("bg_rgb", C.c_ubyte * 3)]
+
+
+class BeatParamsC(C.Structure):
+    """include/amuse_hip.h `amuse_beat_params`."""
+    _fields_ = [("sigma_s", C.c_double), ("onset_delta", C.c_double), ("onset_window", C.c_int), ("onset_avg_window", C.c_int), ("motion_order", C.c_int),
+                ("fps", C.c_double)]
 
 
 class Schedule(C.Structure):
@@ -246,6 +254,21 @@ def load() -> C.CDLL:
     lib.amuse_motion_metrics_row.argtypes = []
     lib.amuse_motion_metrics.argtypes = [fp, fp, vp, C.c_int, C.c_int, vp, vp]
     lib.amuse_motion_metrics_row.restype = lib.amuse_motion_metrics.restype = C.c_int
+    # beat alignment (csrc/amuse_beat.hip): the plan and the defaults need no GPU; the context owns the fbank tables; pick and align are context-free
+    bp = C.POINTER(BeatParamsC)
+    lib.amuse_beat_default_params.argtypes = [bp]
+    lib.amuse_beat_create.restype = vp
+    lib.amuse_beat_create.argtypes = [C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    lib.amuse_beat_destroy.restype = None
+    lib.amuse_beat_destroy.argtypes = [vp]
+    lib.amuse_beat_plan.argtypes = [C.c_longlong, ip]
+    lib.amuse_beat_reserve.argtypes = [vp, C.c_int, C.c_int]
+    lib.amuse_beat_onsets.argtypes = [vp, fp, vp, C.c_int, C.c_int, bp, fp, vp, vp]
+    lib.amuse_beat_pick.argtypes = [fp, vp, C.c_int, C.c_int, bp, vp, vp]
+    lib.amuse_beat_align_row.argtypes = []
+    lib.amuse_beat_align.argtypes = [vp, vp, C.c_int, fp, vp, C.c_int, C.c_int, bp, vp, vp, vp]
+    for n in ("amuse_beat_default_params", "amuse_beat_plan", "amuse_beat_reserve", "amuse_beat_onsets", "amuse_beat_pick", "amuse_beat_align_row", "amuse_beat_align"):
+        getattr(lib, n).restype = C.c_int
     if lib.amuse_abi_version() != ABI_VERSION:
         raise AmuseHipError(f"ABI mismatch: library {lib.amuse_abi_version()} vs binding {ABI_VERSION}")
     _lib = lib

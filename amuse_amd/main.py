@@ -253,6 +253,12 @@ def main(argv=None):
                          "<model_path>/viz/motion_metrics_<stamp>_E<epoch>.json (amuse_amd/motion_metrics.py) - an extension: the reference's val_metrics.py cannot "
                          "run and its trainer passes metricsmodel=None.  Needs the SMPL-X model files (--smplx-models DIR); works under metrics_only: True")
     ap.add_argument("--metrics-diversity-times", type=int, default=300, help="--motion-metrics: clips per index set of the Diversity draw (it needs more clips than this)")
+    ap.add_argument("--beat-align", action="store_true",
+                    help="infer_gesture: after the run, every WAV is scored against the motion its NPZ holds - speech onsets of the waveform the front-end read against "
+                         "the motion beats (local minima of joint speed) of the posed SMPL-X joints, all in HIP kernels - and "
+                         "<model_path>/viz/beat_align_<stamp>_E<epoch>.json is written (amuse_amd/beat_align.py).  An extension and this project's own statement of the "
+                         "metric: not compared with librosa or with BEAT's code.  Needs the SMPL-X model files (--smplx-models DIR); the NPZ files keep their bytes; "
+                         "works with --long-form, --resample, --gpus N")
     args = ap.parse_args(argv)
     fn = args.fn[0]
     if fn not in ("infer_gesture", "edit_gesture", "train_gesture"):
@@ -277,6 +283,16 @@ def main(argv=None):
                              "directory)")
         if args.metrics_diversity_times < 1:
             raise SystemExit(f"--metrics-diversity-times {args.metrics_diversity_times}: at least 1")
+    if args.beat_align:
+        if fn != "infer_gesture":
+            raise SystemExit("--beat-align belongs to --fn infer_gesture: it scores every WAV against the motion generated from it (which WAV an edited motion "
+                             "should align with is a separate question)")
+        if not args.smplx_models:
+            raise SystemExit("--beat-align needs --smplx-models DIR: the motion beats are taken on the joints the SMPL-X body models pose")
+        from . import body
+        if not body.models_present(args.smplx_models):      # checked before anything is loaded or sampled
+            raise SystemExit(f"--beat-align: {', '.join(body.SMPLX_FILES.values())} were not all found in {args.smplx_models} (--smplx-models DIR names the "
+                             "directory)")
     if args.long_form and fn != "infer_gesture":
         raise SystemExit("--long-form belongs to --fn infer_gesture: it joins the windows of one WAV into one motion; the edit tasks work on 10 s clips")
     if args.long_form:
@@ -312,7 +328,7 @@ def main(argv=None):
     if args.all_pairs:
         tp["test"].setdefault("emotion_control_list", {})["all_pairs"] = True
     pg = False
-    if world > 1 and (args.motion_metrics or (fn == "edit_gesture" and tp["test"].get("emotion_control_list", {}).get("all_pairs"))):
+    if world > 1 and (args.motion_metrics or args.beat_align or (fn == "edit_gesture" and tp["test"].get("emotion_control_list", {}).get("all_pairs"))):
         # the ONE exchange of the inference path: S sources x T targets - every rank's jobs read most WAVs, so each rank embeds a share and
         # the embeddings (3 x 256 floats per WAV) are all-gathered.  RCCL between the GPUs; gloo when the ranks share a device (tests).
         import torch.distributed as dist
@@ -367,6 +383,10 @@ def main(argv=None):
         from . import body
         tp["test"]["motion_metrics"], tp["test"]["metrics_diversity_times"] = True, int(args.metrics_diversity_times)
         metric_models = body.load_models(args.smplx_models)
+    if args.beat_align:      # (as above: the key is this path's own)
+        from . import body
+        tp["test"]["beat_align"] = True
+        metric_models = metric_models or body.load_models(args.smplx_models)
     model.precision = args.precision
     print(f"[amuse_amd] sampler / decoder precision: {args.precision}; audio front-end precision: {args.audio_precision}"
           + (" (split-fp16 AST encoders: with --precision fp32 / fp32x the run is in parity from the waveform)" if args.audio_precision == "fp32x"

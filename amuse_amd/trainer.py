@@ -381,6 +381,9 @@ class trainer:
         # TRAIN_PARAM.test.motion_metrics (amuse_amd.main --motion-metrics; an extension, amuse_amd/motion_metrics.py): the SMPL-X models the joint half poses
         self.body_models = body_models
         self._mm_body, self._mm_tasks, self.motion_metrics_path = None, {}, None
+        # TRAIN_PARAM.test.beat_align (amuse_amd.main --beat-align; an extension, amuse_amd/beat_align.py): (NPZ, WAV) of every file the audio list wrote
+        self.beat_pairs: List[tuple] = []
+        self.beat_align_path = None
 
     # ------------------------------------------------------------------ visualizer stand-in
     def _animate(self, sample_dict, video_dump, n_clips: int = 1):
@@ -556,6 +559,41 @@ class trainer:
         print(f"[amuse_amd] motion metrics: {self.motion_metrics_path}")
         return self.motion_metrics_path
 
+    # ------------------------------------------------------------------ beat alignment (opt-in)
+    def _beat_align_on(self) -> bool:
+        return bool(self.config["TRAIN_PARAM"]["test"].get("beat_align", False)) and self.body_models is not None
+
+    def _beat_align_write(self, ldm_epoch) -> Optional[Path]:
+        """TRAIN_PARAM.test.beat_align: every WAV of the audio list against the motion its NPZ holds - stitched or not, as the file holds it (lower body frozen,
+        zero translation), posed by the NPZ's own gender and betas; the waveform is the one the front-end read (_load_wave: resampled under
+        TRAIN_PARAM.test.resample, the mean removed).  Writes <model_path>/viz/beat_align_<stamp>_E<epoch>.json; reads the NPZ files, changes none.  More than
+        one rank: as the motion metrics - the additive states are all-gathered and rank 0 writes; ranks without a process group each write their own share."""
+        from . import beat_align as ba
+
+        def front_end_wave(path):
+            w = self._load_wave(path)
+            return (w - w.mean())[0]
+        res = ba.score_pairs(self.beat_pairs, self.body_models, self.device, load_wave=front_end_wave)
+        per_file, state, suffix = res["per_file"], res["state"], ""
+        if self.world > 1:
+            if _dist_ready():
+                import torch.distributed as dist
+                parts = [None] * self.world
+                dist.all_gather_object(parts, (per_file, state))
+                if self.rank != 0:
+                    return None
+                per_file = {k: v for p, _ in parts for k, v in p.items()}
+                state = ba.BeatAlign()
+                for _, st in parts:
+                    state.merge(st)
+                state = state.state()
+            else:
+                suffix = f"_rank{self.rank}"
+        path = self.model_path / "viz" / f"beat_align_{self.stamp}_E{ldm_epoch}{suffix}.json"
+        self.beat_align_path = ba.write_report(path, per_file, state, res["params"], str(getattr(self.model, "precision", "")))
+        print(f"[amuse_amd] beat alignment: {self.beat_align_path}")
+        return self.beat_align_path
+
     # ------------------------------------------------------------------ infer_gesture
     def _infer_prior_latdiff_from_audio_v1(self, baseline, ldm_epoch, audio_list, short_audio_list, modelversion, ammetric):
         start_time = time.time()
@@ -587,12 +625,14 @@ class trainer:
             rst_all = run_jobs(self.model, jobs, batched=self.batched, rank=self.rank, world=self.world)
             video_dump_r = target_path / f"Custom_audios_{self.stamp}_E{ldm_epoch}" / f"rep{rep_i}"
             assert self.viz_type in ["CaMN"], "[LDM EVAL] Invalid viz type: [%s]" % self.viz_type
-            for sample_dict in rst_all:
+            for k, sample_dict in enumerate(rst_all):
                 rst = [sample_dict]
+                n_before = len(self.written)
                 for i, sd in enumerate(rst):
                     if sd is not None:
                         print(f"VISUALIZATION: LIST AUDIOS {i} =====>")
                     self._animate(sd, video_dump_r / f"rst_{i}")
+                self.beat_pairs += [(p, audios[k]) for p in self.written[n_before:]]      # job k is audio k: what --beat-align scores afterwards
             # opt-in (amuse_amd.main --audio-metrics): the reference's collect_audio_metrics (infer_ldm.py:195-208) for each of this rank's audios,
             # beside its motion: <rep>/rst_0/<audio stem>/audio_metrics/fbank.pkl
             if self.config["TRAIN_PARAM"]["test"].get("audio_metrics", False):
@@ -601,6 +641,8 @@ class trainer:
                         wave = self._load_wave(a)
                         self.model.collect_audio_metrics(wave - wave.mean(), framerate=16000, baseline=baseline, tgtpath=video_dump_r / "rst_0" / a.stem)
         print(f"[LDM EVAL] Audio list inference done, total time elapsed: {time.time() - start_time:.4f} s")
+        if self._beat_align_on():
+            self._beat_align_write(ldm_epoch)
 
     # ------------------------------------------------------------------ edit tasks
     def eval_prior_latdiff_forward_backward_v1(self, baseline, ldm_epoch, audio_list, short_audio_list=False,

@@ -788,6 +788,70 @@ int amuse_debug_render_raster(amuse_renderer* r, const int* screen_dev, int M, u
 int amuse_motion_metrics_row(void);
 int amuse_motion_metrics(const float* joints_gen, const float* joints_ref, const int* lengths_dev, int N, int F, double* rows_out, void* stream);
 
+/* ------------------------------------------------------------------ beat alignment (csrc/amuse_beat_host.hpp, amuse_beat.hip, k_beat.hip; amuse_amd/beat_align.py)
+ * AN EXTENSION, off by default: the reference has no such measure.  Speech onsets of the 16 kHz waveform against the motion beats of every SMPL-X joint, scored by
+ * how close the two sets lie in time.  This is THIS PROJECT'S OWN statement of the metric, in the manner of BEAT's `alignment` and of librosa's spectral-flux
+ * onset detector, both written down from memory: neither is on the build machine, nothing here is pinned against either, and no number this code gives has been
+ * compared with librosa or with BEAT's own code.  It is checked against its own float64 restatement (tests/beat_ref.py) and, for the motion beats, against
+ * scipy.signal.argrelextrema.  Deviation stated: a frame's time is its window CENTRE (audio) and the middle of the two motion frames a speed is taken between.
+ *
+ * Definitions (csrc/amuse_beat_host.hpp restates the row offsets; the kernels and tests/beat_ref.py follow these):
+ *   log-mel   S[t][m]: the kaldi fbank log energy of amuse_audio_fbank BEFORE its normalisation, same tables (mel [128][257], window [400]): frame t covers
+ *             the samples [160 t, 160 t + 400): DC removal, pre-emphasis 0.97, window, 512-point FFT, floor 1.1920929e-07, natural log.
+ *             T = 0 if n < 400, else 1 + (n - 400) / 160   (amuse_beat_plan)
+ *   envelope  e[0] = 0;  e[t] = (1 / 128) sum_m max(0, S[t][m] - S[t-1][m]), fp32
+ *   onsets    double after the fp32 load, no division by the maximum.  M = max_t e[t] over the clip's valid frames; M <= 0: no onset.  Frame t is an onset iff
+ *               1. e[t] >  e[t-i] for i = 1..onset_window with t - i >= 0        (strict on the left,
+ *               2. e[t] >= e[t+i] for i = 1..onset_window with t + i < T          not on the right: a plateau gives its FIRST frame)
+ *               3. e[t] >= mean(e[max(0, t-a) .. min(T-1, t+a)]) + onset_delta M, a = onset_avg_window; the mean is the ascending sum over the count
+ *             Two onsets are therefore more than onset_window frames apart; no greedy pass.  Onset time tau_a = (160 t + 200) / 16000 s.
+ *   beats     joint j, f = 0..L-2: s_j[f] = |X[f+1][j] - X[f][j]| fps, double after the fp32 load.  f is a beat iff s[f] < s[clip(f +- i, 0, L-2)] for all
+ *             i = 1..motion_order (strict; an index that clips onto f itself fails): scipy.signal.argrelextrema(s, np.less, order) in its default clip mode.
+ *             Beat time tau_m = (f + 0.5) / fps.
+ * One row of amuse_beat_align_row() = 166 doubles per clip:
+ *   offset  length  block
+ *        0       1  n_onsets   onsets with tau_a <= (L - 1) / fps; later ones are dropped everywhere
+ *        1      55  n_beats    motion beats of joint j
+ *       56      55  a2m        sum_a exp(-min_m (tau_a - tau_m)^2 / (2 sigma_s^2)); 0 when joint j has no beat
+ *      111      55  m2a        sum_m exp(-min_a (tau_m - tau_a)^2 / (2 sigma_s^2)); 0 when there is no onset
+ * Sums run in ascending time, in double (exp included), one lane per joint: no atomics, the order depends on the clip alone, so the same clip gives the same
+ * bits at any N and any position in the batch.  Only frames f < L are read; frames at or beyond L may hold NaN.
+ *
+ * Parameters: amuse_beat_default_params fills sigma_s 0.1 s, onset_delta 0.07, onset_window 3 and onset_avg_window 10 (frames of 10 ms), motion_order 3
+ * (motion frames), fps 30.  A NULL params pointer means the defaults.  Checked on the host, AMUSE_EINVAL otherwise: sigma_s > 0 and finite; onset_delta >= 0
+ * (and finite); both onset windows >= 1; 1 <= motion_order <= 32 (the speeds a lane keeps); fps > 0 and finite.
+ *
+ * Every call below is stream-ordered, makes no host synchronisation and checks its arguments before any HIP call. */
+typedef struct amuse_beat amuse_beat;
+typedef struct { double sigma_s, onset_delta; int onset_window, onset_avg_window, motion_order; double fps; } amuse_beat_params;
+int amuse_beat_default_params(amuse_beat_params* params);
+/* The context owns the two tables on the device (host arrays mel_banks [128][257], window [400], as amuse_audio_create takes them).  NULL on failure. */
+amuse_beat* amuse_beat_create(int device, const float* mel_banks, const float* window);
+void amuse_beat_destroy(amuse_beat* ctx);
+/* *frames = T as above; needs no GPU.  AMUSE_EINVAL for n_samples < 0 or a T beyond an int. */
+int amuse_beat_plan(long long n_samples, int* frames);
+/* Only for amuse_beat_onsets with envelope_out == NULL: makes the context's own envelope buffer hold B clips of n_samples.  Grows only; what an earlier call
+ * may still read is freed at destroy, never before.  This is the one call here that allocates. */
+int amuse_beat_reserve(amuse_beat* ctx, int B, int n_samples);
+/* waves_dev [B][n_samples]; n_valid_dev [B] or NULL (every clip has n_samples; a value is clamped to 0..n_samples) for ragged batches: clip b has
+ * T_b = plan(n_valid[b]) frames.  envelope_out [B][T], onset_mask_out [B][T] (1 = onset), T = plan(n_samples); either may be NULL, not both; with envelope_out
+ * NULL the envelope goes to the reserved buffer (AMUSE_EINVAL if amuse_beat_reserve has not covered B x T).  Frames beyond T_b get envelope 0 and mask 0.
+ * Two launches: the envelope (one workgroup per run of 16 frames, no [T][128] intermediate) and exactly the stage of amuse_beat_pick.  T == 0 launches nothing.
+ * AMUSE_EINVAL: NULL ctx / waves; B < 1; n_samples < 1; B x max(T, 1) beyond an int; bad params. */
+int amuse_beat_onsets(amuse_beat* ctx, const float* waves_dev, const int* n_valid_dev, int n_samples, int B, const amuse_beat_params* params,
+                      float* envelope_out, unsigned char* onset_mask_out, void* stream);
+/* Context-free: the pick stage alone on a caller's envelope dev [B][T]; frames_dev [B] (clamped to 0..T).  AMUSE_EINVAL: a NULL pointer; B < 1; T < 1;
+ * B x T beyond an int; bad params. */
+int amuse_beat_pick(const float* envelope_dev, const int* frames_dev, int B, int T, const amuse_beat_params* params, unsigned char* onset_mask_out, void* stream);
+int amuse_beat_align_row(void);
+/* Context-free.  onset_mask_dev [N][T] (non-zero = onset), audio_frames_dev [N] (clamped to 0..T); joints dev [N][F][55][3] as amuse_body_forward writes them;
+ * lengths_dev [N]; rows_out dev [N][166]; beat_mask_out dev [N][F][55] or NULL (1 = beat; 0 at every frame that cannot be one).  A clip whose length lies
+ * outside 2..F gets a row of NaN (and a beat mask of 0), reads nothing and harms no other clip.  One workgroup per clip.
+ * AMUSE_EINVAL: a NULL pointer other than beat_mask_out (onset_mask_dev may be NULL when T == 0); N < 1; F < 2; T < 0 or T > 131072 (the onset bits a
+ * workgroup keeps in LDS: 21 minutes of audio); N x F, N x T or 166 N beyond an int; bad params. */
+int amuse_beat_align(const unsigned char* onset_mask_dev, const int* audio_frames_dev, int T, const float* joints, const int* lengths_dev, int N, int F,
+                     const amuse_beat_params* params, double* rows_out, unsigned char* beat_mask_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -40,6 +40,8 @@ EXPORTS = [
     "amuse_motion_metrics_row", "amuse_motion_metrics",
     "amuse_beat_default_params", "amuse_beat_create", "amuse_beat_destroy", "amuse_beat_plan", "amuse_beat_reserve", "amuse_beat_onsets", "amuse_beat_pick",
     "amuse_beat_align_row", "amuse_beat_align",
+    "amuse_mjpeg_tables", "amuse_mjpeg_plan", "amuse_mjpeg_create", "amuse_mjpeg_reserve", "amuse_mjpeg_destroy", "amuse_mjpeg_encode",
+    "amuse_debug_mjpeg_coefficients", "amuse_debug_mjpeg_header",
 ]
 PCM_U8, PCM_S16, PCM_S32, PCM_F32 = 0, 1, 2, 3   # include/amuse_hip.h AMUSE_PCM_*
 BODY_ROT_AA, BODY_ROT_6D = 0, 1   # include/amuse_hip.h AMUSE_BODY_ROT_*
@@ -268,6 +270,20 @@ def load() -> C.CDLL:
     lib.amuse_beat_align_row.argtypes = []
     lib.amuse_beat_align.argtypes = [vp, vp, C.c_int, fp, vp, C.c_int, C.c_int, bp, vp, vp, vp]
     for n in ("amuse_beat_default_params", "amuse_beat_plan", "amuse_beat_reserve", "amuse_beat_onsets", "amuse_beat_pick", "amuse_beat_align_row", "amuse_beat_align"):
+        getattr(lib, n).restype = C.c_int
+    # preview video (csrc/amuse_mjpeg.hip): the tables, the plan and the header need no GPU; one encoder per (GPU, image size, quality)
+    ub, sz = C.POINTER(C.c_ubyte), C.POINTER(C.c_size_t)
+    lib.amuse_mjpeg_tables.argtypes = [C.c_int, ub, ub]
+    lib.amuse_mjpeg_plan.argtypes = [C.c_int, C.c_int, C.c_int, ip, ip, ip, sz, sz]
+    lib.amuse_mjpeg_create.restype = vp
+    lib.amuse_mjpeg_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
+    lib.amuse_mjpeg_reserve.argtypes = [vp, C.c_int]
+    lib.amuse_mjpeg_destroy.restype = None
+    lib.amuse_mjpeg_destroy.argtypes = [vp]
+    lib.amuse_mjpeg_encode.argtypes = [vp, vp, C.c_int, vp, C.c_size_t, vp, vp, vp, vp]
+    lib.amuse_debug_mjpeg_coefficients.argtypes = [vp, vp, C.c_int, vp, vp]
+    lib.amuse_debug_mjpeg_header.argtypes = [C.c_int, C.c_int, C.c_int, ub, C.c_size_t, ip]
+    for n in ("amuse_mjpeg_tables", "amuse_mjpeg_plan", "amuse_mjpeg_reserve", "amuse_mjpeg_encode", "amuse_debug_mjpeg_coefficients", "amuse_debug_mjpeg_header"):
         getattr(lib, n).restype = C.c_int
     if lib.amuse_abi_version() != ABI_VERSION:
         raise AmuseHipError(f"ABI mismatch: library {lib.amuse_abi_version()} vs binding {ABI_VERSION}")

@@ -31,6 +31,7 @@ floor(30 x seconds) frames - overlapping 10 s windows, sampled independently, cr
 `--fn infer_gesture | edit_gesture --preview --smplx-models DIR [--preview-size 512] [--preview-stride 10] [--preview-frames]` writes, beside every
 *_motion_smplx.npz, *_preview.png - a contact sheet of the posed SMPL-X mesh, rasterised in HIP (amuse_amd/render.py) - and with --preview-frames
 *_preview/frame_%04d.png.  A flat-shaded preview from a fixed front camera, not the reference's Blender render; the NPZ files keep their bytes.  Off by default.
+With --preview-video [--preview-quality 90] also *_preview.avi: every frame as Motion-JPEG, encoded in HIP (amuse_amd/video.py), with the speech as 16-bit PCM.
 """
 from __future__ import annotations
 
@@ -247,6 +248,12 @@ def main(argv=None):
     ap.add_argument("--preview-size", type=int, default=512, help="--preview: pixels per side of a frame")
     ap.add_argument("--preview-stride", type=int, default=10, help="--preview: every stride-th frame goes on the sheet")
     ap.add_argument("--preview-frames", action="store_true", help="--preview: also write *_preview/frame_%%04d.png for every frame")
+    ap.add_argument("--preview-video", action="store_true",
+                    help="--preview: also write *_preview.avi - every frame as Motion-JPEG, encoded in HIP kernels while still on the device, with the speech as "
+                         "16-bit PCM (amuse_amd/video.py): infer_gesture muxes the job's WAV (with --long-form the whole WAV against the whole motion), edit_gesture "
+                         "the content source WAV, a dataset-driven edit (--eval-data) clip c of its take's ld_waveform (16 kHz) when the dictionary holds one; a motion whose audio the run does not hold gets the video stream alone.  A preview encoder (fixed Huffman "
+                         "tables, no chroma subsampling), an AVI 1.0 file (below 2 GiB)")
+    ap.add_argument("--preview-quality", type=int, default=None, help="--preview-video: JPEG quality 1..100 (default 90)")
     ap.add_argument("--motion-metrics", action="store_true",
                     help="edit tasks on the dataset (--eval-data): after every task, APE / AVE / velocity / acceleration on posed SMPL-X joints (summed per clip in a HIP "
                          "kernel) and FID / Diversity on the motion prior's latents, between every generated motion and its source motion, written to "
@@ -268,10 +275,16 @@ def main(argv=None):
                          "SMPL-X body models")
     if args.resample and fn == "train_gesture":
         raise SystemExit("--resample belongs to --fn infer_gesture / edit_gesture: it converts the WAVs those read; the training reader is left as it is")
-    if (args.preview or args.preview_frames) and fn == "train_gesture":
+    if (args.preview or args.preview_frames or args.preview_video) and fn == "train_gesture":
         raise SystemExit("--preview belongs to --fn infer_gesture / edit_gesture: it draws the NPZ files those write")
     if args.preview_frames and not args.preview:
         raise SystemExit("--preview-frames belongs to --preview")
+    if args.preview_video and not args.preview:
+        raise SystemExit("--preview-video belongs to --preview")
+    if args.preview_quality is not None and not args.preview_video:
+        raise SystemExit("--preview-quality belongs to --preview-video")
+    if args.preview_quality is not None and not 1 <= args.preview_quality <= 100:
+        raise SystemExit(f"--preview-quality {args.preview_quality} outside 1..100")
     if args.motion_metrics:
         if fn == "train_gesture":
             raise SystemExit("--motion-metrics belongs to --fn infer_gesture / edit_gesture: it evaluates the pairs the edit tasks collect")
@@ -402,12 +415,15 @@ def main(argv=None):
     torch.cuda.synchronize()
     if preview_models is not None:      # this rank's own files: what the NPZ holds (lower body frozen, zero translation), as the reference renders the NPZ
         from . import render
-        pv = render.Previewer(preview_models, device, args.preview_size, args.preview_stride, args.preview_frames)
+        pv = render.Previewer(preview_models, device, args.preview_size, args.preview_stride, args.preview_frames, video=args.preview_video,
+                              quality=90 if args.preview_quality is None else args.preview_quality)
         try:
-            n_png = sum(len(pv.preview(p)) for p in written)
+            from .video import preview_wav
+            drawn = [f for p in written for f in pv.preview(p, wav=preview_wav(tr.preview_audio.get(str(p))) if args.preview_video else None)]
         finally:
             pv.close()
-        print(f"[amuse_amd] --preview: {n_png} PNG files beside {len(written)} NPZ files")
+        n_avi = sum(1 for f in drawn if Path(f).suffix == ".avi")
+        print(f"[amuse_amd] --preview: {len(drawn) - n_avi} PNG files" + (f" and {n_avi} AVI files" if n_avi else "") + f" beside {len(written)} NPZ files")
     print(f"AMUSE: ({fn}) completed in: {(time.time() - tic) / 3600} hrs; {len(written)} NPZ files" + (f" on rank {rank} of {world}" if world > 1 else ""))
     if world > 1 and os.environ.get("AMUSE_MANIFEST_DIR"):      # the launcher collects what the ranks wrote
         Path(os.environ["AMUSE_MANIFEST_DIR"], f"rank{rank}.json").write_text(json.dumps([str(p) for p in written]))

@@ -4,10 +4,11 @@ AN EXTENSION, off by default.  The reference hands its NPZ to Blender (1024 x 10
 This is a PREVIEW: the mesh flat-shaded from one fixed front camera, so that a result can be looked at without Blender and the SMPL-X add-on.  It matches no
 other renderer's image and is checked against its own restatement only (tests/render_ref.py).
 
-    python -m amuse_amd.render FILE_motion_smplx.npz --smplx-models DIR [--size 512] [--stride 10] [--frames]
+    python -m amuse_amd.render FILE_motion_smplx.npz --smplx-models DIR [--size 512] [--stride 10] [--frames] [--video [--audio FILE.wav] [--quality 90]]
 
 writes FILE_preview.png (a contact sheet of every stride-th frame) beside the NPZ, with --frames also FILE_preview/frame_%04d.png; `main.py --preview` does the
-same for every NPZ a run writes.  The model files must carry their triangles (key 'f', as the published SMPL-X files do).  There is no CPU fallback."""
+same for every NPZ a run writes.  With --video [--audio FILE.wav] [--quality 90] EVERY frame also goes, still on the device, through the HIP JPEG encoder of
+amuse_amd/video.py into FILE_preview.avi (Motion-JPEG, with the WAV's own samples as 16-bit PCM when one is given).  The model files must carry their triangles (key 'f', as the published SMPL-X files do).  There is no CPU fallback."""
 from __future__ import annotations
 
 import ctypes as C
@@ -189,10 +190,14 @@ def preview_paths(npz_path, out_dir=None):
 class Previewer:
     """The body engines and renderers of a run, built once per gender: preview(npz) poses the file's poses / trans / betas / gender and writes its pictures."""
 
-    def __init__(self, models: dict, device="cuda:0", size: int = 512, stride: int = 10, frames: bool = False, ss: int = 2, batch: int = 64):
+    def __init__(self, models: dict, device="cuda:0", size: int = 512, stride: int = 10, frames: bool = False, ss: int = 2, batch: int = 64, video: bool = False,
+                 quality: int = 90):
         if size < 1 or stride < 1:
             raise SystemExit(f"preview: --preview-size {size} and --preview-stride {stride} must be >= 1")
+        if video and not 1 <= quality <= 100:
+            raise SystemExit(f"preview: --quality {quality} outside 1..100")
         self.models, self.device, self.size, self.stride, self.frames, self.ss, self.batch = models, torch.device(device), int(size), int(stride), bool(frames), ss, batch
+        self.video, self.quality, self._enc = bool(video), int(quality), None
         self._eng = {}
 
     def _engine(self, gender):
@@ -207,9 +212,20 @@ class Previewer:
             e.close()
             r.close()
         self._eng = {}
+        if self._enc is not None:
+            self._enc.close()
+            self._enc = None
 
-    def preview(self, npz_path, out_dir=None):
-        """-> the paths written (the sheet first)"""
+    def _video_writer(self, path, wav):
+        """video=True: the AVI of one NPZ; wav = a WAV file, (int16 [samples, channels], rate), or None for a video stream alone"""
+        from . import video
+        if self._enc is None:
+            self._enc = video.JpegEncoder(self.device, self.size, self.size, self.quality)
+        audio = video.load_pcm16(wav) if isinstance(wav, (str, Path)) else wav
+        return video.AviWriter(path, self.size, self.size, 30, audio)
+
+    def preview(self, npz_path, out_dir=None, wav=None):
+        """-> the paths written (the sheet first; with video=True the AVI last)"""
         with np.load(str(npz_path), allow_pickle=False) as z:
             poses, trans = np.asarray(z["poses"], np.float32), np.asarray(z["trans"], np.float32)
             betas, gender = np.asarray(z["betas"], np.float32).reshape(-1), str(z["gender"])
@@ -225,15 +241,31 @@ class Previewer:
         rot = torch.from_numpy(np.ascontiguousarray(poses.reshape(1, F, 55, 3))).to(self.device)
         tr = torch.from_numpy(np.ascontiguousarray(trans.reshape(1, F, 3))).to(self.device)
         cam = Camera.front(eng.joints(rot, tr).cpu().numpy(), self.size, self.size)      # one camera for the clip: framed on every frame's joints
-        picked = list(range(F)) if self.frames else list(range(0, F, self.stride))
-        out = np.empty((len(picked), self.size, self.size, 3), np.uint8)
-        idx = torch.tensor(picked, device=self.device)
-        for i0 in range(0, len(picked), self.batch):
-            sel = idx[i0:i0 + self.batch]
-            v = eng.vertices(rot[:, sel].contiguous(), tr[:, sel].contiguous())[0]
-            out[i0:i0 + self.batch] = ren.render(v, cam).cpu().numpy()
         sheet_path, frames_dir = preview_paths(npz_path, out_dir)
         sheet_path.parent.mkdir(parents=True, exist_ok=True)
+        # the video takes EVERY frame; the host keeps what the pictures need: every frame with frames=True, every stride-th otherwise
+        picked = list(range(F)) if (self.frames or self.video) else list(range(0, F, self.stride))
+        kept = picked if self.frames else list(range(0, F, self.stride))
+        out = np.empty((len(kept), self.size, self.size, 3), np.uint8)
+        idx = torch.tensor(picked, device=self.device)
+        avi = self._video_writer(sheet_path.with_suffix(".avi"), wav) if self.video else None
+        try:
+            for i0 in range(0, len(picked), self.batch):
+                sel = idx[i0:i0 + self.batch]
+                v = eng.vertices(rot[:, sel].contiguous(), tr[:, sel].contiguous())[0]
+                rgb = ren.render(v, cam)
+                if avi is not None:
+                    for jpeg in self._enc.encode(rgb):      # the frames never leave the device as raw RGB for the video
+                        avi.write_frame(jpeg)
+                if len(kept) == len(picked):
+                    out[i0:i0 + self.batch] = rgb.cpu().numpy()
+                else:
+                    local = [i for i in range(int(sel.numel())) if picked[i0 + i] % self.stride == 0]
+                    if local:
+                        out[[picked[i0 + i] // self.stride for i in local]] = rgb[torch.tensor(local, device=self.device)].cpu().numpy()
+        finally:
+            if avi is not None:
+                avi.close()
         sheet = out[::self.stride] if self.frames else out
         write_png(sheet_path, contact_sheet(sheet, SHEET_COLS))
         written = [sheet_path]
@@ -242,16 +274,19 @@ class Previewer:
             for f in range(F):
                 write_png(frames_dir / f"frame_{f:04d}.png", out[f])
                 written.append(frames_dir / f"frame_{f:04d}.png")
+        if avi is not None:
+            written.append(avi.path)
         return written
 
 
-def preview_npz(npz_path, models, out_dir=None, size: int = 512, stride: int = 10, frames: bool = False, device="cuda:0"):
+def preview_npz(npz_path, models, out_dir=None, size: int = 512, stride: int = 10, frames: bool = False, device="cuda:0", video: bool = False, quality: int = 90,
+                wav=None):
     """One NPZ (this project's or the reference's own): models = {"male" | "female" | "neutral": BodyModel} or a directory holding the SMPL-X files."""
     if not isinstance(models, dict):
         models = load_preview_models(models)
-    p = Previewer(models, device, size, stride, frames)
+    p = Previewer(models, device, size, stride, frames, video=video, quality=quality)
     try:
-        return p.preview(npz_path, out_dir)
+        return p.preview(npz_path, out_dir, wav)
     finally:
         p.close()
 
@@ -266,19 +301,32 @@ def main(argv=None):
     ap.add_argument("--frames", action="store_true", help="also write <name>_preview/frame_%%04d.png for every frame")
     ap.add_argument("--out-dir", default=None, help="default: beside the NPZ")
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--video", action="store_true", help="also write <name>_preview.avi: every frame as Motion-JPEG, encoded in HIP kernels (amuse_amd/video.py)")
+    ap.add_argument("--audio", default=None, help="--video: the WAV whose own samples the AVI carries as 16-bit PCM (one NPZ only)")
+    ap.add_argument("--quality", type=int, default=None, help="--video: JPEG quality 1..100 (default 90)")
     args = ap.parse_args(argv)
+    if (args.audio is not None or args.quality is not None) and not args.video:
+        raise SystemExit("preview: --audio and --quality belong to --video")
+    quality = 90 if args.quality is None else args.quality
+    if not 1 <= quality <= 100:
+        raise SystemExit(f"preview: --quality {quality} outside 1..100")
+    if args.audio is not None and len(args.npz) != 1:
+        raise SystemExit(f"preview: --audio names the WAV of ONE motion; {len(args.npz)} NPZ files were given")
+    if args.audio is not None and not Path(args.audio).is_file():
+        raise SystemExit(f"preview: {args.audio} does not exist")
     models = load_preview_models(args.smplx_models)
     for n in args.npz:
         if not Path(n).is_file():
             raise SystemExit(f"preview: {n} does not exist")
-    p = Previewer(models, args.device, args.size, args.stride, args.frames)
+    p = Previewer(models, args.device, args.size, args.stride, args.frames, video=args.video, quality=quality)
     written = []
     try:
         for n in args.npz:
-            written += p.preview(n, args.out_dir)
+            written += p.preview(n, args.out_dir, args.audio)
     finally:
         p.close()
-    print(f"preview: wrote {len(written)} PNG files; first {written[0]}")
+    n_avi = sum(1 for w in written if Path(w).suffix == ".avi")
+    print(f"preview: wrote {len(written) - n_avi} PNG files" + (f" and {n_avi} AVI files" if n_avi else "") + f"; first {written[0]}")
     return written
 
 

@@ -126,6 +126,8 @@ def _emotion_of_take(take_emo: str) -> str:
 
 
 def _job(actor, take, z_con, z_emo, z_sty, bsz, info, swap_info=None, audio=None, src_motion=None, **extra) -> dict:
+    """`waveform` (in extra; amuse_amd.main --preview-video, an extension): the take's `ld_waveform`, (C, n) at 16 kHz, whole and by reference - clip c of the
+    job is its samples [160000 c, 160000 (c + 1)) (preview_audio_of_job).  Nothing else reads it."""
     bsz = int(bsz)
     j = {"actor": actor, "take": take, "bsz": bsz, "z_con": z_con[:bsz], "z_emo": None if z_emo is None else z_emo[:bsz],
          "z_sty": None if z_sty is None else z_sty[:bsz], "info": info, "swap_info": swap_info,
@@ -198,13 +200,13 @@ def emotion_control_jobs(data: Dict, take_element: str = "first") -> List[dict]:
                     emo = f"swap emo {_emotion_of_take(key.split('_')[-1])} in element {take_element}"
                 info = f"{attr[0]} {attr[1]} {attr[2]} {attr[4]} yrs {tt} {emo}"
                 jobs.append(_job(actor, take, z_con, z_emo, z_sty, bsz, info, "", e.get("ld_wav"), e.get("ld_motion"),
-                                 z_emo_key=key))
+                                 z_emo_key=key, waveform=e.get("ld_waveform")))
     return jobs
 
 
 def _transfer_jobs(eval_set, a1_attr, a2_attr, label, emotion, min_over_z: bool):
     jobs = []
-    for actor, take, z, audio, z_con, z_emo, z_sty, swap, src_motion in eval_set:
+    for actor, take, z, audio, z_con, z_emo, z_sty, swap, src_motion, waveform in eval_set:
         act_attr = a1_attr if actor in a1_attr else a2_attr
         tt = take.split("_")[-1]
         rst_info = f"{label} - {act_attr} yrs {tt} {emotion[1:-1]}"
@@ -216,7 +218,7 @@ def _transfer_jobs(eval_set, a1_attr, a2_attr, label, emotion, min_over_z: bool)
         else:
             swap_info = "Not swapped, original"
             bsz = z.shape[0]
-        jobs.append(_job(actor, take, z_con, z_emo, z_sty, bsz, rst_info, swap_info, audio, src_motion))
+        jobs.append(_job(actor, take, z_con, z_emo, z_sty, bsz, rst_info, swap_info, audio, src_motion, waveform=waveform))
     return jobs
 
 
@@ -227,7 +229,7 @@ def style_transfer_jobs(data: Dict, actors: str, emotion: str) -> List[dict]:
     at = lambda a: f"{a[0]} {a[1]} {a[2]} {a[4]}"
     a1_attr, a2_attr = at(data[a1][t1]["ld_attr"]), at(data[a2][t2]["ld_attr"])
     row = lambda a, t, ek, sk, swap: (a, t, data[a][t]["ld_z"], data[a][t].get("ld_wav"), data[a][t]["ld_z_con"],
-                                      data[a][t][ek], data[a][t][sk], swap, data[a][t].get("ld_motion"))
+                                      data[a][t][ek], data[a][t][sk], swap, data[a][t].get("ld_motion"), data[a][t].get("ld_waveform"))
     es = []
     for t in (t1, t2):
         es += [row(a1, t, "ld_z_emo", "ld_z_sty", ""), row(a2, t, "ld_z_emo", "ld_z_sty", ""),
@@ -245,7 +247,7 @@ def style_Xemo_transfer_jobs(data: Dict, actors: str, emotion: str) -> List[dict
 
     def row(a, label_take, t, ek="ld_z_emo", sk="ld_z_sty", swap=""):
         e = data[a][t]
-        return (a, label_take, e["ld_z"], e.get("ld_wav"), e["ld_z_con"], e[ek], e[sk], swap, e.get("ld_motion"))
+        return (a, label_take, e["ld_z"], e.get("ld_wav"), e["ld_z_con"], e[ek], e[sk], swap, e.get("ld_motion"), e.get("ld_waveform"))
     es = [row(a1, t1, t1), row(a2, t1, t3),
           row(a1, t1, t1, f"ld_z_emo_{a2}_{t4}", f"ld_z_sty_{a2}_{t4}", f"{a1}_{t1}_to_{a2}_{t4}"),
           row(a2, t1, t3, f"ld_z_emo_{a1}_{t2}", f"ld_z_sty_{a1}_{t2}", f"{a2}_{t3}_to_{a1}_{t2}"),
@@ -253,6 +255,14 @@ def style_Xemo_transfer_jobs(data: Dict, actors: str, emotion: str) -> List[dict
           row(a1, t2, t2, f"ld_z_emo_{a2}_{t3}", f"ld_z_sty_{a2}_{t3}", f"{a1}_{t2}_to_{a2}_{t3}"),
           row(a2, t2, t4, f"ld_z_emo_{a1}_{t1}", f"ld_z_sty_{a1}_{t1}", f"{a2}_{t4}_to_{a1}_{t1}")]
     return _transfer_jobs(es, a1_attr, a2_attr, "Style X Emo Transfer", emotion, min_over_z=False)
+
+
+def preview_audio_of_job(job: Optional[dict], n_files: int) -> list:
+    """amuse_amd.main --preview-video on a dataset-driven edit: what the preview of each of a job's `n_files` NPZ files carries - ("ld_waveform", waveform, c) for
+    clip c when the take's dictionary held `ld_waveform` (the content is the take's own: every job keeps its take's z_con), None otherwise.  The samples are cut
+    and converted only when a video is written (video.clip_pcm16)."""
+    w = None if job is None else job.get("waveform")
+    return [None if w is None else ("ld_waveform", w, c) for c in range(int(n_files))]
 
 
 def run_jobs(model, jobs: List[dict], return_latents: bool = False, batched: bool = True, rank: int = 0, world: int = 1) -> List[Optional[dict]]:
@@ -384,9 +394,12 @@ class trainer:
         # TRAIN_PARAM.test.beat_align (amuse_amd.main --beat-align; an extension, amuse_amd/beat_align.py): (NPZ, WAV) of every file the audio list wrote
         self.beat_pairs: List[tuple] = []
         self.beat_align_path = None
+        # amuse_amd.main --preview-video (an extension, amuse_amd/video.py): str(NPZ) -> the audio its preview carries - a WAV path, or ("ld_waveform", the take's
+        # 16 kHz waveform, clip index) from preview_audio_of_job
+        self.preview_audio: Dict[str, object] = {}
 
     # ------------------------------------------------------------------ visualizer stand-in
-    def _animate(self, sample_dict, video_dump, n_clips: int = 1):
+    def _animate(self, sample_dict, video_dump, n_clips: int = 1, audio=None, job=None):
         """CaMNVisualizer.animate_ldm_sample_v1 / _v2 up to the NPZ (visualizer.py:298-364).  sample_dict None = a job another rank sampled
         and writes: only the file tags of its `n_clips` files are drawn (6 characters each, npz_writer.write_sample), so that every
         rank names ITS files as the single-process run names them."""
@@ -394,7 +407,12 @@ class trainer:
             for _ in range(6 * int(n_clips)):
                 random.choice(string.ascii_uppercase + string.ascii_lowercase + string.digits)
             return
+        n_before = len(self.written)
         self.written += write_sample(sample_dict["feats"], video_dump, subject_of(sample_dict["info"]))
+        new = self.written[n_before:]
+        for p, a in zip(new, [audio] * len(new) if audio is not None else preview_audio_of_job(job, len(new))):
+            if a is not None:
+                self.preview_audio[str(p)] = a
 
     def _embed(self, path, baseline=False):
         return self._embed_all([path], baseline)[0]
@@ -631,7 +649,7 @@ class trainer:
                 for i, sd in enumerate(rst):
                     if sd is not None:
                         print(f"VISUALIZATION: LIST AUDIOS {i} =====>")
-                    self._animate(sd, video_dump_r / f"rst_{i}")
+                    self._animate(sd, video_dump_r / f"rst_{i}", audio=audios[k])
                 self.beat_pairs += [(p, audios[k]) for p in self.written[n_before:]]      # job k is audio k: what --beat-align scores afterwards
             # opt-in (amuse_amd.main --audio-metrics): the reference's collect_audio_metrics (infer_ldm.py:195-208) for each of this rank's audios,
             # beside its motion: <rep>/rst_0/<audio stem>/audio_metrics/fbank.pkl
@@ -685,7 +703,7 @@ class trainer:
                         video_dump_r = self.model_path / "viz" / f"{name}_{run_info}_{self.stamp}_E{ldm_epoch}" / f"rep{rep_i}"
                         assert self.viz_type in ["CaMN"], "[LDM EVAL] Invalid viz type: [%s]" % self.viz_type
                         for i, sample_dict in enumerate(rst):
-                            self._animate(sample_dict, video_dump_r / f"rst_{i}", jobs[i]["bsz"])
+                            self._animate(sample_dict, video_dump_r / f"rst_{i}", jobs[i]["bsz"], job=jobs[i])
                         if name == "emotion_control":                       # trainer.py:919
                             n = len(rst) if self.world > 1 else len([f for f in video_dump_r.iterdir() if f.is_dir()])   # (other ranks may still be writing)
                             assert n == 64, "[LDM EVAL] Invalid number of rst dirs: [%d]" % n
@@ -719,7 +737,7 @@ class trainer:
                 for i, sample_dict in enumerate(rst):
                     if sample_dict is not None:
                         print(f"VISUALIZATION: LIST AUDIOS {i} =====>")
-                    self._animate(sample_dict, video_dump_r / f"rst_{i}")
+                    self._animate(sample_dict, video_dump_r / f"rst_{i}", audio=wavs[spec[i][1]])      # (the content source WAV)
                 print(f"END VISUALIZATION: DEMO EMOTION CONTROL {rep_i + 1}/{reps} =====>")
         if self._motion_metrics_on():
             self._motion_metrics_write(ldm_epoch)

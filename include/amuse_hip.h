@@ -852,6 +852,50 @@ int amuse_beat_align_row(void);
 int amuse_beat_align(const unsigned char* onset_mask_dev, const int* audio_frames_dev, int T, const float* joints, const int* lengths_dev, int N, int F,
                      const amuse_beat_params* params, double* rows_out, unsigned char* beat_mask_out, void* stream);
 
+/* ------------------------------------------------------------------ preview video (csrc/amuse_mjpeg_host.hpp, amuse_mjpeg.hip, k_mjpeg.hip; amuse_amd/video.py)
+ * AN EXTENSION, off by default: the reference muxes its Blender frames with ffmpeg; this encodes the preview renderer's frames, still on the device, as
+ * baseline JPEG files for a Motion-JPEG AVI.  A PREVIEW encoder: fixed Huffman tables, no chroma subsampling; compared with libjpeg through PIL only
+ * (tests/mjpeg_ref.py restates it), and no player has been run against it in a test.
+ *
+ * Format: baseline sequential DCT (SOF0), 8 bit, components Y Cb Cr with H = V = 1, interleaved in one scan; one MCU = one 8 x 8 block per component in the
+ * order Y, Cb, Cr.  Segments in order: SOI, APP0 (JFIF 1.01, aspect 1:1), DQT luma, DQT chroma, SOF0 (true width and height), DHT DC luma, AC luma, DC chroma,
+ * AC chroma (ITU-T T.81 Annex K.3), DRI, SOS, entropy data, EOI.  Restart interval = one MCU row, Ri = ceil(width / 8); interval k >= 1 is preceded by RSTm,
+ * m = (k - 1) mod 8; DC predictors are 0 at the start of an interval; an interval is padded to a byte with 1-bits; a data byte 0xFF is followed by 0x00.
+ * Tables from quality by libjpeg's rule on Annex K.1 / K.2: s = q < 50 ? 5000 / q : 200 - 2 q, t = clamp((base s + 50) / 100, 1, 255), integers.
+ * Arithmetic, fp32: Y = 0.299 R + 0.587 G + 0.114 B - 128, Cb = -0.168735892 R - 0.331264108 G + 0.5 B, Cr = 0.5 R - 0.418687589 G - 0.081312411 B, not
+ * rounded; a width or height that is no multiple of 8 repeats the last column / row; F = orthonormal 8 x 8 DCT-II; coefficient = F / t rounded half away from
+ * zero, DC clamped to [-1024, 1023], AC to [-1023, 1023].  The entropy coding is a pure function of the coefficients and is bit exact: DC difference against
+ * the previous block of the component inside the interval, category + magnitude bits; AC run / size with ZRL (0xF0) per 16 zeros; EOB unless coefficient 63 is
+ * non-zero.
+ *
+ * amuse_mjpeg_tables: host only; the two tables of a quality in natural (row-major) order.
+ * amuse_mjpeg_plan: host only; *mcus_x = ceil(width / 8), *mcus_y = ceil(height / 8), *header_bytes = SOI .. SOS (629), *workspace_bytes = what
+ * amuse_mjpeg_reserve(frames) allocates (the coefficients, 384 bytes per MCU, and 8 bytes per interval + 4 per frame of sizes and offsets, each section rounded
+ * up to 256), *worst_case_bytes_per_frame = header + mcus_y x 2 ceil(mcus_x x 3 x 1660 / 8) + 2 (mcus_y - 1) + 2 (every block at its 1660-bit maximum, every
+ * byte stuffed): about 1.2 KB per MCU, which is why a call reserves no worst-case slots.  Any output pointer may be NULL. */
+typedef struct amuse_mjpeg amuse_mjpeg;
+int amuse_mjpeg_tables(int quality, unsigned char* luma_q64, unsigned char* chroma_q64);
+int amuse_mjpeg_plan(int width, int height, int frames, int* mcus_x, int* mcus_y, int* header_bytes, size_t* workspace_bytes, size_t* worst_case_bytes_per_frame);
+/* One encoder per (GPU, image size, quality): uploads the header, the Huffman words and the divisors.  NULL on failure (amuse_last_error). */
+amuse_mjpeg* amuse_mjpeg_create(int device, int width, int height, int quality);
+/* Makes the workspace hold calls of up to `frames` frames.  Grows only; an outgrown block is freed at destroy, never before.  With create, the only call here
+ * that allocates. */
+int amuse_mjpeg_reserve(amuse_mjpeg* e, int frames);
+void amuse_mjpeg_destroy(amuse_mjpeg* e);
+/* M frames, rgb dev uint8 [M][height][width][3] (amuse_render's rgb_out).  The frames come out back to back in out_dev, each a complete file SOI .. EOI;
+ * offsets_dev [M], sizes_dev [M] and *total_dev (the sum of the sizes) are written whatever out_capacity is.  NO BYTE IS WRITTEN AT OR BEYOND out_capacity,
+ * whatever the input: every store is checked.  A frame with offset + size <= out_capacity is complete; any other is not, and total_dev > out_capacity says so:
+ * call again with total bytes.  The same frame gives the same bytes alone, at any position of any batch, on any run: sizes become offsets by sums in a fixed
+ * order, no atomics.  Stream-ordered, allocates nothing, never synchronises (capture into a graph has not been tested).  One workspace per encoder: its calls must not overlap on two
+ * streams.  Checked before any HIP call, AMUSE_EINVAL otherwise: width and height 1..4096, quality 1..100 (create); every pointer non-NULL; M >= 1 and within
+ * the frames reserved; the launches' block counts within an int. */
+int amuse_mjpeg_encode(amuse_mjpeg* e, const unsigned char* rgb_dev, int M, unsigned char* out_dev, size_t out_capacity, unsigned long long* offsets_dev,
+                       unsigned int* sizes_dev, unsigned long long* total_dev, void* stream);
+/* tests: the transform alone; coef dev int16 [M][mcus_y][mcus_x][3][64], every block in zigzag order.  Uses no workspace. */
+int amuse_debug_mjpeg_coefficients(amuse_mjpeg* e, const unsigned char* rgb_dev, int M, short* coef_dev, void* stream);
+/* tests: the header (SOI .. SOS) of a size and quality into HOST memory; *bytes = its length, copied only when capacity holds it.  No GPU needed. */
+int amuse_debug_mjpeg_header(int width, int height, int quality, unsigned char* out_host, size_t capacity, int* bytes);
+
 #ifdef __cplusplus
 }
 #endif

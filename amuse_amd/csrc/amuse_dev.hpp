@@ -89,6 +89,18 @@ __device__ __forceinline__ F16Pair split_f16(f32x4 a, f32x4 b) {
     p.lo = __builtin_convertvector(v - __builtin_convertvector(p.hi, f32x8), f16x8);
     return p;
 }
+// one product of split operands, weights as the A operand: acc += Wl.xh + Wh.xl + Wh.xh (small terms first, the term order of gemm_ring_s)
+__device__ __forceinline__ f32x4 mfma3(f16x8 wh, f16x8 wl, const F16Pair& x, f32x4 acc) {
+    acc = mfma_f16(wl, x.hi, acc);
+    acc = mfma_f16(wh, x.lo, acc);
+    return mfma_f16(wh, x.hi, acc);
+}
+// the same product with the operands swapped: the accumulator holds the TRANSPOSED tile (rows along the registers)
+__device__ __forceinline__ f32x4 mfma3t(f16x8 wh, f16x8 wl, const F16Pair& x, f32x4 acc) {
+    acc = mfma_f16(x.hi, wl, acc);
+    acc = mfma_f16(x.lo, wh, acc);
+    return mfma_f16(x.hi, wh, acc);
+}
 __device__ __forceinline__ bf16x8 pack_bf16(f32x4 lo, f32x4 hi) {
     f32x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
     return __builtin_convertvector(v, bf16x8);  // v_cvt_pk_bf16_f32, round-to-nearest-even
@@ -164,6 +176,19 @@ __device__ __forceinline__ uint4 ldw(const uint4* p) {
 }
 __device__ __forceinline__ uint4 ldw_pos(const uint4* p, int pos) {
     return ldw(p);
+}
+// LDS-DMA: 64 lanes x 16 B from per-lane global addresses to LDS [dst, dst + 1 KiB), lane-linear.  Inline asm: the
+// compiler neither counts it in its s_waitcnt bookkeeping (its own waits can only become longer, never too short: vmcnt
+// retires in order) nor drains it at barriers; whoever issues it does the counting (amuse_stage.hpp: the stage protocol).
+__device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_dst) {
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "v"(gsrc), "s"(lds_dst)
+                 : "memory");
+}
+__device__ __forceinline__ unsigned lds_addr(const void* p) {
+    return (unsigned)(size_t)(__attribute__((address_space(3))) const void*)p;
 }
 // Lazy rescaling in the online-softmax loops whose scores leave the MFMA relative to the running maximum (amuse_fused.hpp attend, k_vae_fusedx.hip attend_x, k_audio.hip):
 // a chunk only moves a tile's running maxima when some score exceeds its row's by more than kAttnTau log2 units.  Until then p = exp2(s - m_run) may reach 2^kAttnTau
@@ -690,6 +715,30 @@ __device__ __forceinline__ f32x4 counter_normal4(uint64_t seed, uint64_t clip, u
     const float r1 = __builtin_amdgcn_sqrtf(-1.38629436111989061883f * __builtin_amdgcn_logf(u[2]));
     return f32x4{r0 * __builtin_amdgcn_cosf(u[1]), r0 * __builtin_amdgcn_sinf(u[1]),
                  r1 * __builtin_amdgcn_cosf(u[3]), r1 * __builtin_amdgcn_sinf(u[3])};
+}
+
+// ---- scheduler.step on one element (diffusers 0.17.1 DDIM / DDPM; amuse_hip.h amuse_schedule has the coefficients):
+//   x0 = (x_t - sb e) / sa, clipped to +-clipv if clipv > 0;   x_{t-1} = c0 x0 + cx x_t + ce e + sg z
+// Each product and sum is rounded on its own, like the scheduler's tensor ops: hipcc contracts even __fmul_rn / __fadd_rn pairs
+// into v_fma under its default -ffp-contract=fast, hence the pragmas.  FASTU (the 16-bit modes): reciprocal multiply
+// (inv_sa = 1 / sa) instead of the IEEE division.  A caller that fetches its noise only when sg != 0 passes sg = 0 here and
+// adds the term with sched_noise under its own test of sg.
+__device__ __forceinline__ float sched_noise(float nx, float sg, float z) {
+#pragma clang fp contract(off)
+    return __fadd_rn(nx, __fmul_rn(sg, z));
+}
+template <bool FASTU>
+__device__ __forceinline__ float sched_update(float xl, float e, float z, float sb, float sa, float c0, float cx, float ce, float sg, float clipv,
+                                              float inv_sa) {
+#pragma clang fp contract(off)
+    const float num = __fsub_rn(xl, __fmul_rn(sb, e));
+    float x0 = FASTU ? num * inv_sa : __fdiv_rn(num, sa);
+    if (clipv > 0.f) x0 = fminf(fmaxf(x0, -clipv), clipv);
+    float nx = __fmul_rn(c0, x0);
+    if (cx != 0.f) nx = __fadd_rn(nx, __fmul_rn(cx, xl));
+    if (ce != 0.f) nx = __fadd_rn(nx, __fmul_rn(ce, e));
+    if (sg != 0.f) nx = sched_noise(nx, sg, z);
+    return nx;
 }
 
 // ---- shared by the decode kernels (k_vae.hip, k_vae_fused.hip)

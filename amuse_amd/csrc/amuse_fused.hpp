@@ -1,10 +1,11 @@
 // The building blocks of the persistent per-clip kernels (k_vae_fused.hip: MotionPrior.decode; k_den_fused.hip: one step of the
-// diffusion_only Denoiser): operand-type macros of the two builds (bf16 / fp16), LDS map, LDS-DMA weight-stage ring (Stager),
+// diffusion_only Denoiser): operand-type macros of the two builds (bf16 / fp16), LDS map, the LDS-DMA weight-stage ring as they use it (Stager = amuse_stage.hpp StageRing<2>),
 // fragment-walking GEMM cores, and the S ~ 300 attention of one 16-query tile against K / V^T fragment images in LDS.
 // Included by a .hip AFTER it has (optionally) defined AMUSE_OP_F16; everything lives in namespace amuse's anonymous namespace.
 #pragma once
 #include "amuse_dev.hpp"
 #include "amuse_kernels.hpp"
+#include "amuse_stage.hpp"
 #include <cstdio>
 
 // Every kernel built on this header is compiled twice: as is (bf16 operands: k_vae_fused / launch_vae_fused, ...) and through a
@@ -37,9 +38,6 @@ constexpr int kWaves = 8;
 constexpr int kKeyRows = 320;             // 300 keys padded to 20 tiles
 constexpr int kPairs = kKeyRows / 32;     // 10 key-tile pairs
 constexpr int kKvBytes = kKeyRows * 64 + kPairs * 2 * 16 * 64;   // K fragments 20 KiB + V^T fragments 20 KiB
-constexpr int kStage = kVaeFusedStageUnits;                      // 16 units = 16 KiB per stage
-constexpr int kStageBytes = kStage * 1024;
-constexpr int kWBufs = 3;
 constexpr int kPvSlot = 8192;             // one block's small parameters (7,680 B) rounded up to whole DMA pieces
 constexpr int kCaBytes = 5120;            // [9][128] floats rounded up to whole DMA pieces
 constexpr int kQStride = 100;            // staging row stride (floats) of one 96-feature quarter (16 joints) of the last stage
@@ -78,44 +76,8 @@ __device__ int g_fprof_n;
 #define FSTAMP(tag) do { } while (0)
 #endif
 
-// ---- LDS-DMA: 64 lanes x 16 B from per-lane global addresses to LDS [dst, dst + 1 KiB), lane-linear.  Inline asm: the
-// compiler neither counts it in its s_waitcnt bookkeeping (its own waits can only become longer, never too short: vmcnt
-// retires in order) nor drains it at barriers; the stage protocol below does the counting.
-__device__ __forceinline__ void glds16(const uint4* gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(gsrc), "s"(lds_dst)
-                 : "memory");
-}
-__device__ __forceinline__ unsigned lds_addr(const void* p) {
-    return (unsigned)(size_t)(__attribute__((address_space(3))) const void*)p;
-}
-
-struct Stager {
-    const uint4* src;   // this lane's source address of the wave's pieces of the NEXT stage to fetch
-    unsigned dst0;      // LDS byte address of the wave's pieces inside buffer 0
-    const char* ring;   // weight ring base (generic pointer) + lane * 16
-    int widx, ridx;     // buffer the next fetch fills / buffer the current stage reads
-};
-// (A wave-uniform source base in SGPRs + a 32-bit lane offset - the saddr form of global_load_lds_dwordx4 - and 32-bit LDS addresses for
-// the ring were tried in round 4 to free the four registers these pointers hold: hipcc's allocation got WORSE, 28 -> 46 spilled registers.)
-__device__ __forceinline__ void stage_fetch(Stager& s) {
-    const unsigned d = __builtin_amdgcn_readfirstlane(s.dst0 + s.widx * kStageBytes);
-#pragma unroll
-    for (int i = 0; i < 2; ++i) glds16(s.src + i * 64, d + i * 1024);
-    s.src += kStage * 64;
-    s.widx = s.widx == kWBufs - 1 ? 0 : s.widx + 1;
-}
-// end of a stage: all of this wave's DMA except the two pieces of the fetch issued in this stage has landed, its LDS reads
-// and writes are done; after the barrier that holds for every wave - the next stage's buffer is complete, this stage's is free
-__device__ __forceinline__ void stage_end(Stager& s) {
-    asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    s.ridx = s.ridx == kWBufs - 1 ? 0 : s.ridx + 1;
-}
-__device__ __forceinline__ OPV wfrag(const Stager& s, int u) {
-    return __builtin_bit_cast(OPV, *reinterpret_cast<const uint4*>(s.ring + s.ridx * kStageBytes + u * 1024));
-}
+// the weight-stage ring (amuse_stage.hpp) as these kernels use it: every wave copies two pieces of every 16-piece stage
+using Stager = StageRing<2>;
 
 // f(u, fragment) for the units U0 .. U0 + NU - 1 of the current stage, the fragments read kFragAhead units ahead of their use.
 // (Left to hipcc, a unit loop recycles ONE fragment register: read, wait for the whole LDS round trip, MFMAs, next read - the
@@ -125,11 +87,11 @@ __device__ __forceinline__ void for_units(const Stager& s, F&& f) {
     constexpr int PF = kFragAhead < NU ? kFragAhead : NU;
     OPV wf[PF];
 #pragma unroll
-    for (int u = 0; u < PF; ++u) wf[u] = wfrag(s, U0 + u);
+    for (int u = 0; u < PF; ++u) wf[u] = wfrag<OPV>(s, U0 + u);
 #pragma unroll
     for (int u = 0; u < NU; ++u) {
         const OPV cur = wf[u % PF];
-        if (u + PF < NU) wf[u % PF] = wfrag(s, U0 + u + PF);
+        if (u + PF < NU) wf[u % PF] = wfrag<OPV>(s, U0 + u + PF);
         f(u, cur);
     }
 }
@@ -141,12 +103,12 @@ __device__ __forceinline__ void gemm5(f32x4 (&acc)[NT][NO], const OPV (&xb)[NT][
     constexpr int NU = NO * NC, PF = kFragAhead;
     OPV wf[NU < PF ? NU : PF];
 #pragma unroll
-    for (int u = 0; u < PF && u < NU; ++u) wf[u] = wfrag(s, U0 + u);
+    for (int u = 0; u < PF && u < NU; ++u) wf[u] = wfrag<OPV>(s, U0 + u);
 #pragma unroll
     for (int u = 0; u < NU; ++u) {
         const int c = u / NO, o = u - c * NO;
         const OPV cur = wf[u % PF];
-        if (u + PF < NU) wf[u % PF] = wfrag(s, U0 + u + PF);
+        if (u + PF < NU) wf[u % PF] = wfrag<OPV>(s, U0 + u + PF);
 #pragma unroll
         for (int j = 0; j < NT; ++j) acc[j][o] = OP_MFMA(cur, xb[j][c], acc[j][o]);
     }

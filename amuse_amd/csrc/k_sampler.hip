@@ -455,25 +455,11 @@ __global__ __launch_bounds__(256, 1) void k_sample(Args a) {
             }
             constexpr bool FASTU = (PREC == PREC_BF16);  // bf16 mode: reciprocal multiply instead of IEEE division
             const float inv_sa = 1.0f / sa;
-            {
-// each product and sum rounded on its own, like the scheduler's tensor ops (hipcc contracts even __fmul_rn /
-// __fadd_rn pairs into v_fma under its default -ffp-contract=fast)
-#pragma clang fp contract(off)
 #pragma unroll
             for (int t = 0; t < kTiles; ++t) {
 #pragma unroll
-                for (int m = 0; m < 4; ++m) {
-                    const float e = x[t][m], xl = lat[t][m];
-                    const float num = __fsub_rn(xl, __fmul_rn(sb, e));
-                    float x0 = FASTU ? num * inv_sa : __fdiv_rn(num, sa);
-                    if (clipv > 0.f) x0 = fminf(fmaxf(x0, -clipv), clipv);
-                    float nx = __fmul_rn(c0, x0);
-                    if (cx != 0.f) nx = __fadd_rn(nx, __fmul_rn(cx, xl));
-                    if (ce != 0.f) nx = __fadd_rn(nx, __fmul_rn(ce, e));
-                    if (sg != 0.f) nx = __fadd_rn(nx, __fmul_rn(sg, zt[t][m]));
-                    lat[t][m] = nx;
-                }
-            }
+                for (int m = 0; m < 4; ++m)
+                    lat[t][m] = sched_update<FASTU>(lat[t][m], x[t][m], zt[t][m], sb, sa, c0, cx, ce, sg, clipv, inv_sa);
             }
             stamp<PROF>(pf);  // scheduler update done
             if (a.traj_out && is_lat && wave == 0) {

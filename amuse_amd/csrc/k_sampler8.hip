@@ -29,8 +29,7 @@
 // bf16 operands ON it (slots (c, c), c < 4), so the gather of one combine never aliases the partial writes of the
 // next - | row statistics | bf16 skip stack | small parameters | static token rows | latent | double-buffered time
 // token.
-#include "amuse_dev.hpp"
-#include "amuse_kernels.hpp"
+#include "amuse_sample8.hpp"
 
 // This file is compiled twice: as is (bf16 operands: k_sample8 / launch_sample8) and through k_sampler8h.hip with AMUSE_OP_F16
 // defined (fp16 operands, AMUSE_PREC_F16: k_sample8h / launch_sample8h) - the same instruction stream on v_mfma_f32_16x16x32_f16
@@ -57,9 +56,7 @@ namespace amuse {
 
 namespace {
 
-constexpr int kR8 = kRing8;
-constexpr int kA8Bytes = 8 * kTiles * 64 * 16;                 // 65,536
-constexpr int kStat8Off = kA8Bytes;                            // [4 reducers][16 rows] float2 (1 KiB reserved)
+// (amuse_sample8.hpp: combine matrix A8, then the row statistics at kStat8Off)
 constexpr int kSkip8Off = kStat8Off + 8 * 16 * 8;              // [4 levels][4 pairs][64] uint4
 constexpr int kPv8Off = kSkip8Off + 4 * 4 * 64 * 16;
 constexpr int kPv8Floats = kLayers * kEncPv + 4 * kD + 2 * kD;
@@ -67,8 +64,6 @@ constexpr int kTokRows8Off = kPv8Off + kPv8Floats * 4;         // [8 tiles][64] 
 constexpr int kLat8Off = kTokRows8Off + kTiles * 64 * 16;      // [8 tiles][64] f32x4: the latent (rows tok == 0)
 constexpr int kTT8Off = kLat8Off + kTiles * 64 * 16;           // [2][128] float
 static_assert(kTT8Off + 2 * kD * 4 == kSample8LdsBytes, "LDS layout");
-
-using Ring = WRing<kR8>;
 
 // Issue split of an A wave's 32 units inside the out_proj (C1) and linear2 (C2) combines: N0 before the first barrier
 // (C2 only - there the A waves arrive early), N1 / N2 after the first / second barrier, the rest after the gather.
@@ -80,9 +75,6 @@ constexpr int kBEarly = 20;
 // VALU instructions scheduled behind each MFMA while one FFN quarter's GELU overlaps the other quarter's GEMM (ffn_half)
 constexpr int kFfnValuPerMfma = 7;
 
-__device__ __forceinline__ f32x4* a8_slot(char* lds, int row, int col, int lane) {
-    return reinterpret_cast<f32x4*>(lds) + (row * kTiles + col) * 64 + lane;
-}
 // packed bf16 operand c (feature tiles 2c, 2c+1 of the residual stream) is published in diagonal slot (c, c)
 __device__ __forceinline__ uint4* xb_slot(char* lds, int c, int lane) {
     return reinterpret_cast<uint4*>(a8_slot(lds, c, c, lane));
@@ -102,13 +94,7 @@ __device__ __forceinline__ void gemm_xb(f32x4 (&acc)[NO], const OPV (&xb)[4], co
 // ---- split-K combine, B waves reduce.  NP = 4: partials from the A waves only (out_proj); NP = 8: from all waves
 // (linear2).  B wave h reduces feature tiles 2h, 2h+1: residual + bias, LayerNorm (row statistics of the four
 // 32-feature slices merged with Chan's formula), publishes them on the diagonal of A8; every wave gathers.
-// Row of A8 holding writer w's partial of tile t - never the diagonal, and the tile's reducer (wave 4 + t/2) keeps its
-// own partial in registers:
-__device__ __forceinline__ constexpr int part_row(int w, int t) {
-    const int red = 4 + (t >> 1);
-    const int k = w - (w > red ? 1 : 0);
-    return k + (k >= t ? 1 : 0);
-}
+// Partials travel through the rows part_row (amuse_sample8.hpp) assigns.
 // LN = false (U-Net skip linear): tiles = sum + bias - no residual, no LayerNorm, and one barrier less.
 template <int W, int NP, bool FAST, bool LN, bool DRP>
 __device__ __forceinline__ void combine_red(f32x4 (&part)[kTiles], f32x4 (&xo)[2], OPV (&xb)[4], const float* bias,
@@ -156,26 +142,11 @@ __device__ __forceinline__ void combine_red(f32x4 (&part)[kTiles], f32x4 (&xo)[2
         }
     }
     if constexpr (LN) {
-    float s = ((y[0][0] + y[0][1]) + (y[0][2] + y[0][3])) + ((y[1][0] + y[1][1]) + (y[1][2] + y[1][3]));
-    s = allreduce_g_sum(s);
-    const float mw = s * (1.0f / 32.0f);
-    float m2 = 0.f;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            const float d = y[i][m] - mw;
-            m2 += d * d;
-        }
-    m2 = allreduce_g_sum(m2);
-    if (g == 0) stats[W * 16 + r] = float2{mw, m2};
+    const float2 st = row_stats32(y);
+    if (g == 0) stats[W * 16 + r] = st;
     __syncthreads();
-    const float2 s0 = stats[r], s1 = stats[16 + r], s2 = stats[32 + r], s3 = stats[48 + r];
-    const float mean = ((s0.x + s1.x) + (s2.x + s3.x)) * 0.25f;
-    const float d0 = s0.x - mean, d1 = s1.x - mean, d2 = s2.x - mean, d3 = s3.x - mean;
-    const float M2 = ((s0.y + s1.y) + (s2.y + s3.y)) + 32.0f * ((d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3));
-    const float var = M2 * (1.0f / kD) + 1e-5f;
-    const float rstd = FAST ? __builtin_amdgcn_rsqf(var) : 1.0f / sqrtf(var);
+    const float2 ms = row_stats_merge<FAST>(stats, r);
+    const float mean = ms.x, rstd = ms.y;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -230,10 +201,6 @@ __device__ __forceinline__ void combine_publish(const f32x4 (&part)[kTiles], OPV
     for (int c = 0; c < 4; ++c) xb[c] = __builtin_bit_cast(OPV, *xb_slot(lds, c, lane));
     ring_issue<N3, kR8, (IPH0 + N0 + N1 + N2) % kR8>(rg);
 }
-
-// Slot of the combine matrix through which A wave h hands the skip-input half of the next output block's skip linear
-// (feature tile t = 2h + i) to B wave h: off the diagonal, written after the reducers have read their partials.
-__device__ __forceinline__ f32x4* u_slot(char* lds, int t, int lane) { return a8_slot(lds, t == 6 ? 5 : 6, t, lane); }
 
 // The A waves' side of the linear2 combine: as combine_publish, fetching the next block's group of 32 units - its
 // first 8 units into slots 24..31, then q, k, v into slots 0..23.  In front of an ordinary block the leading 8 are out_proj.
@@ -299,19 +266,6 @@ __device__ __forceinline__ void attention_head8(const f32x4 (&q)[2], const f32x4
         o[td] = OP_MFMA(OP_PACK(v[td], splat4(0.f)), OP_PACK(p, splat4(0.f)), splat4(0.f));
 }
 
-// optional phase timeline: s_memtime stamps by lane 0 of every wave of workgroup 0 during ONE step ([8][96] u64)
-struct Prof8 {
-    unsigned long long* out;
-    int idx;
-    bool on;
-};
-template <bool PROF>
-__device__ __forceinline__ void stamp8(Prof8& pf) {
-    if constexpr (PROF) {
-        if (pf.on) pf.out[pf.idx++] = __builtin_readcyclecounter();
-    }
-}
-
 // GELU (amuse_dev.hpp OP_GELU: the result is an MFMA operand, i.e. rounded to bf16 next) on one FFN quarter (two
 // hidden tiles); linear1's bias is already in the accumulators (ffn_half)
 // DROP: then the FFN's inner dropout (site 2), keep bits 0..3 / 4..7 of dbits for the two tiles
@@ -361,29 +315,6 @@ __device__ __forceinline__ void ffn_half(f32x4 (&part)[kTiles], const OPV (&xb)[
     }
     __builtin_amdgcn_sched_barrier(0);
     gemm_ring<P, kTiles, 2, false, kR8, 24, false>(part, hb, rg);
-}
-
-// per-lane constants of the tile (row-lane layout: lane (g, r) holds row r)
-struct Lane8 {
-    int lane, g, r, cl, tok;
-    long clip;
-    bool valid, is_lat;
-};
-// Cheap to derive, expensive to keep: held across the block loop these constants get spilled to scratch (the ring
-// leaves no slack), so the step loop re-derives them where it needs them from an opaque copy of the lane id.
-__device__ __forceinline__ Lane8 lane_info(const SampleKernelArgs& a, int lane) {
-    asm volatile("" : "+v"(lane));
-    Lane8 L;
-    L.lane = lane;
-    L.g = lane >> 4;
-    L.r = lane & 15;
-    const int S = a.S, R = S * a.G;
-    L.cl = L.r / S;
-    L.tok = L.r - L.cl * S;
-    L.clip = (long)blockIdx.x * a.G + L.cl;
-    L.valid = (L.r < R) && (L.clip < (long)a.B);
-    L.is_lat = L.valid && L.tok == 0;
-    return L;
 }
 
 // ---- train-mode sampling (amuse_hip.h amuse_set_sample_dropout): the uniform part of the mask counters; the per-lane part (global
@@ -507,11 +438,6 @@ __device__ __forceinline__ void encoder_block8(OPV (&xb)[4], f32x4 (&xo)[2], Rin
     stamp8<PROF>(pf);  // 4: combine 2
 }
 
-// debugging taps: one feature tile of the [16 x 128] residual stream
-__device__ __forceinline__ void store_tap_tile(float* tap, int slot, int t, const f32x4& v, int g, int r) {
-    st4(tap + ((size_t)slot * 16 + r) * kD + 16 * t + 4 * g, v);
-}
-
 // The whole T-step loop of one role.  Both roles execute the same sequence of workgroup barriers.
 template <bool ROLEA, bool PROF, bool DROP, class Args>
 __device__ __forceinline__ void role_loop8(const Args& a, char* smem, int w8, const Lane8& L0) {
@@ -525,14 +451,9 @@ __device__ __forceinline__ void role_loop8(const Args& a, char* smem, int w8, co
     const float* pv_final = pv_skip + 4 * kD;
     const int lane = L0.lane, g = L0.g, r = L0.r, h = w8 & 3;
     const int S = a.S, R = S * a.G;
-    // attention key mask for this lane's query row: keys j = 4 g + m of the SAME clip; padding rows attend to
-    // themselves only (keeps them finite, they never touch valid rows)
-    bool kvalid[4];
+    bool kvalid[4];   // attention key mask of this lane's query row
 #pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        const int j = 4 * g + m;
-        kvalid[m] = L0.valid ? (j < R && (j / S) == L0.cl) : (j == r);
-    }
+    for (int m = 0; m < 4; ++m) kvalid[m] = key_valid8(L0, 4 * g + m, S, R);
     const bool tap = !ROLEA && a.tap_out != nullptr && blockIdx.x == 0;  // the B waves tap their own fp32 tiles
     const uint32_t wbase_units = ROLEA ? (uint32_t)w8 * (a.wave_units_a + kR8)
                                        : 4u * (a.wave_units_a + kR8) + (uint32_t)(w8 - 4) * a.wave_units_b;
@@ -558,13 +479,7 @@ __device__ __forceinline__ void role_loop8(const Args& a, char* smem, int w8, co
         f32x4 xo[2] = {splat4(0.f), splat4(0.f)};
         {
             const Lane8 L = lane_info(a, lane);
-            auto assemble = [&](int t) -> f32x4 {
-                const f32x4 sv = tokrows[t * 64 + lane];
-                // unconditional loads (a divergent branch around them costs registers)
-                f32x4 tt = ld4(ttl + (step & 1) * kD + 16 * t + 4 * g);
-                if (a.time_tok_clip) tt = ld4(a.time_tok_clip + (size_t)(L.valid ? L.clip : 0) * kD + 16 * t + 4 * g);
-                return !L.valid ? splat4(0.f) : (L.tok == 0 ? latl[t * 64 + lane] + sv : (L.tok == 1 ? tt : sv));
-            };
+            auto assemble = [&](int t) { return assemble_tile(a, L, lane, g, tokrows, ttl, latl, step, t); };
 #pragma unroll
             for (int c = 0; c < 4; ++c) xb[c] = OP_PACK(assemble(2 * c), assemble(2 * c + 1));
             if constexpr (!ROLEA) {
@@ -625,28 +540,13 @@ __device__ __forceinline__ void role_loop8(const Args& a, char* smem, int w8, co
         // ---- final LayerNorm (SkipTransformerEncoder.norm) + scheduler.step (diffusers 0.17.1 DDIM / DDPM;
         // amuse_hip.h amuse_schedule) on the B waves' own tiles; the latent lives in LDS
         if constexpr (!ROLEA) {
-            float sm = ((xo[0][0] + xo[0][1]) + (xo[0][2] + xo[0][3])) + ((xo[1][0] + xo[1][1]) + (xo[1][2] + xo[1][3]));
-            sm = allreduce_g_sum(sm);
-            const float mw = sm * (1.0f / 32.0f);
-            float m2 = 0.f;
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int m = 0; m < 4; ++m) {
-                    const float d = xo[i][m] - mw;
-                    m2 += d * d;
-                }
-            m2 = allreduce_g_sum(m2);
-            if (g == 0) stats[h * 16 + r] = float2{mw, m2};
+            const float2 st = row_stats32(xo);
+            if (g == 0) stats[h * 16 + r] = st;
         }
         __syncthreads();
         if constexpr (!ROLEA) {
             const Lane8 L = lane_info(a, lane);
-            const float2 s0 = stats[L.r], s1 = stats[16 + L.r], s2 = stats[32 + L.r], s3 = stats[48 + L.r];
-            const float mean = ((s0.x + s1.x) + (s2.x + s3.x)) * 0.25f;
-            const float d0 = s0.x - mean, d1 = s1.x - mean, d2 = s2.x - mean, d3 = s3.x - mean;
-            const float M2 = ((s0.y + s1.y) + (s2.y + s3.y)) + 32.0f * ((d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3));
-            const float rstd = __builtin_amdgcn_rsqf(M2 * (1.0f / kD) + 1e-5f);
+            const float2 ms = row_stats_merge<true>(stats, L.r);
             const float* cf = a.coef + (size_t)step * 8;
             const float sb = cf[0], sa = cf[1], c0 = cf[2], cx = cf[3], ce = cf[4], sg = cf[5], clipv = cf[6];
             const float inv_sa = 1.0f / sa;
@@ -656,33 +556,19 @@ __device__ __forceinline__ void role_loop8(const Args& a, char* smem, int w8, co
                 const f32x4 ga = ld4(pv_final + f), be = ld4(pv_final + kD + f);
                 f32x4 e;
 #pragma unroll
-                for (int m = 0; m < 4; ++m) e[m] = (xo[i][m] - mean) * rstd * ga[m] + be[m];
+                for (int m = 0; m < 4; ++m) e[m] = (xo[i][m] - ms.x) * ms.y * ga[m] + be[m];
                 if (tap && step == 0) store_tap_tile(a.tap_out, 10, t, e, L.g, L.r);
                 if (a.eps_out && L.is_lat && step == a.T - 1) st4(a.eps_out + (size_t)L.clip * kD + f, e);
                 if (!a.no_update) {
                     // ancestral noise of the latent rows: counter (global clip, step, feature group) - the values
-                    // amuse_counter_normal exposes
+                    // amuse_counter_normal exposes.  (Fetched here: as a shared function it changes the register allocation of the kernels without stamps.)
                     f32x4 z = splat4(0.f);
                     if (sg != 0.f && L.is_lat)
                         z = a.step_noise ? ld4(a.step_noise + ((size_t)step * a.B + L.clip) * kD + f)
                                          : counter_normal4(a.seed, a.clip0 + (uint64_t)L.clip, (uint32_t)step, (uint32_t)(4 * t + L.g), 1u);
                     f32x4 l = latl[t * 64 + L.lane];
-                    {
-// each product and sum rounded on its own, like the scheduler's tensor ops (see k_sampler.hip)
-#pragma clang fp contract(off)
 #pragma unroll
-                    for (int m = 0; m < 4; ++m) {
-                        const float xl = l[m];
-                        const float num = __fsub_rn(xl, __fmul_rn(sb, e[m]));
-                        float x0 = num * inv_sa;
-                        if (clipv > 0.f) x0 = fminf(fmaxf(x0, -clipv), clipv);
-                        float nx = __fmul_rn(c0, x0);
-                        if (cx != 0.f) nx = __fadd_rn(nx, __fmul_rn(cx, xl));
-                        if (ce != 0.f) nx = __fadd_rn(nx, __fmul_rn(ce, e[m]));
-                        if (sg != 0.f) nx = __fadd_rn(nx, __fmul_rn(sg, z[m]));
-                        l[m] = nx;
-                    }
-                    }
+                    for (int m = 0; m < 4; ++m) l[m] = sched_update<true>(l[m], e[m], z[m], sb, sa, c0, cx, ce, sg, clipv, inv_sa);
                     latl[t * 64 + L.lane] = l;
                     if (a.traj_out && L.is_lat) st4(a.traj_out + ((size_t)step * a.B + L.clip) * kD + f, l);
                 }
@@ -707,22 +593,13 @@ __global__ __launch_bounds__(512) void OP_KERNEL(Args a) {
     }
     for (int i = threadIdx.x; i < (4 * kD + 2 * kD) / 4; i += 512) st4(pvl + kLayers * kEncPv + 4 * i, ld4(a.pvec + PV_SKIP_B + 4 * i));
     const int w8 = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int S = a.S;
     const Lane8 L = lane_info(a, threadIdx.x & 63);
-    // static token rows (pe[0] under the latent rows, condition tokens; denoiser.py:174,180-181) and the initial
-    // latent -> LDS (registers are the scarce resource at 2 waves / SIMD; wave 0 owns the latent's update)
+    // static token rows and the initial latent -> LDS (wave 0 owns the latent's update); the first step's time token
     if (w8 == 0) {
 #pragma unroll
         for (int t = 0; t < kTiles; ++t) {
             const int f = 16 * t + 4 * L.g;
-            f32x4 sv = splat4(0.f), l0 = splat4(0.f);
-            if (L.valid) {
-                if (L.tok == 0) sv = ld4(a.pe0 + f);
-                else if (L.tok >= 2) sv = ld4(a.cond_tok + ((size_t)L.clip * (S - 2) + (L.tok - 2)) * kD + f);
-            }
-            if (L.is_lat)
-                l0 = a.x_init ? ld4(a.x_init + (size_t)L.clip * kD + f)
-                              : counter_normal4(a.seed, a.clip0 + (uint64_t)L.clip, 0u, (uint32_t)(4 * t + L.g), 0u);
+            const f32x4 sv = static_row4(a, L, f), l0 = init_latent4(a, L, t, f);
             tokrows[t * 64 + L.lane] = sv;
             latl[t * 64 + L.lane] = l0;
         }

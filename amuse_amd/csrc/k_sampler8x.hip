@@ -28,16 +28,13 @@
 //
 // LDS (134,144 B): combine matrix A8 [8 rows][8 tiles][64] f32x4 | row statistics | small parameters (2 slots + tail) | skip
 // stack | static token rows | latent | double-buffered time token.
-#include "amuse_dev.hpp"
-#include "amuse_kernels.hpp"
+#include "amuse_sample8.hpp"
 
 namespace amuse {
 
 namespace {
 
-constexpr int kR8 = kRing8;
-constexpr int kA8Bytes = 8 * kTiles * 64 * 16;                 // 65,536
-constexpr int kStat8Off = kA8Bytes;                            // [4 reducers][16 rows] float2 (1 KiB reserved)
+// (amuse_sample8.hpp: combine matrix A8, then the row statistics at kStat8Off)
 // small parameters: the CURRENT and the NEXT block's (two slots of 7 KiB, filled by LDS-DMA a block ahead) + skip-linear biases +
 // final LayerNorm.  (All nine blocks resident cost 61.5 KiB - the room the skip stack needs as split operands.)
 constexpr int kPvSlotFloats = 7 * 256;                         // kEncPv = 1664 floats rounded up to whole 1 KiB DMA pieces
@@ -50,8 +47,6 @@ constexpr int kLat8Off = kTokRows8Off + kTiles * 64 * 16;      // [8 tiles][64] 
 constexpr int kTT8Off = kLat8Off + kTiles * 64 * 16;           // [2][128] float
 static_assert(kTT8Off + 2 * kD * 4 == kSample8xLdsBytes, "LDS layout");
 
-using Ring = WRing<kR8>;
-
 // Issue split of an A wave's 32 units inside the out_proj (C1) and linear2 (C2) combines: N0 before the first barrier,
 // N1 / N2 after the first / second barrier, the rest after the gather.
 constexpr int kXC1N1 = 12, kXC1N2 = 12, kXC2N1 = 8;
@@ -63,9 +58,6 @@ constexpr int kXBPrio = 3;
 // GELU takes libm erff: same-box wall clock of this kernel, us per step: libm 71.4, the branch-free fit (amuse_dev.hpp erf_bf) 75.3,
 // Abramowitz-Stegun on rcp / exp2 79.7 (docs/history.md; the 3 : 1 FFN split of tools/probes/fp32x_ffn_3_1_split ranked them the other way round).
 
-__device__ __forceinline__ f32x4* a8_slot(char* lds, int row, int col, int lane) {
-    return reinterpret_cast<f32x4*>(lds) + (row * kTiles + col) * 64 + lane;
-}
 // split operand c (feature tiles 2c, 2c+1 of the residual stream): hi in diagonal slot (c, c), lo in (4 + c, 4 + c) -
 // partials never use the diagonal (part_row below)
 __device__ __forceinline__ uint4* xs_hi_slot(char* lds, int c, int lane) { return reinterpret_cast<uint4*>(a8_slot(lds, c, c, lane)); }
@@ -108,13 +100,7 @@ __device__ __forceinline__ void gemm_xs(f32x4 (&acc)[NO], const F16Pair* xs, Rin
 }
 
 // ---- split-K combine, B waves reduce (k_sampler8.hip combine_red): NP = 4 partials from the A waves (out_proj) or 8
-// from all waves (linear2).  Row of A8 holding writer w's partial of tile t - never the diagonal, and the tile's
-// reducer (wave 4 + t/2) keeps its own partial in registers:
-__device__ __forceinline__ constexpr int part_row(int w, int t) {
-    const int red = 4 + (t >> 1);
-    const int k = w - (w > red ? 1 : 0);
-    return k + (k >= t ? 1 : 0);
-}
+// from all waves (linear2); partials travel through the rows part_row (amuse_sample8.hpp) assigns.
 template <int W, int NP>
 __device__ __forceinline__ void combine_red(f32x4 (&part)[kTiles], f32x4 (&xo)[2], F16Pair (&xs)[4], const float* bias,
                                             const float* gamma, const float* beta, char* lds, int lane) {
@@ -154,25 +140,11 @@ __device__ __forceinline__ void combine_red(f32x4 (&part)[kTiles], f32x4 (&xo)[2
             y[i] = xo[i] + (sum + bi[i]);
         }
     }
-    float s = ((y[0][0] + y[0][1]) + (y[0][2] + y[0][3])) + ((y[1][0] + y[1][1]) + (y[1][2] + y[1][3]));
-    s = allreduce_g_sum(s);
-    const float mw = s * (1.0f / 32.0f);
-    float m2 = 0.f;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            const float d = y[i][m] - mw;
-            m2 += d * d;
-        }
-    m2 = allreduce_g_sum(m2);
-    if (g == 0) stats[W * 16 + r] = float2{mw, m2};
+    const float2 st = row_stats32(y);
+    if (g == 0) stats[W * 16 + r] = st;
     __syncthreads();
-    const float2 s0 = stats[r], s1 = stats[16 + r], s2 = stats[32 + r], s3 = stats[48 + r];
-    const float mean = ((s0.x + s1.x) + (s2.x + s3.x)) * 0.25f;
-    const float d0 = s0.x - mean, d1 = s1.x - mean, d2 = s2.x - mean, d3 = s3.x - mean;
-    const float M2 = ((s0.y + s1.y) + (s2.y + s3.y)) + 32.0f * ((d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3));
-    const float rstd = 1.0f / sqrtf(M2 * (1.0f / kD) + 1e-5f);
+    const float2 ms = row_stats_merge<false>(stats, r);
+    const float mean = ms.x, rstd = ms.y;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -198,28 +170,11 @@ __device__ __forceinline__ void combine_reduce(f32x4 (&part)[kTiles], f32x4 (&xo
     else combine_red<3, NP>(part, xo, xs, bias, gamma, beta, lds, lane);
 }
 
-// Slot of the combine matrix through which A wave h hands the skip-input half of the next output block's skip linear
-// (feature tile t = 2h + i) to B wave h: off the diagonal, written after the reducers have read their partials.
-__device__ __forceinline__ f32x4* u_slot(char* lds, int t, int lane) { return a8_slot(lds, t == 6 ? 5 : 6, t, lane); }
 // where B wave h publishes its two tiles of a skip linear's result: rows 7 (hi) and 5 (lo), columns 0..3 - not the
 // diagonal (lagging waves may still be gathering the linear2 combine's operands), not u_slot's cells, not a row the next
 // out_proj combine's partials use (rows 0..4)
 __device__ __forceinline__ uint4* sk_hi_slot(char* lds, int c, int lane) { return reinterpret_cast<uint4*>(a8_slot(lds, 7, c, lane)); }
 __device__ __forceinline__ uint4* sk_lo_slot(char* lds, int c, int lane) { return reinterpret_cast<uint4*>(a8_slot(lds, 5, c, lane)); }
-
-// LDS-DMA: 64 lanes x 16 B from per-lane global addresses to LDS [dst, dst + 1 KiB), lane-linear (k_vae_fused.hip glds16).  Inline
-// asm: hipcc does not count it in its s_waitcnt bookkeeping - its own waits can only become longer, never too short (vmcnt
-// retires in order) - and does not drain it at barriers.  Completion before the data is read: see combine_publish_c1.
-__device__ __forceinline__ void glds16(const uint4* gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(gsrc), "s"(lds_dst)
-                 : "memory");
-}
-__device__ __forceinline__ unsigned lds_addr(const void* p) {
-    return (unsigned)(size_t)(__attribute__((address_space(3))) const void*)p;
-}
 
 // The A waves' side of the out_proj combine: publish the partial, then the barriers and the gather - with the issue of
 // this wave's first 32 FFN units (linear1 of both quarters) in between, into the whole (empty) ring.  Two more jobs ride here,
@@ -323,19 +278,6 @@ __device__ __forceinline__ void attention_head8x(const f32x4 (&q)[2], const f32x
         o[td] = mfma_f16(vs.lo, ps.hi, splat4(0.f));
         o[td] = mfma_f16(vs.hi, ps.lo, o[td]);
         o[td] = mfma_f16(vs.hi, ps.hi, o[td]);
-    }
-}
-
-// optional phase timeline: s_memtime stamps by lane 0 of every wave of workgroup 0 during ONE step ([8][96] u64)
-struct Prof8 {
-    unsigned long long* out;
-    int idx;
-    bool on;
-};
-template <bool PROF>
-__device__ __forceinline__ void stamp8(Prof8& pf) {
-    if constexpr (PROF) {
-        if (pf.on) pf.out[pf.idx++] = __builtin_readcyclecounter();
     }
 }
 
@@ -459,32 +401,6 @@ __device__ __forceinline__ void encoder_block8x(F16Pair (&xs)[4], f32x4 (&xo)[2]
     stamp8<PROF>(pf);  // 4: combine 2
 }
 
-// debugging taps: one feature tile of the [16 x 128] residual stream
-__device__ __forceinline__ void store_tap_tile(float* tap, int slot, int t, const f32x4& v, int g, int r) {
-    st4(tap + ((size_t)slot * 16 + r) * kD + 16 * t + 4 * g, v);
-}
-
-// per-lane constants of the tile (row-lane layout: lane (g, r) holds row r); re-derived where needed (k_sampler8.hip)
-struct Lane8 {
-    int lane, g, r, cl, tok;
-    long clip;
-    bool valid, is_lat;
-};
-__device__ __forceinline__ Lane8 lane_info(const SampleKernelArgs& a, int lane) {
-    asm volatile("" : "+v"(lane));
-    Lane8 L;
-    L.lane = lane;
-    L.g = lane >> 4;
-    L.r = lane & 15;
-    const int S = a.S, R = S * a.G;
-    L.cl = L.r / S;
-    L.tok = L.r - L.cl * S;
-    L.clip = (long)blockIdx.x * a.G + L.cl;
-    L.valid = (L.r < R) && (L.clip < (long)a.B);
-    L.is_lat = L.valid && L.tok == 0;
-    return L;
-}
-
 // The whole T-step loop of one role.  Both roles execute the same sequence of workgroup barriers.
 template <bool ROLEA, bool PROF>
 __device__ __forceinline__ void role_loop8x(const SampleKernelArgs& a, char* smem, int w8, const Lane8& L0) {
@@ -497,14 +413,9 @@ __device__ __forceinline__ void role_loop8x(const SampleKernelArgs& a, char* sme
     const float* pv_final = pv_skip + 4 * kD;
     const int lane = L0.lane, g = L0.g, r = L0.r, h = w8 & 3;
     const int S = a.S, R = S * a.G;
-    // attention key mask for this lane's query row: keys j = 4 g + m of the SAME clip; padding rows attend to
-    // themselves only (keeps them finite, they never touch valid rows)
-    bool kvalid[4];
+    bool kvalid[4];   // attention key mask of this lane's query row
 #pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        const int j = 4 * g + m;
-        kvalid[m] = L0.valid ? (j < R && (j / S) == L0.cl) : (j == r);
-    }
+    for (int m = 0; m < 4; ++m) kvalid[m] = key_valid8(L0, 4 * g + m, S, R);
     const bool tap = !ROLEA && a.tap_out != nullptr && blockIdx.x == 0;  // the B waves tap their own fp32 tiles
     const uint32_t wbase_units = ROLEA ? (uint32_t)w8 * (a.wave_units_a + kR8)
                                        : 4u * (a.wave_units_a + kR8) + (uint32_t)(w8 - 4) * a.wave_units_b;
@@ -525,13 +436,7 @@ __device__ __forceinline__ void role_loop8x(const SampleKernelArgs& a, char* sme
         f32x4 xo[2] = {splat4(0.f), splat4(0.f)};
         {
             const Lane8 L = lane_info(a, lane);
-            auto assemble = [&](int t) -> f32x4 {
-                const f32x4 sv = tokrows[t * 64 + lane];
-                // unconditional loads (a divergent branch around them costs registers)
-                f32x4 tt = ld4(ttl + (step & 1) * kD + 16 * t + 4 * g);
-                if (a.time_tok_clip) tt = ld4(a.time_tok_clip + (size_t)(L.valid ? L.clip : 0) * kD + 16 * t + 4 * g);
-                return !L.valid ? splat4(0.f) : (L.tok == 0 ? latl[t * 64 + lane] + sv : (L.tok == 1 ? tt : sv));
-            };
+            auto assemble = [&](int t) { return assemble_tile(a, L, lane, g, tokrows, ttl, latl, step, t); };
 #pragma unroll
             for (int c = 0; c < 4; ++c) xs[c] = split_f16(assemble(2 * c), assemble(2 * c + 1));
             if constexpr (!ROLEA) {
@@ -595,63 +500,35 @@ __device__ __forceinline__ void role_loop8x(const SampleKernelArgs& a, char* sme
         // ---- final LayerNorm (SkipTransformerEncoder.norm) + scheduler.step (diffusers 0.17.1 DDIM / DDPM;
         // amuse_hip.h amuse_schedule) on the B waves' own tiles; the latent lives in LDS
         if constexpr (!ROLEA) {
-            float sm = ((xo[0][0] + xo[0][1]) + (xo[0][2] + xo[0][3])) + ((xo[1][0] + xo[1][1]) + (xo[1][2] + xo[1][3]));
-            sm = allreduce_g_sum(sm);
-            const float mw = sm * (1.0f / 32.0f);
-            float m2 = 0.f;
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int m = 0; m < 4; ++m) {
-                    const float d = xo[i][m] - mw;
-                    m2 += d * d;
-                }
-            m2 = allreduce_g_sum(m2);
-            if (g == 0) stats[h * 16 + r] = float2{mw, m2};
+            const float2 st = row_stats32(xo);
+            if (g == 0) stats[h * 16 + r] = st;
         }
         __syncthreads();
         if constexpr (!ROLEA) {
             const Lane8 L = lane_info(a, lane);
-            const float2 s0 = stats[L.r], s1 = stats[16 + L.r], s2 = stats[32 + L.r], s3 = stats[48 + L.r];
-            const float mean = ((s0.x + s1.x) + (s2.x + s3.x)) * 0.25f;
-            const float d0 = s0.x - mean, d1 = s1.x - mean, d2 = s2.x - mean, d3 = s3.x - mean;
-            const float M2 = ((s0.y + s1.y) + (s2.y + s3.y)) + 32.0f * ((d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3));
-            const float rstd = 1.0f / sqrtf(M2 * (1.0f / kD) + 1e-5f);
+            const float2 ms = row_stats_merge<false>(stats, L.r);
             const float* cf = a.coef + (size_t)step * 8;
             const float sb = cf[0], sa = cf[1], c0 = cf[2], cx = cf[3], ce = cf[4], sg = cf[5], clipv = cf[6];
+            const float inv_sa = 1.0f / sa;
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
                 const int t = 2 * h + i, f = 16 * t + 4 * L.g;
                 const f32x4 ga = ld4(pv_final + f), be = ld4(pv_final + kD + f);
                 f32x4 e;
 #pragma unroll
-                for (int m = 0; m < 4; ++m) e[m] = (xo[i][m] - mean) * rstd * ga[m] + be[m];
+                for (int m = 0; m < 4; ++m) e[m] = (xo[i][m] - ms.x) * ms.y * ga[m] + be[m];
                 if (tap && step == 0) store_tap_tile(a.tap_out, 10, t, e, L.g, L.r);
                 if (a.eps_out && L.is_lat && step == a.T - 1) st4(a.eps_out + (size_t)L.clip * kD + f, e);
                 if (!a.no_update) {
                     // ancestral noise of the latent rows: counter (global clip, step, feature group) - the values
-                    // amuse_counter_normal exposes
+                    // amuse_counter_normal exposes.  (Fetched here: as a shared function it changes the register allocation of the kernels without stamps.)
                     f32x4 z = splat4(0.f);
                     if (sg != 0.f && L.is_lat)
                         z = a.step_noise ? ld4(a.step_noise + ((size_t)step * a.B + L.clip) * kD + f)
                                          : counter_normal4(a.seed, a.clip0 + (uint64_t)L.clip, (uint32_t)step, (uint32_t)(4 * t + L.g), 1u);
                     f32x4 l = latl[t * 64 + L.lane];
-                    {
-// each product and sum rounded on its own, like the scheduler's tensor ops (see k_sampler.hip)
-#pragma clang fp contract(off)
 #pragma unroll
-                    for (int m = 0; m < 4; ++m) {
-                        const float xl = l[m];
-                        const float num = __fsub_rn(xl, __fmul_rn(sb, e[m]));
-                        float x0 = __fdiv_rn(num, sa);
-                        if (clipv > 0.f) x0 = fminf(fmaxf(x0, -clipv), clipv);
-                        float nx = __fmul_rn(c0, x0);
-                        if (cx != 0.f) nx = __fadd_rn(nx, __fmul_rn(cx, xl));
-                        if (ce != 0.f) nx = __fadd_rn(nx, __fmul_rn(ce, e[m]));
-                        if (sg != 0.f) nx = __fadd_rn(nx, __fmul_rn(sg, z[m]));
-                        l[m] = nx;
-                    }
-                    }
+                    for (int m = 0; m < 4; ++m) l[m] = sched_update<false>(l[m], e[m], z[m], sb, sa, c0, cx, ce, sg, clipv, inv_sa);
                     latl[t * 64 + L.lane] = l;
                     if (a.traj_out && L.is_lat) st4(a.traj_out + ((size_t)step * a.B + L.clip) * kD + f, l);
                 }
@@ -673,22 +550,13 @@ __global__ __launch_bounds__(512) void k_sample8x(SampleKernelArgs a) {
     for (int i = threadIdx.x; i < (4 * kD + 2 * kD) / 4; i += 512)
         st4(reinterpret_cast<float*>(smem + kPvTail8Off) + 4 * i, ld4(a.pvec + PV_SKIP_B + 4 * i));
     const int w8 = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int S = a.S;
     const Lane8 L = lane_info(a, threadIdx.x & 63);
-    // static token rows (pe[0] under the latent rows, condition tokens; denoiser.py:174,180-181) and the initial
-    // latent -> LDS
+    // static token rows and the initial latent -> LDS (wave 0 owns the latent's update); the first step's time token
     if (w8 == 0) {
 #pragma unroll
         for (int t = 0; t < kTiles; ++t) {
             const int f = 16 * t + 4 * L.g;
-            f32x4 sv = splat4(0.f), l0 = splat4(0.f);
-            if (L.valid) {
-                if (L.tok == 0) sv = ld4(a.pe0 + f);
-                else if (L.tok >= 2) sv = ld4(a.cond_tok + ((size_t)L.clip * (S - 2) + (L.tok - 2)) * kD + f);
-            }
-            if (L.is_lat)
-                l0 = a.x_init ? ld4(a.x_init + (size_t)L.clip * kD + f)
-                              : counter_normal4(a.seed, a.clip0 + (uint64_t)L.clip, 0u, (uint32_t)(4 * t + L.g), 0u);
+            const f32x4 sv = static_row4(a, L, f), l0 = init_latent4(a, L, t, f);
             tokrows[t * 64 + L.lane] = sv;
             latl[t * 64 + L.lane] = l0;
         }

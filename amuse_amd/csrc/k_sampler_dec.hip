@@ -193,23 +193,11 @@ __global__ __launch_bounds__(256, 1) void k_sample_dec(SampleDecArgs a) {
             }
             constexpr bool FASTU = is_op16(PREC);  // 16-bit modes: reciprocal multiply instead of IEEE division
             const float inv_sa = 1.0f / sa;
-            {
-#pragma clang fp contract(off)
 #pragma unroll
-                for (int t = 0; t < kTiles; ++t) {
+            for (int t = 0; t < kTiles; ++t) {
 #pragma unroll
-                    for (int m = 0; m < 4; ++m) {
-                        const float e = x[t][m], xl = lat[t][m];
-                        const float num = __fsub_rn(xl, __fmul_rn(sb, e));
-                        float x0 = FASTU ? num * inv_sa : __fdiv_rn(num, sa);
-                        if (clipv > 0.f) x0 = fminf(fmaxf(x0, -clipv), clipv);
-                        float nx = __fmul_rn(c0, x0);
-                        if (cx != 0.f) nx = __fadd_rn(nx, __fmul_rn(cx, xl));
-                        if (ce != 0.f) nx = __fadd_rn(nx, __fmul_rn(ce, e));
-                        if (sg != 0.f) nx = __fadd_rn(nx, __fmul_rn(sg, zt[t][m]));
-                        lat[t][m] = nx;
-                    }
-                }
+                for (int m = 0; m < 4; ++m)
+                    lat[t][m] = sched_update<FASTU>(lat[t][m], x[t][m], zt[t][m], sb, sa, c0, cx, ce, sg, clipv, inv_sa);
             }
             if (a.traj_out && valid && wave == 0) {
 #pragma unroll

@@ -374,19 +374,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 const size_t idx = ((size_t)b * kFrames + fr) * kFeats + c;
                 if (a.feats_out) a.feats_out[idx] = e;
                 if (a.x_out) {
-#pragma clang fp contract(off)
-                    const float xl = a.enc_feats[idx];
-                    const float num = __fsub_rn(xl, __fmul_rn(sb, e));
-                    float x0 = FASTU ? num * inv_sa : __fdiv_rn(num, sa);
-                    if (clipv > 0.f) x0 = fminf(fmaxf(x0, -clipv), clipv);
-                    float nx = __fmul_rn(c0, x0);
-                    if (cx != 0.f) nx = __fadd_rn(nx, __fmul_rn(cx, xl));
-                    if (ce != 0.f) nx = __fadd_rn(nx, __fmul_rn(ce, e));
+                    float nx = sched_update<FASTU>(a.enc_feats[idx], e, 0.f, sb, sa, c0, cx, ce, 0.f, clipv, inv_sa);
                     if (sg != 0.f) {
                         const size_t el = (size_t)fr * kFeats + c;   // element of the clip's state: draw el % 4 of counter el / 4
-                        const float z = a.step_noise ? a.step_noise[idx]
-                                                     : counter_normal4(a.seed, a.clip0 + (uint64_t)b, (uint32_t)a.step, (uint32_t)(el >> 2), 1u)[el & 3];
-                        nx = __fadd_rn(nx, __fmul_rn(sg, z));
+                        nx = sched_noise(nx, sg, a.step_noise ? a.step_noise[idx] : counter_normal4(a.seed, a.clip0 + (uint64_t)b, (uint32_t)a.step, (uint32_t)(el >> 2), 1u)[el & 3]);
                     }
                     a.x_out[idx] = nx;
                 }

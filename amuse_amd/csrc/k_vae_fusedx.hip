@@ -12,7 +12,7 @@
 //     two tiles in LDS (the K / V image region is free in those phases: 4 waves x 2 tiles x 8 KiB) and read them back as fragments; the third tile's stays in registers;
 //   * the U-Net skip stack is the staged path's fp32 array, written and read back by the same lanes.
 // LDS: K_h / V_h^T hi and lo fragment images 80 KiB | weight ring 3 x 16 KiB | block parameters 2 x 8 KiB | cross-attention constants 5 KiB = 149 KiB.
-// The weight stream is in unit PAIRS (hi | lo, 2 KiB): a 16 KiB LDS stage = 8 pairs; the stage protocol is k_vae_fused.hip's (amuse_fused.hpp Stager).
+// The weight stream is in unit PAIRS (hi | lo, 2 KiB): a 16 KiB LDS stage = 8 pairs; the stage protocol is k_vae_fused.hip's (amuse_stage.hpp).
 #define AMUSE_OP_F16
 #include "amuse_fused.hpp"
 
@@ -30,46 +30,10 @@ static_assert(kXLdsBytes <= 160 * 1024, "LDS");
 // (1.65 ms per 256-clip decode); without any erf the decode takes 1.54 instead of 1.76 ms (no hoist): 0.22 ms of exposed VALU time (profiles/r05_fusedx_decode.txt).
 constexpr int kParkTile = 8192;                          // one parked operand image: [4 k-pairs][hi | lo][64 lanes x 16 B]
 
-// one product of split operands, weights as the A operand: acc += Wl.xh + Wh.xl + Wh.xh (the term order of k_vae_rows8x)
-__device__ __forceinline__ f32x4 mfma3(f16x8 wh, f16x8 wl, const F16Pair& x, f32x4 acc) {
-    acc = mfma_f16(wl, x.hi, acc);
-    acc = mfma_f16(wh, x.lo, acc);
-    return mfma_f16(wh, x.hi, acc);
-}
-// the same product with the operands swapped: the accumulator holds the TRANSPOSED tile (rows along the registers) - V^T for the PV product
-__device__ __forceinline__ f32x4 mfma3t(f16x8 wh, f16x8 wl, const F16Pair& x, f32x4 acc) {
-    acc = mfma_f16(x.hi, wl, acc);
-    acc = mfma_f16(x.lo, wh, acc);
-    return mfma_f16(x.hi, wh, acc);
-}
-// the 8 unit pairs of the current LDS stage: f(i, hi, lo); pair i + 1 is read before pair i's MFMAs
-// Who copies the weight stream: two pieces of every 16-piece stage per wave, as in the 16-bit kernels.  (Leaving the copies to the four TWO-tile waves - the three-tile waves
-// are the critical path of every stage - is bitwise the same and flat: 1.67 ms per 256-clip decode either way, profiles/r05_fusedx_decode.txt.)
+// Who copies the weight stream: two pieces of every 16-piece stage per wave, as in the 16-bit kernels (amuse_stage.hpp, Stager = StageRing<2>).  (Leaving the copies to the
+// four TWO-tile waves - the three-tile waves are the critical path of every stage - is bitwise the same and flat: 1.67 ms per 256-clip decode either way,
+// profiles/r05_fusedx_decode.txt.)  The split products are mfma3 / mfma3t (amuse_dev.hpp; mfma3t: V^T for the PV product).
 constexpr int kP = 2;   // pieces per stage and wave
-template <int NT>
-__device__ __forceinline__ void stage_fetch_x(Stager& s) {
-    const unsigned d = __builtin_amdgcn_readfirstlane(s.dst0 + s.widx * kStageBytes);
-#pragma unroll
-    for (int i = 0; i < kP; ++i) glds16(s.src + i * 64, d + i * 1024);
-    s.src += kStage * 64;
-    s.widx = s.widx == kWBufs - 1 ? 0 : s.widx + 1;
-}
-template <int NT>
-__device__ __forceinline__ void stage_end_x(Stager& s) {
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(kP) : "memory");
-    s.ridx = s.ridx == kWBufs - 1 ? 0 : s.ridx + 1;
-}
-template <int NT, bool FETCH = true, class F>
-__device__ __forceinline__ void for_pairs(Stager& s, F&& f) {
-    if constexpr (FETCH) stage_fetch_x<NT>(s);
-    f16x8 h = wfrag(s, 0), l = wfrag(s, 1);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const f16x8 ch = h, cl = l;
-        if (i + 1 < 8) { h = wfrag(s, 2 * i + 2); l = wfrag(s, 2 * i + 3); }
-        f(i, ch, cl);
-    }
-}
 
 // operand images of a wave's NT tiles for a phase that accumulates into the residual registers: tiles [0, PARK) in LDS, the rest in registers
 template <int NT>
@@ -226,11 +190,11 @@ __device__ __forceinline__ void attn_half_x(f32x4 (&x)[NT][kTiles], Stager& sg, 
             F16Pair xc[NT];
 #pragma unroll
             for (int j = 0; j < NT; ++j) xc[j] = im.get(j, c);
-            for_pairs<NT>(sg, [&](int o, f16x8 wh, f16x8 wl) {
+            for_pairs<true, false>(sg, [&](int o, f16x8 wh, f16x8 wl) {
 #pragma unroll
                 for (int j = 0; j < NT; ++j) x[j][o] = mfma3(wh, wl, xc[j], x[j][o]);
             });
-            stage_end_x<NT>(sg);
+            stage_end(sg);
         }
         const float* sk = a.skip + (size_t)(8 - blk) * nrows * kD;
 #pragma unroll 1
@@ -243,11 +207,11 @@ __device__ __forceinline__ void attn_half_x(f32x4 (&x)[NT][kTiles], Stager& sg, 
                 const bool ok = frame < S;
                 xc[j] = split_f16(ok ? ld4(src) : splat4(0.f), ok ? ld4(src + 16) : splat4(0.f));
             }
-            for_pairs<NT>(sg, [&](int o, f16x8 wh, f16x8 wl) {
+            for_pairs<true, false>(sg, [&](int o, f16x8 wh, f16x8 wl) {
 #pragma unroll
                 for (int j = 0; j < NT; ++j) x[j][o] = mfma3(wh, wl, xc[j], x[j][o]);
             });
-            stage_end_x<NT>(sg);
+            stage_end(sg);
         }
     }
     FSTAMP(2);   // skip linear done
@@ -273,7 +237,7 @@ __device__ __forceinline__ void attn_half_x(f32x4 (&x)[NT][kTiles], Stager& sg, 
 #pragma unroll
                 for (int s2 = 0; s2 < 2; ++s2) {
                     F16Pair xc[NT];
-                    for_pairs<NT>(sg, [&](int i, f16x8 wh, f16x8 wl) {   // per k-pair c: k tiles (2), v tiles (2)
+                    for_pairs<true, false>(sg, [&](int i, f16x8 wh, f16x8 wl) {   // per k-pair c: k tiles (2), v tiles (2)
                         const int c = 2 * s2 + (i >> 2), t = i & 3;
                         if (t == 0) {
 #pragma unroll
@@ -285,7 +249,7 @@ __device__ __forceinline__ void attn_half_x(f32x4 (&x)[NT][kTiles], Stager& sg, 
                             else vv[j][t - 2] = mfma3t(wh, wl, xc[j], vv[j][t - 2]);
                         }
                     });
-                    if (s2 == 0) stage_end_x<NT>(sg);
+                    if (s2 == 0) stage_end(sg);
                 }
                 FSTAMP(3);   // k, v computed
 #pragma unroll
@@ -309,7 +273,7 @@ __device__ __forceinline__ void attn_half_x(f32x4 (&x)[NT][kTiles], Stager& sg, 
                     }
                 }
                 FSTAMP(4);   // images written
-                stage_end_x<NT>(sg);
+                stage_end(sg);
                 FSTAMP(5);   // barrier of stage A passed
             }
             // ---- stage B (one LDS stage): q of this head; attention, a tile at a time; the output to the scratch
@@ -324,7 +288,7 @@ __device__ __forceinline__ void attn_half_x(f32x4 (&x)[NT][kTiles], Stager& sg, 
 #pragma unroll
                 for (int j = 0; j < NT; ++j) { q[j][0] = bq0; q[j][1] = bq1; }
                 F16Pair xc[NT];
-                for_pairs<NT>(sg, [&](int i, f16x8 wh, f16x8 wl) {
+                for_pairs<true, false>(sg, [&](int i, f16x8 wh, f16x8 wl) {
                     const int c = i >> 1, o = i & 1;
                     if (o == 0) {
 #pragma unroll
@@ -353,7 +317,7 @@ __device__ __forceinline__ void attn_half_x(f32x4 (&x)[NT][kTiles], Stager& sg, 
                 qs[NT - 1] = first;
             }
             FSTAMP(7);   // attention of the wave's tiles, outputs stored
-            stage_end_x<NT>(sg);
+            stage_end(sg);
             FSTAMP(8);   // barrier of stage B passed
         }
     }
@@ -405,7 +369,7 @@ __device__ __forceinline__ void row_half_x(f32x4 (&x)[NT][kTiles], Stager& sg, c
         fetch_o(0);
 #pragma unroll 1
         for (int c = 0; c < 4; ++c) {
-            stage_fetch_x<NT>(sg);
+            stage_fetch(sg);
             if (c + 1 < 4) {
                 fetch_o(c + 1);
                 asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kP + 2 * NT) : "memory");   // this k-pair's outputs are in (and every older weight stage)
@@ -418,7 +382,7 @@ __device__ __forceinline__ void row_half_x(f32x4 (&x)[NT][kTiles], Stager& sg, c
                 const char* src = obuf_l + (c & 1) * (NT * 2048) + (2 * j) * 1024;
                 xc[j] = split_f16(*reinterpret_cast<const f32x4*>(src), *reinterpret_cast<const f32x4*>(src + 1024));
             }
-            for_pairs<NT, false>(sg, [&](int o, f16x8 wh, f16x8 wl) {
+            for_pairs<false, false>(sg, [&](int o, f16x8 wh, f16x8 wl) {
 #pragma unroll
                 for (int j = 0; j < NT; ++j) x[j][o] = mfma3(wh, wl, xc[j], x[j][o]);
             });
@@ -426,7 +390,7 @@ __device__ __forceinline__ void row_half_x(f32x4 (&x)[NT][kTiles], Stager& sg, c
                 asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(kP + 2 * NT) : "memory");
                 sg.ridx = sg.ridx == kWBufs - 1 ? 0 : sg.ridx + 1;
             } else {
-                stage_end_x<NT>(sg);
+                stage_end(sg);
             }
             FSTAMP(9);   // an out_proj stage
         }
@@ -469,7 +433,7 @@ __device__ __forceinline__ void row_half_x(f32x4 (&x)[NT][kTiles], Stager& sg, c
 #pragma unroll
         for (int j = 0; j < NT; ++j) { acc[j][0] = b0; acc[j][1] = b1; }
         F16Pair xc[NT];
-        for_pairs<NT>(sg, [&](int i, f16x8 wh, f16x8 wl) {
+        for_pairs<true, false>(sg, [&](int i, f16x8 wh, f16x8 wl) {
             const int c = i >> 1, o = i & 1;
             if (o == 0) {
 #pragma unroll
@@ -492,7 +456,7 @@ __device__ __forceinline__ void row_half_x(f32x4 (&x)[NT][kTiles], Stager& sg, c
         }
     };
     lin1(hid, 0);
-    stage_end_x<NT>(sg);
+    stage_end(sg);
 #pragma unroll 1
     for (int ch = 0; ch < 16; ++ch) {
         F16Pair hs[NT];
@@ -509,21 +473,21 @@ __device__ __forceinline__ void row_half_x(f32x4 (&x)[NT][kTiles], Stager& sg, c
                 lin1(nxt, ch + 1);
             }
             FSTAMP(12);   // linear1 of the next chunk + GELU of this one
-            stage_end_x<NT>(sg);
+            stage_end(sg);
             FSTAMP(13);
 #pragma unroll
             for (int j = 0; j < NT; ++j) { hid[j][0] = nxt[j][0]; hid[j][1] = nxt[j][1]; }
         } else {
             gelu_split(hs);
         }
-        for_pairs<NT>(sg, [&](int o, f16x8 wh, f16x8 wl) {
+        for_pairs<true, false>(sg, [&](int o, f16x8 wh, f16x8 wl) {
 #pragma unroll
             for (int j = 0; j < NT; ++j) {
                 x[j][o] = mfma3(wh, wl, hs[j], x[j][o]);
             }
         });
         FSTAMP(14);   // linear2 of the chunk
-        stage_end_x<NT>(sg);
+        stage_end(sg);
         FSTAMP(15);
     }
 #pragma unroll 1
@@ -605,12 +569,12 @@ __device__ __forceinline__ void decode_tiles_x(const VaeFusedXArgs& a, char* sme
         }
 #pragma unroll
         for (int s3 = 0; s3 < 3; ++s3) {
-            for_pairs<NT>(sg, [&](int i, f16x8 wh, f16x8 wl) {
+            for_pairs<true, false>(sg, [&](int i, f16x8 wh, f16x8 wl) {
                 const int lin = 8 * s3 + i, c = lin / 6, o = lin - 6 * c;
 #pragma unroll
                 for (int j = 0; j < NT; ++j) f[j][o] = mfma3(wh, wl, xs[j][c], f[j][o]);
             });
-            stage_end_x<NT>(sg);
+            stage_end(sg);
         }
         const int f0 = 96 * quarter, nfe = quarter == 3 ? kFeats - 288 : 96, njo = quarter == 3 ? kJoints - 48 : 16;
 #pragma unroll 1
@@ -675,8 +639,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     sg.ring = smem + kXOffW + lane * 16;
     sg.widx = 0;
     sg.ridx = 0;
-    if (wave < 4) { stage_fetch_x<3>(sg); stage_fetch_x<3>(sg); }
-    else { stage_fetch_x<2>(sg); stage_fetch_x<2>(sg); }
+    if (wave < 4) { stage_fetch(sg); stage_fetch(sg); }
+    else { stage_fetch(sg); stage_fetch(sg); }
     if (wave < 4) decode_tiles_x<3>(a, smem, sg, wave, b, len, wave, lane);
     else decode_tiles_x<2>(a, smem, sg, wave + 8, b, len, wave, lane);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the two surplus fetches must not outlive the workgroup's LDS
@@ -731,11 +695,11 @@ __device__ __forceinline__ void den_tiles_x(const DenFusedXArgs& a, char* smem, 
 #pragma unroll
         for (int j = 0; j < NT; ++j) xc[j] = split_f16(cur[j][0], cur[j][1]);
         if (c + 1 < 11) load_xt_pair<NT>(cur, xin, tile0, r, g, npre, c + 1);
-        for_pairs<NT>(sg, [&](int o, f16x8 wh, f16x8 wl) {
+        for_pairs<true, false>(sg, [&](int o, f16x8 wh, f16x8 wl) {
 #pragma unroll
             for (int j = 0; j < NT; ++j) x[j][o] = mfma3(wh, wl, xc[j], x[j][o]);
         });
-        stage_end_x<NT>(sg);
+        stage_end(sg);
     }
     // xseq = cat(emb_latent, pose_embd(sample)) + query_pos (denoiser.py:180-181); the tokens arrive with their positions added
 #pragma unroll
@@ -813,12 +777,12 @@ __device__ __forceinline__ void den_tiles_x(const DenFusedXArgs& a, char* smem, 
         }
 #pragma unroll
         for (int s3 = 0; s3 < 3; ++s3) {
-            for_pairs<NT>(sg, [&](int i, f16x8 wh, f16x8 wl) {
+            for_pairs<true, false>(sg, [&](int i, f16x8 wh, f16x8 wl) {
                 const int lin = 8 * s3 + i, c = lin / 6, o = lin - 6 * c;
 #pragma unroll
                 for (int j = 0; j < NT; ++j) f[j][o] = mfma3(wh, wl, xs[j][c], f[j][o]);
             });
-            stage_end_x<NT>(sg);
+            stage_end(sg);
         }
         const int f0 = 96 * quarter, nfe = quarter == 3 ? kFeats - 288 : 96;
 #pragma unroll 1
@@ -837,18 +801,8 @@ __device__ __forceinline__ void den_tiles_x(const DenFusedXArgs& a, char* smem, 
                 const size_t el = (size_t)fr * kFeats + f0 + c;
                 if (eo) eo[el] = e;
                 if (xo) {
-#pragma clang fp contract(off)
-                    const float xl = xin[el];
-                    const float num = __fsub_rn(xl, __fmul_rn(sb, e));
-                    float x0 = __fdiv_rn(num, sa);
-                    if (clipv > 0.f) x0 = fminf(fmaxf(x0, -clipv), clipv);
-                    float nx = __fmul_rn(c0, x0);
-                    if (cxx != 0.f) nx = __fadd_rn(nx, __fmul_rn(cxx, xl));
-                    if (ce != 0.f) nx = __fadd_rn(nx, __fmul_rn(ce, e));
-                    if (sgm != 0.f) {
-                        const float z = nz ? nz[el] : counter_normal4(a.seed, a.clip0 + (uint64_t)b, (uint32_t)a.step, (uint32_t)(el >> 2), 1u)[el & 3];
-                        nx = __fadd_rn(nx, __fmul_rn(sgm, z));
-                    }
+                    float nx = sched_update<false>(xin[el], e, 0.f, sb, sa, c0, cxx, ce, 0.f, clipv, 0.f);
+                    if (sgm != 0.f) nx = sched_noise(nx, sgm, nz ? nz[el] : counter_normal4(a.seed, a.clip0 + (uint64_t)b, (uint32_t)a.step, (uint32_t)(el >> 2), 1u)[el & 3]);
                     xo[el] = nx;
                 }
             }
@@ -879,8 +833,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     sg.ring = smem + kXOffW + lane * 16;
     sg.widx = 0;
     sg.ridx = 0;
-    if (wave < 4) { stage_fetch_x<3>(sg); stage_fetch_x<3>(sg); }
-    else { stage_fetch_x<2>(sg); stage_fetch_x<2>(sg); }
+    if (wave < 4) { stage_fetch(sg); stage_fetch(sg); }
+    else { stage_fetch(sg); stage_fetch(sg); }
     if (wave < 4) den_tiles_x<3, ENCM>(a, smem, sg, wave, b, wave, lane);
     else den_tiles_x<2, ENCM>(a, smem, sg, wave + 8, b, wave, lane);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the two surplus fetches must not outlive the workgroup's LDS

@@ -15,8 +15,7 @@
 //     attention kernels between the stages stay as they are.
 // Every LDS stage is either one k-pair x 8 output tiles or (linear1) 4 k-pairs x 2 output tiles; the last stage's 24 output tiles go in
 // four quarters of 6 (one staging tile of 16 x 96 features per wave, as in k_vae_fused.hip).
-#include "amuse_dev.hpp"
-#include "amuse_kernels.hpp"
+#include "amuse_stage.hpp"
 
 namespace amuse {
 namespace {
@@ -32,10 +31,6 @@ constexpr int kRowTiles = 19;                 // ceil(300 / 16)
 constexpr int kTilesPerWave = 1;              // row tiles per wave: a weight fragment read from LDS feeds 3 x NT MFMAs
 // the waves that copy the stream (16 units per LDS stage): eight with two pieces each, four with four in the small workgroups
 constexpr int dma_waves(int waves) { return waves >= 8 ? 8 : 4; }
-constexpr int kStage = 16;                    // units per LDS stage (8 hi | lo pairs)
-constexpr int kStageBytes = kStage * 1024;
-// LDS stages in the weight ring (the copying wave keeps kWBufs - 1 stages ahead of the stage being read, kWBufs - 2 of them may still be in flight at a stage's end)
-constexpr int kWBufs = 3;                     // (deeper rings measured flat: profiles/r04_rows8x_ring_depth_ab.txt)
 static_assert(kWBufs == 3 || (kProd && kWBufs <= 5), "deeper rings: copying-wave protocol only; vmcnt is a 6-bit counter");
 constexpr int kQStride = 100;                 // staging row stride (floats) of one 96-feature quarter of the last stage
 constexpr int kOffW = 0;
@@ -43,67 +38,10 @@ constexpr int kOffBias = kWBufs * kStageBytes;          // [384] floats: in_proj
 constexpr int kOffStage = kOffBias + 384 * 4;
 constexpr int rows8_lds_bytes(int waves, bool last_stage) { return kOffStage + (last_stage ? waves * 16 * kQStride * 4 : 0); }   // (the staging tiles serve the final stage only)
 
-__device__ __forceinline__ void glds16(const uint4* gsrc, unsigned lds_dst) {   // (k_vae_fused.hip: LDS-DMA outside hipcc's waitcnt bookkeeping)
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(gsrc), "s"(lds_dst)
-                 : "memory");
-}
-template <int P>   // P = pieces (1 KiB units) a copying wave moves per stage
-struct Stager {
-    const uint4* src;   // this lane's source address of the wave's pieces of the NEXT stage to fetch
-    unsigned dst0;      // LDS byte address of the wave's pieces inside buffer 0
-    const char* ring;   // weight ring base (generic pointer) + lane * 16
-    int widx, ridx;     // buffer the next fetch fills / buffer the current stage reads
-    bool dma;           // this wave copies (waves 0..7)
-};
-template <int P>
-__device__ __forceinline__ void stage_fetch(Stager<P>& s) {
-    if constexpr (P == 0) return;
-    if (s.dma) {   // (wave-uniform; the other waves' vmcnt(P) at the stage's end is trivially true - the barrier is what they need)
-        const unsigned d = __builtin_amdgcn_readfirstlane(s.dst0 + s.widx * kStageBytes);
-#pragma unroll
-        for (int i = 0; i < P; ++i) glds16(s.src + i * 64, d + i * 1024);
-    }
-    s.src += kStage * 64;
-    s.widx = s.widx == kWBufs - 1 ? 0 : s.widx + 1;
-}
-template <int P>
-__device__ __forceinline__ void stage_end(Stager<P>& s) {
-    if constexpr (P == 0) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // (row wave beside a copying wave: no vmcnt)
-    else if constexpr (P == 2) asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    else if constexpr (P == 4) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(16)\n\ts_barrier" ::: "memory");
-    s.ridx = s.ridx == kWBufs - 1 ? 0 : s.ridx + 1;
-}
-template <int P>
-__device__ __forceinline__ f16x8 wfrag(const Stager<P>& s, int u) {
-    return __builtin_bit_cast(f16x8, *reinterpret_cast<const uint4*>(s.ring + s.ridx * kStageBytes + u * 1024));
-}
-// one product of split operands: acc += Wl.xh + Wh.xl + Wh.xh (the term order of gemm_ring_s, amuse_dev.hpp)
-__device__ __forceinline__ f32x4 mfma3(f16x8 wh, f16x8 wl, const F16Pair& x, f32x4 acc) {
-    acc = mfma_f16(wl, x.hi, acc);
-    acc = mfma_f16(wh, x.lo, acc);
-    return mfma_f16(wh, x.hi, acc);
-}
-// the 8 unit pairs of the current LDS stage, pair i -> f(i, hi, lo); the fragments of pair i + 1 are read before pair i's MFMAs
-template <int P, class F>
-__device__ __forceinline__ void for_pairs(Stager<P>& s, F&& f) {
-    stage_fetch(s);
-    f16x8 h = wfrag(s, 0), l = wfrag(s, 1);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const f16x8 ch = h, cl = l;
-        if (i + 1 < 8) { h = wfrag(s, 2 * i + 2); l = wfrag(s, 2 * i + 3); }
-        f(i, ch, cl);
-    }
-    stage_end(s);
-}
 // acc[j][o] += W[o-tile][k-pairs 0..3] . x_j over FOUR LDS stages (k-pair outer, 8 output tiles inner); a fragment pair read from LDS
 // feeds the MFMAs of all NT row tiles of the wave
-template <int NT, int P>
-__device__ __forceinline__ void gemm_k128_o8(f32x4 (&acc)[NT][8], const F16Pair (&xs)[NT][4], Stager<P>& s) {
+template <int NT, class Ring>
+__device__ __forceinline__ void gemm_k128_o8(f32x4 (&acc)[NT][8], const F16Pair (&xs)[NT][4], Ring& s) {
 #pragma unroll
     for (int c = 0; c < 4; ++c)
         for_pairs(s, [&](int o, f16x8 wh, f16x8 wl) {
@@ -151,8 +89,8 @@ __global__ __launch_bounds__(64 * (kWaves + kProdWaves)) __attribute__((amdgpu_w
         row[j] = (size_t)b[j] * S + (rvalid[j] ? frame[j] : 0);
     }
     const size_t nrows = (size_t)a.B * S;
-    const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) const void*)smem;
-    Stager<kPieces> sg;
+    const unsigned lds0 = lds_addr(smem);
+    StageRing<kPieces, SomeWaves> sg;
     sg.dma = wave < kDmaWaves;
     const bool hoisted = a.stage == 1 && a.c1 != nullptr;   // block 0's self-attention half comes as the constant c1 (VaeRowsArgs)
     sg.src = a.wstream + (size_t)a.stage_base[a.stage] * 64 + (hoisted ? 4 * kStage * 64 : 0) + (size_t)(wave % kDmaWaves) * kPieces * 64 + lane;

@@ -17,7 +17,8 @@ generator); the distribution is the same.  Attention dropout: a hash of (seed, o
 kernel, when selected, keeps its own Philox state, returned and replayed).
 
 The eager layers of nn_modules.py remain the definition (CPU, key-padding masks, AMUSE_TRAIN_FUSED=0); tests/test_gpu_train_ops.py pins this
-path to them: outputs and every gradient, eval mode exactly the same arithmetic, train mode through the masks.
+path to them: outputs and every gradient, eval mode exactly the same arithmetic; tests/test_gpu_train_layer_dropout.py pins train mode: outputs and every gradient
+against a float64 restatement of the layers that replays the kernels' masks (tests/train_layer_ref.py).
 """
 from __future__ import annotations
 

@@ -241,7 +241,7 @@ class MotionPrior(nn.Module):
         mu, logvar = out[:, 0][None], out[:, 1][None]                      # (1, B, 128) each
         std = logvar.exp().pow(0.5)
         # validate_args: torch's default (None = on) checks `std > 0` ON THE HOST - two blocking device -> host reads per construction.  The trainer
-        # switches it off (train_gesture.Trainer: the step has no other host synchronisation, and a bad std shows up in the losses it logs)
+        # switches it off (train_gesture.GestureTrainer.__init__: the step has no other host synchronisation, and a bad std shows up in the losses it logs)
         d = torch.distributions.Normal(mu, std, validate_args=self.validate_args)
         return d.rsample(), d
 

@@ -31,6 +31,7 @@ with large messages; there is nothing to overlap it with (it needs the complete 
 from __future__ import annotations
 
 import contextlib
+import json
 import os
 import time
 from pathlib import Path
@@ -38,13 +39,15 @@ from typing import Callable, Dict, Iterable, List, Optional
 
 import numpy as np
 import torch
+import torch.distributed as dist
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import scheduler as sch
-from .nn_modules import Denoiser, MotionPrior, load_numpy_state, numpy_state
+from . import _lib, inner_sampler as ins, scheduler as sch, train_ops, weights as wts
+from .inner_sampler import SEQ_LEN, HipInnerSampler, InnerSampler, TrainModeInnerSampler  # noqa: F401 - re-exported: the samplers live in inner_sampler.py
+from .nn_modules import Denoiser, MotionPrior, load_numpy_state
+from .shard import all_ranks_ok
 
-SEQ_LEN = 300
 LOSS_CFG = {"train_lpdm": {"version": "v0"}, "stage": "vae_diffusion", "LAMBDA_PRIOR": 0.0, "LAMBDA_GEN": 1.0,
             "LAMBDA_LATENT": 1.0, "LAMBDA_KL": 1e-4, "LAMBDA_REC": 1.0, "LAMBDA_JOINT": 1.0, "use_recons_joints": False,
             "predict_epsilon": True, "vtex_displacement": False}   # configs/diff_latent_v2.json "losses" + trainer.py:174-175
@@ -153,15 +156,11 @@ class LatentPriorLosses:
                     total = total + self._update_loss("gen_feature", rs_set["gen_m_rst"], rs_set["m_ref"])
             else:
                 total = total + self._update_loss("latent_feature", rs_set["lat_rm"], rs_set["lat_m"])
-            if self.body is not None:       # values only; accumulated in place on the device (a captured step replays these launches)
-                if self.vtex_grad:          # opt-in: the terms carry gradient (see __init__)
-                    rec, gen = self.body.terms(rs_set["m_ref"], rs_set["m_rst"], rs_set.get("gen_m_rst"), rs_set.get("attr"), rs_set.get("subjects"), grad=True)
-                    self.sums["rec_vtex_displacement"] += rec.detach()
-                    self.sums["gen_vtex_displacement"] += gen.detach()
-                else:
-                    rec, gen = self.body.terms(rs_set["m_ref"], rs_set["m_rst"], rs_set.get("gen_m_rst"), rs_set.get("attr"), rs_set.get("subjects"))
-                    self.sums["rec_vtex_displacement"] += rec
-                    self.sums["gen_vtex_displacement"] += gen
+            if self.body is not None:       # accumulated in place on the device (a captured step replays these launches); vtex_grad: the terms carry gradient (see __init__)
+                rec, gen = self.body.terms(rs_set["m_ref"], rs_set["m_rst"], rs_set.get("gen_m_rst"), rs_set.get("attr"), rs_set.get("subjects"),
+                                           **({"grad": True} if self.vtex_grad else {}))      # (not asked for: as the body models were built - without)
+                self.sums["rec_vtex_displacement"] += rec.detach()
+                self.sums["gen_vtex_displacement"] += gen.detach()
                 total = total + self.cfg["LAMBDA_REC"] * (rec + gen)
         self.sums["total"] += total.detach()
         self.count += 1
@@ -217,9 +216,9 @@ class GestureTrainer:
     both parameter lists (trainer.py:176-182), the iteration of :335-466 and the checkpoint writer of :468-496."""
 
     def __init__(self, prior: MotionPrior, ldm: LatentDiffusionTrainModule, device, lr: float = 1e-4, loss_cfg: Optional[dict] = None,
-                 inner_sampler: Optional[Callable] = None, process_group=None, world: int = 1, kind: Optional[str] = None,
+                 inner_sampler: Optional[InnerSampler] = None, process_group=None, world: int = 1, kind: Optional[str] = None,
                  grads_mode: str = "steal", sampler_stream: bool = True, optimizer: str = "flat", denoiser_stream: bool = True, body=None,
-                 vtex_grad: bool = False):
+                 vtex_grad: bool = False, use_graph: bool = False):
         self.model = {"prior": prior.to(device), "ldm": ldm.to(device)}
         # torch.distributions.Normal validates its arguments with blocking device -> host reads (6 per iteration: the host then waits for the previous
         # iteration's backward + optimizer step before it dispatches anything of the next, tools/probes/train_host/sync_points.py).  Off on the GPU
@@ -228,33 +227,29 @@ class GestureTrainer:
             prior.validate_args = False
         self.device = torch.device(device)
         self.lpdm_losses = LatentPriorLosses(loss_cfg, self.device, body=body, vtex_grad=vtex_grad)
-        self.inner_sampler = inner_sampler      # (con, emo, sty, bsz) -> noise2feats (B,300,333) or None
+        self.inner_sampler = inner_sampler      # an inner_sampler.InnerSampler: (con, emo, sty, bsz) -> noise2feats (B,300,333); None: no gen_feature term
         self.world, self.pg = world, process_group
         self.kind = kind                        # ablation variant of the LMDB id (trainer.py:393-399): full / emotion / identity
         # the parameter lists of trainer.py:181 (prior, then ldm), each in state-dict order - the order of the flat images the
         # HIP library takes (weights.prior_param_spec / denoiser_param_spec).  Every parameter is a view into ONE flat fp32
         # buffer laid out that way, so the in-loop sampler's re-pack reads its two networks as slices of it (no per-iteration
         # torch.cat of 427 tensors), and every p.grad is a view into a second buffer of the same layout: the gradient bucket.
-        from . import weights as wts
         pn, dn = dict(prior.named_parameters()), dict(ldm.denoiser.named_parameters())
         self.params: List[nn.Parameter] = [pn[k] for k in wts.prior_param_spec()] + [dn[k] for k in wts.denoiser_param_spec()]
         assert {id(p) for p in self.params} == {id(p) for m in (prior, ldm) for p in m.parameters()} and len(self.params) == len(pn) + len(dn)
-        n = sum(p.numel() for p in self.params)
         self.n_prior = sum(p.numel() for p in pn.values())
-        self.flat_param = torch.empty(n, device=self.device, dtype=torch.float32)
-        off = 0
-        with torch.no_grad():
-            for p in self.params:
-                v = self.flat_param[off:off + p.numel()].view_as(p)
-                v.copy_(p)
-                p.data = v
-                off += p.numel()
-        self.flat_grad = torch.zeros(n, device=self.device, dtype=torch.float32)
-        off, self.views = 0, []
+        layout, n = [], 0                                   # (parameter, offset, length) in both flat buffers
         for p in self.params:
-            self.views.append(self.flat_grad[off:off + p.numel()].view_as(p))
-            p.grad = self.views[-1]
-            off += p.numel()
+            layout.append((p, n, p.numel()))
+            n += p.numel()
+        self.flat_param = torch.empty(n, device=self.device, dtype=torch.float32)
+        self.flat_grad = torch.zeros(n, device=self.device, dtype=torch.float32)
+        self.views = [self.flat_grad[off:off + k].view_as(p) for p, off, k in layout]
+        with torch.no_grad():
+            for (p, off, k), g in zip(layout, self.views):
+                v = self.flat_param[off:off + k].view_as(p)
+                v.copy_(p)
+                p.data, p.grad = v, g
         # parameters the iteration never reaches (denoiser.mem_pos.pe: the trans_enc path uses query_pos only) get no
         # gradient in the reference (grad stays None after zero_grad(set_to_none=True)), so its AdamW never touches them -
         # not even with weight decay.  They stay in the bucket (zeros) but out of the optimizer.
@@ -263,19 +258,13 @@ class GestureTrainer:
         # `baseline` feed no style token, `identity` no emotion token): their gradients stay None in the reference
         dropped = {"emotion": ("emb_proj_sty",), "baseline": ("emb_proj_sty",), "identity": ("emb_proj_emo",)}.get(kind or "", ())
         unused |= {id(p) for n, p in ldm.denoiser.named_parameters() if n.split(".")[0] in dropped}
-        # the multi-tensor ("fused") AdamW of torch on the GPU: the same update in a handful of launches instead of ~10 per
-        # parameter group of the default foreach path (2.7 ms of device time and 4.8 ms of host time per iteration, section 4.6)
-        # ... and on the GPU that update is ONE launch per contiguous run of optimizer parameters in the flat buffers (train_ops.FlatAdamW, csrc/k_train.hip);
-        # optimizer = "fused" / "foreach" select torch's own implementations (A/B: profiles/r02_train_variants.txt)
+        # on the GPU the update is ONE launch per contiguous run of optimizer parameters in the flat buffers (train_ops.FlatAdamW, csrc/k_train.hip);
+        # optimizer = "fused" / "foreach" select torch's own implementations (A/B: profiles/r02_train_variants.txt; the multi-tensor "fused" one takes a handful of
+        # launches where foreach takes ~10 per parameter group: 2.7 ms of device time and 4.8 ms of host time per iteration, section 4.6)
         opt_kind = optimizer if self.device.type == "cuda" else "foreach"
         opt_params = [p for p in self.params if id(p) not in unused]
         if opt_kind == "flat":
-            from .train_ops import FlatAdamW
-            layout, off = [], 0
-            for p in self.params:
-                layout.append((p, off, p.numel()))
-                off += p.numel()
-            self.lpdm_opt = FlatAdamW(opt_params, self.flat_param, self.flat_grad, layout, lr=lr)
+            self.lpdm_opt = train_ops.FlatAdamW(opt_params, self.flat_param, self.flat_grad, layout, lr=lr)
         else:
             self.lpdm_opt = torch.optim.AdamW(lr=lr, params=opt_params, **({"fused": True} if opt_kind == "fused" else {}))
         # how gradients reach the bucket (grads_mode): "steal" (default) - autograd hands every parameter a fresh gradient, one multi-tensor copy packs
@@ -285,19 +274,43 @@ class GestureTrainer:
         assert grads_mode in ("steal", "sink", "views"), grads_mode
         self.grads_mode = grads_mode
         self.sampler_stream = sampler_stream       # the no-gradient half on a stream of its own beside the forward pass (False: in line; tests)
-        self.steal = self.grads_mode == "steal"
-        # (eager fallback layers only - AMUSE_TRAIN_FUSED=0 / CPU: the library's own GEMMs need no BLAS)  the step's ~500 fp32 GEMMs are small: rocBLAS's
-        # choices run them in 9 ms of device time per iteration where hipBLASLt's heuristics take 12.5, at a third of the host
-        # time per call (a process-wide torch setting)
+        # (eager fallback layers only - AMUSE_TRAIN_FUSED=0 / CPU: the library's own GEMMs need no BLAS)  the step's ~500 fp32 GEMMs are small: rocBLAS's choices run
+        # them in 9 ms of device time per iteration where hipBLASLt's heuristics take 12.5, at a third of the host time per call (a process-wide torch setting)
         if self.device.type == "cuda":
             torch.backends.cuda.preferred_blas_library("cublas")
         self._ar_events: list = []
         self._side_stream = None
         self.denoiser_stream = denoiser_stream     # the Denoiser's forward / backward chain on a stream of its own beside the prior's (False: in line; tests)
         self._den_stream = None
+        self.use_graph = use_graph                 # the epoch loop captures the iteration as two HIP graphs after three eager ones (capture_or_stay_eager)
+        self._graph, self._steps_done = None, 0    # the captured iteration {"g1", "g2", "static", "draws", "keys", "loss"}; iterations of the epoch loop
+
+    steal = property(lambda self: self.grads_mode == "steal")
 
     def n_grad_elements(self) -> int:
         return int(self.flat_grad.numel())
+
+    # ------------------------------------------------------------------ side streams: fork and join, stated once
+    def _fork(self, name: str, lane: Optional[int] = None):
+        """The trainer's stream `name` (created on first use; lane: registered as that scratch lane of the library) after it was made to wait for everything queued on
+        the current one: inside a capture, a parallel branch of the graph.  None: nothing to fork onto - a CPU run, or the pool handed out the stream this runs on."""
+        if self.device.type != "cuda":
+            return None
+        if getattr(self, name) is None:
+            setattr(self, name, torch.cuda.Stream(self.device))
+        stream, cur = getattr(self, name), torch.cuda.current_stream(self.device)
+        if stream.cuda_stream == cur.cuda_stream:
+            return None
+        if lane is not None:                          # (every iteration: the one stream of that lane in the process is this trainer's)
+            train_ops.register_lane(stream, lane)
+        stream.wait_stream(cur)
+        return stream
+
+    def _join(self, stream, *tensors):
+        cur = torch.cuda.current_stream(self.device)
+        cur.wait_stream(stream)
+        for t in tensors:                             # allocated on `stream`, read on this one from here on: the caching allocator must know
+            t.record_stream(cur)
 
     # ------------------------------------------------------------------ one iteration (trainer.py:356-456)
     def forward_losses(self, batch, noise=None, timesteps=None, eps_enc=None, eps_inf=None):
@@ -309,38 +322,21 @@ class GestureTrainer:
             sty = None
         elif self.kind == "identity":
             emo = None
-        con = con.to(self.device)
-        emo = emo.to(self.device) if emo is not None else None
-        sty = sty.to(self.device) if sty is not None else None
+        con, emo, sty = (t if t is None else t.to(self.device) for t in (con, emo, sty))
         # The no-gradient half (in-loop DDIM-50 + decode on the HIP kernels: ~1.7 ms of a latency-bound kernel on 16 of the 256 CUs) depends on the weights and the
         # conditions only: on the GPU it runs on a stream of its own beside the networks' forward pass and is joined in front of the losses.
-        gen, side = None, None
-        if self.inner_sampler is not None:
-            if self.device.type == "cuda" and self.sampler_stream and not getattr(self.inner_sampler, "serial", False):
-                if self._side_stream is None:
-                    self._side_stream = torch.cuda.Stream(self.device)
-                side = self._side_stream
-                side.wait_stream(torch.cuda.current_stream(self.device))     # the weights of the last optimizer step, the conditions
-                with torch.cuda.stream(side), torch.no_grad():
-                    if getattr(self.inner_sampler, "decode_on_trainer_stream", False):
-                        gen = self.inner_sampler.sample_latents(con, emo, sty, motion.shape[0])   # (decoded after the join: the layer kernels' scratch)
-                    else:
-                        gen = self.inner_sampler(con, emo, sty, motion.shape[0])
+        sampler, bsz = self.inner_sampler, motion.shape[0]
+        gen = side = den = None
+        if sampler is not None and self.sampler_stream and not sampler.serial:
+            side = self._fork("_side_stream")         # after: the weights of the last optimizer step, the conditions
+        if side is not None:                          # (decode_on_trainer_stream: decoded after the join - the layer kernels' scratch)
+            with torch.cuda.stream(side), torch.no_grad():
+                gen = sampler.sample_latents(con, emo, sty, bsz) if sampler.decode_on_trainer_stream else sampler(con, emo, sty, bsz)
         # The Denoiser's chain (the no-gradient encode that feeds it, its forward pass and - autograd runs a node's backward pass on its forward pass's stream - its
         # backward pass) shares nothing with the prior's encode -> decode chain but the inputs: 160-row layers, ~1.4 ms of launches that each leave most of the chip
         # idle.  On the GPU it is issued on a stream of its own (scratch lane 1 of the library, train_ops.register_lane) beside the prior's 9,600-row kernels.
-        den = None
-        if self.device.type == "cuda" and self.denoiser_stream and _train_ops_enabled():
-            from . import train_ops
-            if self._den_stream is None:
-                self._den_stream = torch.cuda.Stream(self.device)
-            den = self._den_stream
-            if den.cuda_stream == torch.cuda.current_stream(self.device).cuda_stream:
-                den = None                            # (the pool handed this trainer the stream it is running on: nothing to fork onto)
-            else:
-                train_ops.register_lane(den, 1)       # (every iteration: the one lane-1 stream of the process is this trainer's)
-        if den is not None:
-            den.wait_stream(torch.cuda.current_stream(self.device))          # motion, the conditions, the weights
+        if self.denoiser_stream and self.device.type == "cuda" and train_ops.enabled():
+            den = self._fork("_den_stream", lane=1)   # after: motion, the conditions, the weights
         motion_z, dist_m = prior.encode(motion, lengths)
         if eps_enc is not None:                       # explicit rsample draw (tests): z = mu + std * eps
             motion_z = dist_m.loc + dist_m.scale * eps_enc.to(self.device)
@@ -353,21 +349,14 @@ class GestureTrainer:
                     inferred_z = dist_i.loc + dist_i.scale * eps_inf.to(self.device)
             n_set = ldm.diffusion_forward(inferred_z, con, emo, sty, lengths=lengths, noise=noise, timesteps=timesteps)
         if den is not None:                           # join in front of the losses (the backward pass forks and joins by itself: autograd's stream semantics)
-            torch.cuda.current_stream(self.device).wait_stream(den)
-            for t in (n_set["noise_pred"], n_set["noise"]):
-                t.record_stream(torch.cuda.current_stream(self.device))
+            self._join(den, n_set["noise_pred"], n_set["noise"])
         if side is not None:                          # join: the losses read `gen`, and the optimizer step must not overtake the sampler's reads of the weights
-            torch.cuda.current_stream(self.device).wait_stream(side)
-            gen.record_stream(torch.cuda.current_stream(self.device))
-            if getattr(self.inner_sampler, "decode_on_trainer_stream", False):
-                with torch.no_grad():
-                    gen = self.inner_sampler.decode(gen)
-        elif self.inner_sampler is not None:          # inverse diffusion (no gradient): the HIP sampler + decode
-            with torch.no_grad():
-                gen = self.inner_sampler(con, emo, sty, motion.shape[0])
-        rs_set = {"m_ref": motion, "m_rst": feats_rst, "dist_m": dist_m, "dist_ref": dist_ref, "noise_pred": n_set["noise_pred"],
-                  "noise": n_set["noise"], "gen_m_rst": gen, "attr": batch.get("ld_attr"), "subjects": batch.get("ld_subjects")}
-        return self.lpdm_losses.update(rs_set)
+            self._join(side, gen)
+        if sampler is not None and (side is None or sampler.decode_on_trainer_stream):
+            with torch.no_grad():                     # in line: the whole inverse diffusion, or the decode of the side stream's latents
+                gen = sampler(con, emo, sty, bsz) if side is None else sampler.decode(gen)
+        return self.lpdm_losses.update({"m_ref": motion, "m_rst": feats_rst, "dist_m": dist_m, "dist_ref": dist_ref, "noise_pred": n_set["noise_pred"],
+                                        "noise": n_set["noise"], "gen_m_rst": gen, "attr": batch.get("ld_attr"), "subjects": batch.get("ld_subjects")})
 
     def train_step(self, batch, **explicit) -> torch.Tensor:
         for m in self.model.values():
@@ -386,34 +375,70 @@ class GestureTrainer:
         return loss.detach()
 
     # ------------------------------------------------------------------ the iteration as two HIP graphs (GPU)
-    _graph = None
-
     def enable_graph(self, batch) -> bool:
         """Capture the iteration at `batch`'s shapes as TWO HIP graphs - forward + losses + backward into the bucket (+ the side-stream sampler), and the optimizer
-        step - with the gradient all-reduce between them as an ordinary call; later train_step(batch) calls of those shapes copy the batch into the captured
+        step - with the gradient all-reduce between their replays as an ordinary call; later train_step(batch) calls of those shapes copy the batch into the captured
         buffers and replay (other shapes / explicit draws run eagerly).  What makes a replay a NEW iteration: torch's graph-safe generator for the step's draws
         (noise, timesteps, the two rsamples, the sampler's initial latents), the library's device-side dropout epoch (amuse_train_epoch_advance at the end of the
         second graph) and AdamW's device-side step count (FlatAdamW.step_dev).  Needs the gradient-sink path (the library writes gradients straight into the bucket:
         tools/probes/train_host/graph_capture_probe.py - replays bitwise the eager step) and the flat optimizer.  Call it after a few eager steps (workspaces exist).
-        Returns False - and leaves the trainer eager - where the step is not capturable (CPU, another optimizer, a train-mode inner sampler)."""
-        from . import _lib as _libmod
-        from . import train_ops
+        Returns False - and leaves the trainer eager - where the step is not capturable (CPU, another optimizer, a train-mode inner sampler); a capture that raises
+        leaves the trainer as it was before the call.  One rank's view: with more ranks, capture_or_stay_eager."""
+        before = self._capture_state()
+        try:
+            return self._capture(batch)
+        except Exception:
+            self._capture_rollback(before)
+            raise
+
+    def capture_or_stay_eager(self, batch):
+        """The whole policy of `use_graph` (the epoch loop, the benchmark): try the capture, agree on the outcome with every rank BEFORE the next collective, and replay
+        on all ranks or on none (a rank alone in staying eager runs another gradient path than its peers).  -> (captured, note); not captured: the trainer is as it was."""
+        before = self._capture_state()
+        try:
+            mine = self._capture(batch)
+            note = "captured" if mine else "not capturable in this configuration: eager"
+        except Exception as e:  # noqa: BLE001 - training goes on eagerly, and says so
+            mine, note = False, f"capture failed ({type(e).__name__}: {str(e)[:200]}): eager"
+        captured = all_ranks_ok(mine, self.device, self.pg)
+        if not captured:
+            self._capture_rollback(before)
+        return captured, "capture failed on another rank: eager" if mine and not captured else note
+
+    def _capture_state(self):
+        """What a capture attempt changes, for _capture_rollback: after a capture that raised, or that a peer could not make, the trainer is a twin's that never tried."""
+        opt, s = self.lpdm_opt, self.inner_sampler
+        return (self._graph, self.grads_mode, self.lpdm_losses.count, None if s is None else (s.graph_safe, s.calls),
+                (opt._t, opt._t_dev.clone()) if isinstance(opt, train_ops.FlatAdamW) else None)
+
+    def _capture_rollback(self, before):
+        self._graph, self.grads_mode, self.lpdm_losses.count, sampler, opt = before
+        if sampler:
+            self.inner_sampler.graph_safe, self.inner_sampler.calls = sampler
+        if opt:
+            self.lpdm_opt._t = opt[0]
+            self.lpdm_opt._t_dev.copy_(opt[1])
+
+    def _capture(self, batch, **draws) -> bool:
+        """THE capture of the iteration (enable_graph's docstring); callers hold a _capture_state for the case that it raises.  draws: static noise / timesteps /
+        eps_enc / eps_inf for forward_losses (tests: every replay reads them from self._graph["draws"])."""
+        s = self.inner_sampler
         why = ("not a GPU run" if self.device.type != "cuda" else "the optimizer is not the flat AdamW" if not isinstance(self.lpdm_opt, train_ops.FlatAdamW)
-               else "the inner sampler runs serially on the trainer's modules (--inner-sampler train)" if getattr(self.inner_sampler, "serial", False)
+               else "the inner sampler runs serially on the trainer's modules (--inner-sampler train)" if s is not None and s.serial
                else "the fused layer kernels are off (AMUSE_TRAIN_FUSED=0)" if not train_ops.enabled()
-               else "the inner sampler refreshes its weights every n > 1 calls" if getattr(self.inner_sampler, "refresh", 1) != 1 else None)
+               else "the inner sampler refreshes its weights every n > 1 calls" if s is not None and s.refresh != 1 else None)
         if why is not None:
             print(f"[LPDM-T] training step not captured as a HIP graph: {why}", flush=True)
             return False
         for m in self.model.values():
             m.train()
         torch.set_grad_enabled(True)
-        self.grads_mode, self.steal = "sink", False
-        if self.inner_sampler is not None:
-            self.inner_sampler.graph_safe = True     # initial latents from torch's generator (advances per replay) instead of the host-side clip counter
+        self.grads_mode = "sink"
+        if s is not None:
+            s.graph_safe = True                      # initial latents from torch's generator (advances per replay) instead of the host-side clip counter
         keys = [k for k in ("ld_motion", "ld_audio_con", "ld_audio_emo", "ld_audio_sty") if batch.get(k) is not None]
-        static = {k: batch[k].to(self.device).clone() for k in keys}
-        static["ld_attr"] = batch.get("ld_attr")
+        static = {**{k: batch[k].to(self.device).clone() for k in keys}, "ld_attr": batch.get("ld_attr")}
+        draws = {k: v.to(self.device).clone() for k, v in draws.items()}
         if self.lpdm_losses.body is not None:        # the gendered split as device data: a replay follows the new batch's actors
             static["ld_subjects"] = self.lpdm_losses.body.subjects(batch["ld_attr"])
             if self.lpdm_losses.vtex_grad:           # the transposed posedirs image and the backward partials exist before the capture begins
@@ -421,25 +446,23 @@ class GestureTrainer:
                     e.enable_grad()
                     e.reserve(int(static["ld_motion"].shape[0]) * int(static["ld_motion"].shape[1]))
         lib = train_ops._st(self.device)["lib"]
+        if self._graph is not None:                  # (a second capture: the device-side step count is the optimizer's truth while a graph exists)
+            self.lpdm_opt.sync_step()
         self.lpdm_opt.push_step()
         count0 = self.lpdm_losses.count
         torch.cuda.synchronize(self.device)
         g1, g2 = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-        try:
-            with torch.cuda.graph(g1):
-                loss = self.forward_losses(static)
-                self.backward_into_bucket(loss)
-                out = loss.detach()
-            self.allreduce_gradients()
-            with torch.cuda.graph(g2, pool=g1.pool()):
-                self.lpdm_opt.step_dev()
-                with train_ops._on(self.device):
-                    _libmod.check(lib.amuse_train_epoch_advance(1, torch.cuda.current_stream(self.device).cuda_stream))
-        except Exception:
-            self._graph = None
-            raise
+        with torch.cuda.graph(g1):
+            loss = self.forward_losses(static, **draws)
+            self.backward_into_bucket(loss)
+            out = loss.detach()
+        # (no collective here: nothing is captured around one, and the bucket's gradients are read by nothing before the next backward pass overwrites them)
+        with torch.cuda.graph(g2, pool=g1.pool()):
+            self.lpdm_opt.step_dev()
+            with train_ops._on(self.device):
+                _lib.check(lib.amuse_train_epoch_advance(1, torch.cuda.current_stream(self.device).cuda_stream))
         self.lpdm_losses.count = count0              # (a capture records the launches, it does not run them: no iteration happened)
-        self._graph = {"g1": g1, "g2": g2, "static": static, "keys": keys, "loss": out}
+        self._graph = {"g1": g1, "g2": g2, "static": static, "draws": draws, "keys": keys, "loss": out}
         return True
 
     def _graph_takes(self, batch) -> bool:
@@ -467,16 +490,13 @@ class GestureTrainer:
         packs them, and p.grad points into the bucket again - what allreduce_gradients and the optimizer read."""
         if not self.steal:
             self.flat_grad.zero_()                    # the views stay attached to the bucket; backward accumulates into them
-            if self.grads_mode == "sink":
-                from . import train_ops
-                train_ops.sink_begin(self.flat_param, self.flat_grad)
-                try:
-                    loss.backward()
-                finally:
-                    train_ops.sink_end()
-                return
-            loss.backward()
-            return
+            if self.grads_mode != "sink":
+                return loss.backward()
+            train_ops.sink_begin(self.flat_param, self.flat_grad)
+            try:
+                return loss.backward()
+            finally:
+                train_ops.sink_end()
         for p in self.params:
             p.grad = None
         loss.backward()
@@ -489,7 +509,6 @@ class GestureTrainer:
     def allreduce_gradients(self):
         if self.world <= 1:
             return
-        import torch.distributed as dist
         timed = self.device.type == "cuda"
         if timed:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -505,11 +524,9 @@ class GestureTrainer:
         """Durations (ms) of the all-reduces since the last call, from HIP events.  Call it AFTER a timed region: it waits for the
         recorded events, and a wait inside the loop would serialise host dispatch and device work of a host-bound step."""
         ev, self._ar_events = self._ar_events, []
-        out = []
-        for e0, e1 in ev:
+        for _, e1 in ev:
             e1.synchronize()
-            out.append(e0.elapsed_time(e1))
-        return out
+        return [e0.elapsed_time(e1) for e0, e1 in ev]
 
     # ------------------------------------------------------------------ checkpoints (trainer.py:468-496)
     def save_checkpoint(self, model_path, epoch: int, loss_dict: Optional[dict] = None):
@@ -517,10 +534,8 @@ class GestureTrainer:
         "model_state_dict", "optimizer_state_dict"} with the reference's loss-encoded file names (the readers pick "best"
         by the `total` field, infer_ldm.py:76-81)."""
         ld = {k: float(v) for k, v in (loss_dict or self.lpdm_losses.compute()).items()}
-        for k in ("recons_feature", "recons_joints", "kl_motion", "gen_feature", "gen_joints", "inst_loss", "total"):
+        for k in ("recons_feature", "recons_joints", "kl_motion", "gen_feature", "gen_joints", "inst_loss", "rec_vtex_displacement", "gen_vtex_displacement", "total"):
             ld.setdefault(k, 0.0)
-        ld.setdefault("rec_vtex_displacement", 0.0)
-        ld.setdefault("gen_vtex_displacement", 0.0)
         tail = "recF{:.4f}_recJ{:.4f}_kl{:.4f}_genF{:.4f}_genJ{:.4f}_instL{:.4f}_vtexR{:.4f}_vtexG{:.4f}_total{:.4f}_e{}.pt".format(
             ld["recons_feature"], ld["recons_joints"], ld["kl_motion"], ld["gen_feature"], ld["gen_joints"], ld["inst_loss"],
             ld["rec_vtex_displacement"], ld["gen_vtex_displacement"], ld["total"], epoch + 1)
@@ -529,8 +544,7 @@ class GestureTrainer:
         p1, p2 = model_path / ("prior_model_NoOpt_" + tail), model_path / ("latdiff_model_wOpt_" + tail)
         own = lambda m: {k: v.detach().clone() for k, v in m.state_dict().items()}   # not views of the 27 MB flat buffer
         torch.save({"epoch": epoch, "model_state_dict": own(self.model["prior"])}, p1)
-        torch.save({"epoch": epoch, "model_state_dict": own(self.model["ldm"]),
-                    "optimizer_state_dict": self.lpdm_opt.state_dict()}, p2)
+        torch.save({"epoch": epoch, "model_state_dict": own(self.model["ldm"]), "optimizer_state_dict": self.lpdm_opt.state_dict()}, p2)
         return p1, p2
 
     # ------------------------------------------------------------------ the epoch loop (trainer.py:353-466)
@@ -543,16 +557,12 @@ class GestureTrainer:
                 sampler.set_epoch(epoch)   # a DistributedSampler reshuffles per epoch only when told (the reference's DataLoader(shuffle=True) does by itself)
             for batch in train_loader:
                 self.train_step(batch)
-                self._steps_done = getattr(self, "_steps_done", 0) + 1
-                if getattr(self, "use_graph", False) and self._graph is None and self._steps_done == 3:
-                    try:                               # from the fourth iteration on: two graph replays per step instead of ~1,300 launches (enable_graph)
-                        ok = self.enable_graph(batch)
-                    except Exception as e:  # noqa: BLE001 - training goes on eagerly
-                        ok = False
-                        print(f"[LPDM-T] HIP-graph capture of the iteration failed ({type(e).__name__}: {str(e)[:160]}): staying eager", flush=True)
-                    self.use_graph = ok
-                    if rank == 0:
-                        print(f"[LPDM-T] iteration {'captured as two HIP graphs around the gradient all-reduce' if ok else 'runs eagerly'}", flush=True)
+                self._steps_done += 1
+                if self.use_graph and self._graph is None and self._steps_done == 3:
+                    # from the fourth iteration on: two graph replays per step instead of ~1,300 launches (enable_graph) - on every rank, or on none
+                    self.use_graph, note = self.capture_or_stay_eager(batch)
+                    if rank == 0 or not self.use_graph:
+                        print(f"[LPDM-T] rank {rank}: iteration {'replays as two HIP graphs around the gradient all-reduce' if self.use_graph else 'runs eagerly'} ({note})", flush=True)
                 if on_iteration is not None:
                     on_iteration(self)
             loss_dict = self.lpdm_losses.compute()
@@ -569,153 +579,6 @@ class GestureTrainer:
             print("[LPDM] Training finished, total time elapsed: %4.4f mins" % ((time.time() - iter_start_time) / 60.0))
 
 
-class HipInnerSampler:
-    """ldm.diffusion_backward (DDIM-50, ldm.py:117-153) + prior.decode of its result on the HIP kernels, on the trainer's
-    CURRENT weights.  refresh = n: amuse_update_weights every n-th call (1 = every iteration, the reference's semantics).
-    dropout = p > 0 (`--inner-sampler train-hip`, AMUSE_TRAIN_INNER=train-hip): the reference's train-mode semantics on the same kernel - the Denoiser's
-    encoder dropouts live in all steps (amuse_set_sample_dropout: masks keyed by the global clip index and the library's dropout epoch, so eager calls
-    draw fresh masks through the clip counter and replays of a captured step through the epoch), and the decode is prior.decode on the trainer's own
-    modules in train mode (the library's dropout-live layer kernels), on the trainer's stream after the join (decode_on_trainer_stream).
-    hip_decode (`--inner-sampler train-hip-decode`, with dropout > 0): the decode stays in the library too - amuse_set_decode_dropout turns on the dropout
-    instantiations of the staged decode kernels, masks keyed like the sampler's (seed + 2, the sample's clip base, the dropout epoch) - and on the sampler's
-    side stream, off the trainer's critical stream."""
-
-    def __init__(self, trainer_models: Dict[str, nn.Module], device, precision: str = "bf16", refresh: int = 1, seed: int = 2024,
-                 ldm_cfg: Optional[dict] = None, flat: Optional[tuple] = None, rank: int = 0, world: int = 1, dropout: float = 0.0,
-                 hip_decode: bool = False):
-        from .engine import HipEngine
-        self.models, self.precision, self.refresh, self.seed = trainer_models, precision, max(1, refresh), seed
-        self.flat = flat                        # (prior, denoiser) flat fp32 images that ARE the parameters (GestureTrainer.flat_param)
-        self.engine = HipEngine(self._den_state(), self._prior_state(), device)
-        self.engine.set_schedule(sch.from_ldm_cfg(ldm_cfg, "ddim") if ldm_cfg and "scheduler" in ldm_cfg else sch.ddim_table())
-        self.calls, self.clip_counter, self.sync_ms = 0, 0, []
-        self.rank, self.world = rank, world
-        # the in-loop decode shares the GPU with the networks' forward pass (side stream): the per-clip kernel keeps it on `bsz` CUs (0.51 ms on 32 of 256) where the staged
-        # launches AUTO would take below 64 clips spread over all of them (0.42 ms of 19 chip-wide launches in the forward pass's way)
-        self.engine.set_decode_path("fused")
-        self.what = {"bf16": 2, "fp32x": 8, "fp16": 16}.get(precision, 1)   # AMUSE_UPD_* mask of the streams this sampler runs
-        self.on_device = True      # re-pack on the GPU straight from the trainer's flat parameter buffer (False: the host path of amuse_update_weights; tests)
-        self.dropout = float(dropout)
-        self.hip_decode = bool(hip_decode) and self.dropout > 0
-        self.decode_on_trainer_stream = self.dropout > 0 and not self.hip_decode
-        self._clip0 = 0            # clip base of the last sample: the decode's masks follow the sampler's clips
-        if self.dropout > 0:
-            self.engine.set_sample_dropout(self.dropout, seed=seed + 1)
-
-    def _den_state(self):
-        return {k: v.detach().cpu().numpy() for k, v in self.models["ldm"].denoiser.state_dict().items()}
-
-    def _prior_state(self):
-        return {k: v.detach().cpu().numpy() for k, v in self.models["prior"].state_dict().items()}
-
-    def __call__(self, con, emo, sty, bsz):
-        return self.decode(self.sample_latents(con, emo, sty, bsz))
-
-    def decode(self, lat):
-        if self.hip_decode:       # train mode inside the library's decode kernels (a host-side switch: safe inside a captured step)
-            self.engine.set_decode_dropout(self.dropout, seed=self.seed + 2, clip_index0=self._clip0)
-            return self.engine.vae_decode(lat, None, self.precision, return_feats=True)["feats"]
-        if self.dropout > 0:      # train mode: the trainer's MotionPrior.decode, dropout live through the layer kernels
-            return self.models["prior"].decode(lat[None], [SEQ_LEN] * lat.shape[0])
-        return self.engine.vae_decode(lat, None, self.precision, return_feats=True)["feats"]
-
-    def sample_latents(self, con, emo, sty, bsz):
-        if self.calls % self.refresh == 0 and self.calls > 0:
-            t0 = time.perf_counter()
-            if self.on_device:
-                # the weights never leave the GPU: the parameters ARE the flat images (or one torch.cat per network), then a gather kernel per packed image
-                if self.flat is not None:
-                    pri, den = self.flat
-                else:
-                    from .engine import flatten_on_device
-                    from . import weights as wts
-                    den = flatten_on_device(self.models["ldm"].denoiser.state_dict(), wts.denoiser_param_spec())
-                    pri = flatten_on_device(self.models["prior"].state_dict(), wts.prior_param_spec())
-                self.engine.update_weights_device(den, pri, what=self.what)
-            else:
-                self.engine.update_weights(self._den_state(), self._prior_state(), what=self.what)
-            self.sync_ms.append((time.perf_counter() - t0) * 1e3)
-        self.calls += 1
-        if getattr(self, "graph_safe", False):
-            # inside a captured training step (GestureTrainer.enable_graph) the host-side clip counter would be frozen: the initial latents come from torch's
-            # generator on the device, whose state the graph advances per replay
-            # (with dropout live the clip index still keys the masks: rank r takes clips [r bsz, (r + 1) bsz), the epoch word advances per replay)
-            self._clip0 = self.rank * bsz if self.dropout > 0 else 0
-            return self.engine.sample(con, emo, sty, self.precision, seed=self.seed, x_init=torch.randn(bsz, 128, device=self.engine.device),
-                                      clip_index0=self._clip0)
-        # initial latents are keyed by a global clip index: rank r draws clips [counter + r * bsz, counter + (r + 1) * bsz)
-        self._clip0 = self.clip_counter + self.rank * bsz
-        lat = self.engine.sample(con, emo, sty, self.precision, seed=self.seed, clip_index0=self._clip0)
-        self.clip_counter += bsz * self.world
-        return lat
-
-
-def numpy_denoiser_state(ldm) -> dict:
-    return {k: v.detach().cpu().numpy() for k, v in ldm.denoiser.state_dict().items()}
-
-
-class TrainModeInnerSampler:
-    """OPT-IN (`--inner-sampler train`, AMUSE_TRAIN_INNER=train): the no-gradient half of an iteration with the reference's own semantics.  The reference calls
-    `ldm.diffusion_backward` (DDIM-50, ldm.py:117-153) and `prior.decode` inside its training loop while both networks are in train() mode
-    (trainer.py:357-358,413-415): every dropout of the Denoiser's nine encoder layers - attention weights, both residual branches, the FFN activation - and of
-    the prior's decoder is LIVE in all 50 denoising steps and in the decode.  HipInnerSampler (the default) runs the persistent eval-mode sampler kernel
-    instead: ~10 x faster and, being deterministic, the better estimate of what the networks generate - a stated difference.  This class is the reference's
-    form: the trainer's own modules as they are (train mode -> dropout through the library's counter-based masks, train_ops / k_train.hip; eval mode -> none),
-    50 x Denoiser.forward + the scheduler row update of amuse_amd/scheduler.py (the arithmetic the sampler kernels apply, tests/test_pins_cpu.py), one decode.
-    Runs on the trainer's stream (the layer calls share the rocBLAS handle with the forward pass).  Initial latents: the library's counter-based normals on the
-    GPU (the HIP sampler's draw for the same clips), torch.randn from a seeded generator on the CPU."""
-    serial = True      # forward_losses: no side stream
-
-    def __init__(self, trainer_models: Dict[str, nn.Module], device, seed: int = 2024, ldm_cfg: Optional[dict] = None, rank: int = 0, world: int = 1,
-                 engine=None):
-        self.models, self.device, self.seed, self.rank, self.world = trainer_models, torch.device(device), seed, rank, world
-        self.table = sch.from_ldm_cfg(ldm_cfg, "ddim") if ldm_cfg and "scheduler" in ldm_cfg else sch.ddim_table()
-        self.coef = torch.as_tensor(self.table.coef)            # (T, 8) host copy: the loop reads python floats, no device sync
-        self.engine = engine                                    # a HipEngine to draw the initial latents from (GPU), or None
-        self.calls, self.clip_counter, self.sync_ms = 0, 0, []
-
-    def initial_latents(self, bsz: int) -> torch.Tensor:
-        c0 = self.clip_counter + self.rank * bsz
-        self.clip_counter += bsz * self.world
-        if self.engine is not None:
-            return self.engine.counter_normal(self.seed, c0, bsz, 0, 0)
-        g = torch.Generator().manual_seed((self.seed * 1000003 + c0) & 0x7FFFFFFF)
-        return torch.randn(bsz, 128, generator=g).to(self.device)
-
-    @staticmethod
-    def scheduler_update(row, x, eps, z=None):
-        """One schedule row [sb, sa, c0, cx, ce, sigma, clip, 0] (include/amuse_hip.h amuse_schedule) in the kernels' operation order."""
-        sb, sa, c0, cx, ce, sg, clipv = (float(v) for v in row[:7])
-        x0 = (x - sb * eps) * (1.0 / sa)
-        if clipv > 0:
-            x0 = x0.clamp(-clipv, clipv)
-        nx = c0 * x0
-        if cx != 0:
-            nx = nx + cx * x
-        if ce != 0:
-            nx = nx + ce * eps
-        if sg != 0:
-            nx = nx + sg * z
-        return nx
-
-    @torch.no_grad()
-    def __call__(self, con, emo, sty, bsz, x_init: Optional[torch.Tensor] = None, return_latents: bool = False):
-        den, prior = self.models["ldm"].denoiser, self.models["prior"]
-        x = (self.initial_latents(bsz) if x_init is None else x_init.to(self.device)) * self.table.init_noise_sigma
-        self.calls += 1
-        for i, t in enumerate(self.table.timesteps):
-            eps = den(x[:, None], int(t), con, emo, sty)[0][:, 0]
-            z = torch.randn_like(x) if float(self.coef[i, 5]) != 0 else None          # (eta > 0 only)
-            x = self.scheduler_update(self.coef[i], x, eps, z)
-        feats = prior.decode(x[None], [SEQ_LEN] * bsz)
-        return (feats, x) if return_latents else feats
-
-
-def _train_ops_enabled() -> bool:
-    from . import train_ops
-    return train_ops.enabled()
-
-
 def ablation_kind(lmdb_id: Optional[str]) -> Optional[str]:
     """The ablation variant the reference derives from the LMDB cache id (trainer.py:396-401): full | emotion | identity | baseline."""
     if not lmdb_id:
@@ -728,16 +591,14 @@ def ablation_kind(lmdb_id: Optional[str]) -> Optional[str]:
     return kind
 
 
-def build_trainer(device, rank: int = 0, world: int = 1, process_group=None, seed: int = 0, use_hip_sampler: bool = True,
-                  dropout: float = 0.1, sampler_refresh: int = 1, ldm_cfg: Optional[dict] = None, lr: float = 1e-4,
-                  kind: Optional[str] = None, inner: Optional[str] = None, grads_mode: str = "steal", sampler_stream: bool = True,
-                  optimizer: str = "flat", denoiser_stream: bool = True, body=None, vtex_grad: bool = False) -> GestureTrainer:
-    """Random-init prior + ldm (the deterministic weights of amuse_amd/weights.py, identical on every rank - what DDP's
-    initial broadcast gives the reference's DataParallel-less single-GPU run) and the trainer around them.
-    lr = TRAIN_PARAM.latent_diffusion.lr_base (trainer.py:181-184); ldm_cfg = configs/<arch>.json merged with diff_o.yaml (its
-    "losses" section weighs the terms, its schedulers drive add_noise and the in-loop sampler); kind = the LMDB id's ablation
-    variant (ablation_kind): the condition the variant never feeds keeps its projection out of the optimizer."""
-    from . import weights as wts
+def build_trainer(device, rank: int = 0, world: int = 1, process_group=None, seed: int = 0, use_hip_sampler: bool = True, dropout: float = 0.1, sampler_refresh: int = 1,
+                  ldm_cfg: Optional[dict] = None, lr: float = 1e-4, kind: Optional[str] = None, inner: Optional[str] = None, grads_mode: str = "steal",
+                  sampler_stream: bool = True, optimizer: str = "flat", denoiser_stream: bool = True, body=None, vtex_grad: bool = False, use_graph: bool = False) -> GestureTrainer:
+    """Random-init prior + ldm (the deterministic weights of amuse_amd/weights.py, identical on every rank - what DDP's initial broadcast gives the reference's
+    DataParallel-less single-GPU run) and the trainer around them.  lr = TRAIN_PARAM.latent_diffusion.lr_base (trainer.py:181-184); ldm_cfg = configs/<arch>.json merged
+    with diff_o.yaml (its "losses" section weighs the terms, its schedulers drive add_noise and the in-loop sampler); kind = the LMDB id's ablation variant (ablation_kind):
+    the condition the variant never feeds keeps its projection out of the optimizer; inner = the inner sampler's mode (inner_sampler.MODES; default AMUSE_TRAIN_INNER, else
+    eval); use_graph: the epoch loop captures the iteration as two HIP graphs (GestureTrainer.capture_or_stay_eager)."""
     prior = load_numpy_state(MotionPrior(dropout=dropout), wts.make_prior_weights(seed))
     ldm = LatentDiffusionTrainModule(ldm_cfg, dropout=dropout)
     load_numpy_state(ldm.denoiser, wts.make_denoiser_weights(seed))
@@ -747,39 +608,15 @@ def build_trainer(device, rank: int = 0, world: int = 1, process_group=None, see
         loss_cfg = dict(ldm_cfg["losses"], use_recons_joints=False, vtex_displacement=False)
     if body is not None:                            # the vertex terms are on exactly when the caller hands over the body models (amuse_amd.body.BodyLosses)
         loss_cfg = dict(loss_cfg or LOSS_CFG, vtex_displacement=True)
-    tr = GestureTrainer(prior, ldm, device, lr=lr, loss_cfg=loss_cfg, inner_sampler=None, process_group=process_group,
-                        world=world, kind=None if kind == "full" else kind, grads_mode=grads_mode, sampler_stream=sampler_stream, optimizer=optimizer, denoiser_stream=denoiser_stream,
-                        body=body, vtex_grad=vtex_grad)
-    inner = inner or os.environ.get("AMUSE_TRAIN_INNER", "eval")
-    if inner not in ("eval", "train", "train-hip", "train-hip-decode"):
-        raise ValueError(f"inner sampler {inner!r}: 'eval' (the persistent HIP sampler kernel, default), 'train' (the reference's train-mode semantics, dropout "
-                         "live, through the modules), 'train-hip' (the same semantics on the persistent HIP sampler kernel) or 'train-hip-decode' (train-hip with "
-                         "the train-mode decode in the HIP decode kernels too)")
-    if inner == "train-hip" and torch.device(device).type != "cuda":
-        raise RuntimeError("inner sampler 'train-hip' runs the dropout-live HIP sampler kernel: there is no CPU path (use inner='train' on the CPU)")
-    if inner == "train-hip-decode" and torch.device(device).type != "cuda":
-        raise RuntimeError("inner sampler 'train-hip-decode' runs the dropout-live HIP sampler and decode kernels: there is no CPU path (use inner='train' on the CPU)")
-    if inner == "train":      # TrainModeInnerSampler: the modules themselves (any device); on the GPU the initial latents are the HIP sampler's draws
-        eng = None
-        if torch.device(device).type == "cuda":
-            from .engine import HipEngine
-            eng = HipEngine(numpy_denoiser_state(ldm), numpy_state(prior), device)   # (only amuse_counter_normal is used: the HIP sampler's initial latents)
-        tr.inner_sampler = TrainModeInnerSampler(tr.model, device, ldm_cfg=ldm_cfg, rank=rank, world=world, engine=eng)
-    elif use_hip_sampler:
-        if torch.device(device).type != "cuda":
-            raise RuntimeError("the in-loop sampler of train_gesture runs on the HIP kernels: no CPU path (pass use_hip_sampler=False "
-                               "to train without the no-gradient gen_feature term)")
-        tr.inner_sampler = HipInnerSampler(tr.model, device, refresh=sampler_refresh, ldm_cfg=ldm_cfg,
-                                           flat=(tr.flat_param[:tr.n_prior], tr.flat_param[tr.n_prior:]), rank=rank, world=world,
-                                           dropout=dropout if inner in ("train-hip", "train-hip-decode") else 0.0, hip_decode=inner == "train-hip-decode")
+    tr = GestureTrainer(prior, ldm, device, lr=lr, loss_cfg=loss_cfg, process_group=process_group, world=world, kind=None if kind == "full" else kind, grads_mode=grads_mode,
+                        sampler_stream=sampler_stream, optimizer=optimizer, denoiser_stream=denoiser_stream, body=body, vtex_grad=vtex_grad, use_graph=use_graph)
+    tr.inner_sampler = ins.build(inner or os.environ.get("AMUSE_TRAIN_INNER", "eval"), tr, device, rank, world, ldm_cfg, sampler_refresh, dropout, use_hip_sampler)
     return tr
 
 
 def bench_main(args):
     """`python bench.py --config train [--gpus N]`: iterations/s of the data-parallel step at batch 32 per GPU (weak
     scaling: the reference's batch_size 32 is per process), all-reduce ms, HIP weight re-pack ms.  Prints one JSON line."""
-    import json
-    import torch.distributed as dist
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -807,11 +644,7 @@ def bench_main(args):
     # the iteration as two HIP graphs around the all-reduce (GestureTrainer.enable_graph): the host's ~1,300 launches per step become two replays
     graphed, graph_note = False, "--no-graph"
     if not getattr(args, "no_graph", False):
-        try:
-            graphed = tr.enable_graph(batches[0])
-            graph_note = "captured" if graphed else "not capturable in this configuration: eager"
-        except Exception as e:  # noqa: BLE001 - the bench falls back to the eager step and says so
-            graphed, graph_note = False, f"capture failed ({type(e).__name__}: {str(e)[:200]}): eager"
+        graphed, graph_note = tr.capture_or_stay_eager(batches[0])     # (a failed capture: the eager step on all ranks, and the line says so)
         for i in range(3):
             tr.train_step(batches[i % 4])
     barrier()
@@ -836,7 +669,7 @@ def bench_main(args):
             "ms_per_step": round(elapsed / args.steps * 1e3, 3),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": f"train_gesture (configs/diff_latent_v2.json): prior encode/decode + epsilon loss under autograd "
-                                   f"(fp32; transformer layers = one autograd.Function each on the library's layer entry points: HIP glue, fp32 attention and fp32-MFMA GEMM kernels - no vendor BLAS{'' if __import__('amuse_amd.train_ops', fromlist=['x']).enabled() else ' - SWITCHED OFF: eager torch'}), in-loop DDIM-50 sampler + decode on the HIP kernels (bf16), AdamW(1e-4), one flat "
+                                   f"(fp32; transformer layers = one autograd.Function each on the library's layer entry points: HIP glue, fp32 attention and fp32-MFMA GEMM kernels - no vendor BLAS{'' if train_ops.enabled() else ' - SWITCHED OFF: eager torch'}), in-loop DDIM-50 sampler + decode on the HIP kernels (bf16), AdamW(1e-4), one flat "
                                    f"all-reduce of {tr.n_grad_elements():,} fp32 gradients; batch {bsz} per GPU, {bsz * world} global; "
                                    f"vertex-displacement loss off (needs SMPL-X assets)",
                        "batch_per_gpu": bsz, "grad_elements": tr.n_grad_elements(),
@@ -851,13 +684,7 @@ def bench_main(args):
                                       "weight-gradient reductions (k_train_wgrad), and the generic kernel (k_train_gemm_any) for the 333-wide embedding / output layers, the 32-row "
                                       "condition / memory projections and the Denoiser's 160-row layers; attention, LayerNorm / dropout / GELU / bias gradients, AdamW hand-written too; "
                                       "the library links and loads no vendor BLAS (torch's own ops remain only in the loss arithmetic)",
-                       "inner_sampler": ("train: the reference's train-mode loop, dropout live (TrainModeInnerSampler)" if getattr(tr.inner_sampler, "serial", False)
-                                         else "train-hip-decode: the persistent HIP sampler kernel with the Denoiser's dropouts live + the train-mode decode in the HIP "
-                                              "decode kernels, both on the sampler's stream (the reference's semantics)" if getattr(tr.inner_sampler, "hip_decode", False)
-                                         else "train-hip: the persistent HIP sampler kernel with the Denoiser's dropouts live + the train-mode prior.decode "
-                                              "(the reference's semantics)" if getattr(tr.inner_sampler, "dropout", 0) > 0
-                                         else "eval: the persistent HIP sampler kernel (dropout off - the reference's loop runs in train mode; opt in with "
-                                              "AMUSE_TRAIN_INNER=train-hip, or =train for the module loop)")},
+                       "inner_sampler": ins.MODES[tr.inner_sampler.mode].text},
             "samples_per_s": round(its * bsz * world, 1),
             "allreduce_ms": round(float(np.median(ar)), 3) if ar else None,
             "hip_weight_repack_ms": round(float(np.median(sync)), 3) if sync else None,
@@ -886,11 +713,8 @@ def main(argv=None):
     ap.add_argument("--lr", type=float, default=1e-4, help="TRAIN_PARAM.latent_diffusion.lr_base (AdamW, trainer.py:181-184)")
     ap.add_argument("--kind", default=None, choices=["full", "emotion", "identity", "baseline"],
                     help="ablation variant (default: derived from the --cache id like trainer.py:396-401; synthetic data: full)")
-    ap.add_argument("--inner-sampler", default=None, choices=["eval", "train", "train-hip", "train-hip-decode"],
-                    help="the no-gradient DDIM-50 + decode of every iteration: eval (default) = the persistent HIP sampler kernel, dropout off; train = the "
-                         "reference's semantics (ldm.py:117-153 under model.train(): every dropout live) through the trainer's own modules, ~10 x slower; "
-                         "train-hip = the same semantics on the persistent HIP sampler kernel (dropout-live instantiation) + the train-mode decode on the "
-                         "trainer's modules; train-hip-decode = train-hip with the decode in the HIP decode kernels too (amuse_set_decode_dropout), on the sampler's stream")
+    ap.add_argument("--inner-sampler", default=None, choices=list(ins.MODES),
+                    help="the no-gradient DDIM-50 + decode of every iteration (default: AMUSE_TRAIN_INNER, else eval).  " + ins.MODES_TEXT)
     ap.add_argument("--no-graph", action="store_true", help="keep the iteration eager (default on the GPU: captured as two HIP graphs after three eager iterations)")
     ap.add_argument("--ldm-cfg", default=None, help="JSON file: configs/<arch>.json merged with diff_o.yaml (losses, schedulers); default: the shipped values")
     ap.add_argument("--smplx-models", default=None, help="directory holding SMPLX_MALE.npz, SMPLX_FEMALE.npz and SMPLX_NEUTRAL.npz: train WITH the two vertex-displacement "
@@ -916,7 +740,6 @@ def main(argv=None):
     if device.type == "cuda":
         torch.cuda.set_device(device)       # also for ONE rank on cuda:N, N > 0: the library's handles and workspaces key on the current device
     if world > 1:
-        import torch.distributed as dist
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         if device.type == "cuda":
             dist.init_process_group("nccl", device_id=device)
@@ -927,7 +750,6 @@ def main(argv=None):
     fixseed(args.seed + rank)            # scripts/main.py fixseed(TRAIN_PARAM.seed); per-rank offset: ranks draw different noise / timesteps
     ldm_cfg = None
     if args.ldm_cfg:
-        import json
         ldm_cfg = json.load(open(args.ldm_cfg))
     kind = args.kind or ablation_kind(args.cache)
     body = None
@@ -940,27 +762,13 @@ def main(argv=None):
                 print("[LPDM-T] --vtex-grad: the vertex-displacement terms CARRY GRADIENT to the decoder (skinning backward pass).  This DEVIATES from the reference, "
                       "which computes its vertices under no_grad (latent_losses.py:173)", flush=True)
     tr = build_trainer(device, rank, world, process_group=pg, use_hip_sampler=device.type == "cuda", ldm_cfg=ldm_cfg, lr=args.lr, kind=kind,
-                       inner=args.inner_sampler, body=body, vtex_grad=args.vtex_grad)
-    tr.use_graph = device.type == "cuda" and not args.no_graph
+                       inner=args.inner_sampler, body=body, vtex_grad=args.vtex_grad, use_graph=device.type == "cuda" and not args.no_graph)
     if rank == 0:
         lc = tr.lpdm_losses.cfg
         print(f"[LPDM-T] lr {args.lr:g}, ablation kind {kind or 'full'}, loss weights " +
               ", ".join(f"{k} {lc[k]}" for k in ("LAMBDA_REC", "LAMBDA_KL", "LAMBDA_LATENT", "LAMBDA_GEN")), flush=True)
-        if tr.inner_sampler is None:
-            print("[LPDM-T] inner sampler: none (CPU run: the no-gradient gen_feature term is off)", flush=True)
-        elif getattr(tr.inner_sampler, "serial", False):
-            print("[LPDM-T] inner sampler: train - the reference's semantics (ldm.py:117-153 and prior.decode under model.train(): every dropout live), on the trainer's own modules", flush=True)
-        elif getattr(tr.inner_sampler, "hip_decode", False):
-            print(f"[LPDM-T] inner sampler: train-hip-decode - the reference's semantics (every dropout live, p = {tr.inner_sampler.dropout:g}) on the persistent HIP sampler "
-                  "kernel and the dropout instantiations of the HIP decode kernels, both on the sampler's stream", flush=True)
-        elif getattr(tr.inner_sampler, "dropout", 0) > 0:
-            print(f"[LPDM-T] inner sampler: train-hip - the reference's semantics (every dropout live, p = {tr.inner_sampler.dropout:g}) on the persistent HIP sampler "
-                  "kernel, then prior.decode on the trainer's modules in train mode", flush=True)
-        else:
-            print("[LPDM-T] inner sampler: eval - DDIM-50 + decode on the persistent HIP sampler kernel with dropout OFF.  DEVIATION from the reference, whose loop runs under "
-                  "model.train() with every dropout live (scripts/trainer.py:357-358,413-415): the gen_feature loss term sees un-dropped samples.  "
-                  "--inner-sampler train-hip (or AMUSE_TRAIN_INNER=train-hip) selects the reference's semantics on the HIP kernel, --inner-sampler train "
-                  "through the modules (~10 x slower).", flush=True)
+        print("[LPDM-T] inner sampler: " + ("none (CPU run: the no-gradient gen_feature term is off)" if tr.inner_sampler is None
+                                           else ins.MODES[tr.inner_sampler.mode].text), flush=True)
     if args.cache:
         from .dataload import LatentDiffusionCache, make_loader
         loader = make_loader(LatentDiffusionCache.open(args.cache), args.batch, rank=rank, world=world, seed=args.seed)
@@ -968,7 +776,6 @@ def main(argv=None):
         loader = [synthetic_batch(args.batch, 1000 * rank + i, device) for i in range(args.iters_per_epoch)]
     tr.train_prior_latdiff_forward_backward_v2(loader, args.epochs, args.out, model_save_freq=args.save_freq, rank=rank)
     if world > 1:
-        import torch.distributed as dist
         dist.barrier()
         dist.destroy_process_group()
     return 0

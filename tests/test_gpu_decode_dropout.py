@@ -317,7 +317,7 @@ def test_trainer_with_the_train_mode_hip_decode():
     tr = build_trainer("cuda:0", inner="train-hip-decode")
     s = tr.inner_sampler
     assert isinstance(s, HipInnerSampler) and s.dropout == pytest.approx(0.1) and s.hip_decode and not s.decode_on_trainer_stream
-    assert not getattr(s, "serial", False)
+    assert not getattr(s, "serial", False) and s.mode == "train-hip-decode"
     batch = synthetic_batch(32, 3, "cuda:0")
     for _ in range(3):
         loss = float(tr.train_step(batch))

@@ -318,7 +318,7 @@ def test_trainer_with_the_train_mode_hip_sampler():
     torch.manual_seed(0)
     tr = build_trainer("cuda:0", inner="train-hip")
     s = tr.inner_sampler
-    assert isinstance(s, HipInnerSampler) and s.dropout == pytest.approx(0.1) and not getattr(s, "serial", False)
+    assert isinstance(s, HipInnerSampler) and s.dropout == pytest.approx(0.1) and not getattr(s, "serial", False) and s.mode == "train-hip"
     batch = synthetic_batch(32, 3, "cuda:0")
     for _ in range(3):
         loss = float(tr.train_step(batch))

@@ -90,6 +90,7 @@ def test_update_weights_device_equals_the_host_path():
 
 def test_train_step_with_hip_inner_sampler():
     from amuse_amd.engine import HipEngine
+    from amuse_amd.nn_modules import numpy_state
     from amuse_amd.train_gesture import build_trainer, synthetic_batch
     torch.manual_seed(0)
     tr = build_trainer("cuda:0")
@@ -106,7 +107,7 @@ def test_train_step_with_hip_inner_sampler():
     s = tr.inner_sampler
     assert s.flat is not None and s.on_device
     s(batch["ld_audio_con"], batch["ld_audio_emo"], batch["ld_audio_sty"], 32)
-    fresh = HipEngine(s._den_state(), s._prior_state())
+    fresh = HipEngine(numpy_state(s.models["ldm"].denoiser), numpy_state(s.models["prior"]))
     fresh.set_schedule(s.engine.schedule)
     fresh.set_decode_path("fused")                    # (the in-loop sampler pins the per-clip decode kernel: HipInnerSampler.__init__)
     lat_a = s.engine.sample(batch["ld_audio_con"], batch["ld_audio_emo"], batch["ld_audio_sty"], "bf16", seed=1)
@@ -114,7 +115,7 @@ def test_train_step_with_hip_inner_sampler():
     assert torch.equal(lat_a, lat_b) and len(s.sync_ms) >= 4
     assert torch.equal(s.engine.vae_decode(lat_a, None, "bf16")["poses"], fresh.vae_decode(lat_b, None, "bf16")["poses"])
     # ... and so does the host path
-    s.engine.update_weights(s._den_state(), s._prior_state(), what=2)
+    s.engine.update_weights(numpy_state(s.models["ldm"].denoiser), numpy_state(s.models["prior"]), what=2)
     assert torch.equal(s.engine.sample(batch["ld_audio_con"], batch["ld_audio_emo"], batch["ld_audio_sty"], "bf16", seed=1), lat_b)
     fresh.close()
 

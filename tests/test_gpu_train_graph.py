@@ -7,7 +7,8 @@
   * the device-side dropout epoch (amuse_train_epoch_set / _advance) in the kernels that train the model - ln_fwd / ln_bwd, bias_gelu_drop_fwd / _bwd, the attention
     kernels, and the decoder layer's k_train_vk / k_train_dc through train_ops.decoder_layer;
   * the captured step itself, dropout live: forward + losses + backward into the bucket as one graph, step_dev() + the epoch advance as a second one, replayed three
-    times against the same three calls made eagerly on a twin trainer - BITWISE (same kernels, same operands, same masks, ordered reductions).
+    times against the same three calls made eagerly on a twin trainer - BITWISE (same kernels, same operands, same masks, ordered reductions);
+  * a capture that fails while its second graph is recorded: the trainer is left as it was, bitwise a twin that never tried, and can still be captured.
 
 The bar of the optimizer tests is this project's own 2e-6 of the largest entry (tests/test_gpu_train_ops.py test_flat_adamw_equals_torch_adamw_and_keeps_its_state_layout),
 at lr 3e-3 and weight decay 0.01: one skipped or doubled update is ~1e-3 of the largest parameter away.  Every test leaves the epoch at 0 and train_ops' host-side offset
@@ -447,17 +448,20 @@ _TENSOR_KEYS = ("ld_motion", "ld_audio_con", "ld_audio_emo", "ld_audio_sty")
 
 def test_captured_step_equals_the_eager_step_bit_for_bit():
     """Two trainers from identical arguments (batch 4, the gradient sink, dropout 0.1 LIVE, the default HIP inner sampler, the Denoiser's and the sampler's streams on):
-    G replays the step as two graphs - forward_losses + backward_into_bucket | step_dev + amuse_train_epoch_advance, GestureTrainer.enable_graph's structure with the
-    test's own capture so that every draw stays explicit - and E makes the same three calls eagerly at the epoch pinned to the replay's number.  After each of three
-    replays on three different batches the loss, the gradient bucket, the parameters, both moments and the device-side step count are BITWISE equal.
+    G replays the step as two graphs - forward_losses + backward_into_bucket | step_dev + amuse_train_epoch_advance, captured by GestureTrainer._capture, the routine
+    enable_graph runs, with the test's draws as its static ones so that every draw stays explicit - and E makes the same three calls eagerly at the epoch pinned to the
+    replay's number.  After each of three replays on three different batches the loss, the gradient bucket, the parameters, both moments and the device-side step count
+    are BITWISE equal.
 
     Explicit draws: noise, timesteps and both rsample draws are device tensors (copied into G's static ones per replay); prior.encode's own rsample() still runs, its
     value is overwritten.  Dropout masks: seed = torch's initial seed, offsets from train_ops' host-side counter - pinned to the same value before the capture and before
-    each eager step - and the device-side epoch; the sampler's initial latents: its clip counter, pinned likewise.
+    each eager step - and the device-side epoch.  The sampler's initial latents: the shipped capture draws them from torch's device generator (graph_safe), so E's sampler
+    is switched to the same source and the generator is seeded alike before each replay and each eager step (a replay starts from the generator's state of that moment, as
+    an eager step does); the clip counter stays pinned for the warm-up steps.
 
     The epoch is G's own: after every replay it is read through a small layer call (and must have advanced by one), E pins it for its step, and it is put back to the
     value read.  Control: E's forward + backward on replay 1's operands at epoch 0 instead of 1 does NOT give G's loss or bucket."""
-    from amuse_amd import _lib, train_gesture as tg, train_ops as T
+    from amuse_amd import train_gesture as tg, train_ops as T
     dev = torch.device(DEV)
     B, K, CLIP = 4, 5000, 64
     with _clean_state():
@@ -487,33 +491,24 @@ def test_captured_step_equals_the_eager_step_bit_for_bit():
         assert all(torch.equal(a, b) for a, b in zip(state(G), state(E))) and int(G.lpdm_opt._t_dev) == 2        # the precondition
         assert G._den_stream is not None and G._side_stream is not None and E._den_stream is not None and E._side_stream is not None
 
-        # the capture on G
-        static = {k: warm[0][k].clone() for k in _TENSOR_KEYS}
-        static["ld_attr"] = warm[0]["ld_attr"]
-        sdraws = {k: v.clone() for k, v in warm[1].items()}
-        lib = T._st(dev)["lib"]
+        # the capture on G: the trainer's own routine, the warm-up batch and draws as its static tensors
         pin(G)
-        G.lpdm_opt.push_step()
         torch.cuda.synchronize()
         held = [t.clone() for t in state(G)]
         count0 = G.lpdm_losses.count
-        g1, g2 = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g1):
-            loss = G.forward_losses(static, **sdraws)
-            G.backward_into_bucket(loss)
-            loss_g = loss.detach()
-        with torch.cuda.graph(g2, pool=g1.pool()):
-            G.lpdm_opt.step_dev()
-            with T._on(dev):
-                _lib.check(lib.amuse_train_epoch_advance(1, torch.cuda.current_stream(dev).cuda_stream))
-        G.lpdm_losses.count = count0
+        assert G._capture(warm[0], **warm[1]) and G._graph is not None
+        g1, g2, static, sdraws, loss_g = (G._graph[k] for k in ("g1", "g2", "static", "draws", "loss"))
+        assert set(sdraws) == set(warm[1]) and all(static[k].data_ptr() != warm[0][k].data_ptr() for k in _TENSOR_KEYS)
+        assert G.lpdm_losses.count == count0 and G.inner_sampler.graph_safe
+        E.inner_sampler.graph_safe = True
         torch.cuda.synchronize()
         assert all(torch.equal(a, b) for a, b in zip(held, state(G)))        # a capture runs nothing
         assert _read_epoch() == 0
 
-        def eager(batch, ex, epoch, step):
+        def eager(batch, ex, epoch, step, seed):
             pin(E)
             _epoch_set(epoch)
+            torch.cuda.manual_seed(seed)
             l = E.forward_losses(batch, **ex)
             E.backward_into_bucket(l)
             if step:
@@ -527,16 +522,17 @@ def test_captured_step_equals_the_eager_step_bit_for_bit():
                 static[k].copy_(batch[k])
             for k, v in ex.items():
                 sdraws[k].copy_(v)
+            torch.cuda.manual_seed(900 + r)
             g1.replay()
             g2.replay()
             torch.cuda.synchronize()
             after = _read_epoch()
             assert after == r + 1                                            # the second graph advanced G's epoch by one
             if r == 1:                                                       # the control: the same operands at epoch 0 - other masks, another loss and bucket
-                l0 = eager(batch, ex, 0, step=False)
+                l0 = eager(batch, ex, 0, step=False, seed=900 + r)
                 torch.cuda.synchronize()
                 assert not torch.equal(l0, loss_g) and not torch.equal(E.flat_grad, G.flat_grad)
-            le = eager(batch, ex, r, step=True)
+            le = eager(batch, ex, r, step=True, seed=900 + r)
             _epoch_set(after)
             junk = torch.randn(3_000_000, device=dev).mul_(2)                # an eager allocation between replays
             junk2 = [torch.empty(1 << k, device=dev) for k in range(8, 22)]
@@ -556,6 +552,7 @@ def test_captured_step_equals_the_eager_step_bit_for_bit():
         G.lpdm_opt.sync_step()
         assert G.lpdm_opt._t == 5
         del g1, g2
+        G._graph = None
 
 
 def test_enable_graph_moves_step_count_epoch_and_loss_count_by_one_per_replay():
@@ -569,7 +566,7 @@ def test_enable_graph_moves_step_count_epoch_and_loss_count_by_one_per_replay():
         batches = [tg.synthetic_batch(4, 50 + i, dev) for i in range(3)]
         for i in range(2):
             tr.train_step(batches[i])
-        assert tr.enable_graph(batches[2]) and tr._graph is not None
+        assert tr.enable_graph(batches[2]) and tr._graph is not None and tr._graph["draws"] == {}
         torch.cuda.synchronize()
         assert int(tr.lpdm_opt._t_dev) == 2 and tr.lpdm_losses.count == 2 and _read_epoch() == 0      # a capture runs nothing
         for r in range(2):
@@ -578,3 +575,70 @@ def test_enable_graph_moves_step_count_epoch_and_loss_count_by_one_per_replay():
             assert np.isfinite(loss) and not torch.equal(before, tr.flat_param)
             assert int(tr.lpdm_opt._t_dev) == 3 + r and tr.lpdm_losses.count == 3 + r and _read_epoch() == 1 + r
         tr._graph = None
+
+
+def test_a_capture_that_fails_leaves_the_trainer_as_it_was():
+    """Atomic failure of GestureTrainer.capture_or_stay_eager.  Two trainers from identical arguments (batch 4, grads_mode "steal", dropout 0.1 live, the default HIP
+    sampler), two identical warm-up steps.  On A the optimizer's step_dev is replaced by a function that raises a Python RuntimeError before it launches anything: the
+    first graph is recorded whole (its forked streams joined), the failure comes while the second is being recorded.  Then
+      * the policy method answers (False, note) with the exception's text in the note, nothing ran (parameters, moments, step count, epoch as before), and _graph,
+        grads_mode, steal, the sampler's graph_safe and call count, the loss count and the optimizer's host and device step counts are what they were;
+      * the next eager step with explicit draws is BITWISE - loss, bucket, parameters, moments - that of N, which never tried (the layer kernels' host-side mask offset
+        and the sampler's clip counter are pinned before either step, as in the bit-for-bit test above: they are streams of draws, not trainer state);
+      * a real enable_graph on A then succeeds and a replay is one more iteration."""
+    from amuse_amd import train_gesture as tg, train_ops as T
+    dev = torch.device(DEV)
+    B, K, CLIP = 4, 7000, 32
+    with _clean_state():
+        assert _read_epoch() == 0
+        torch.manual_seed(23)
+        gen = torch.Generator().manual_seed(6)
+        work = [(tg.synthetic_batch(B, 60 + i, dev), _draws(B, gen)) for i in range(3)]
+        A, N = (tg.build_trainer(dev, seed=4, use_hip_sampler=True, inner="eval", dropout=P, grads_mode="steal") for _ in range(2))
+
+        def step(tr, batch, ex):
+            T._OFFSET[0] = K
+            tr.inner_sampler.clip_counter = CLIP
+            return tr.train_step(batch, **ex)
+
+        def facts(tr):
+            return (tr._graph, tr.grads_mode, tr.steal, tr.inner_sampler.graph_safe, tr.inner_sampler.calls, tr.lpdm_losses.count, tr.lpdm_opt._t, int(tr.lpdm_opt._t_dev))
+
+        def tensors(tr):
+            return [tr.flat_param, tr.flat_grad, tr.lpdm_opt._m, tr.lpdm_opt._v]
+
+        for tr in (A, N):
+            for _ in range(2):
+                step(tr, *work[0])
+        torch.cuda.synchronize()
+        assert all(torch.equal(a, b) for a, b in zip(tensors(A), tensors(N)))
+        before, held = facts(A), [t.clone() for t in tensors(A)]
+        assert before[:4] == (None, "steal", True, False) and before[5:7] == (2, 2) and A.inner_sampler.mode == "eval"
+
+        def no_step():
+            raise RuntimeError("injected: the optimizer step cannot be recorded")
+        A.lpdm_opt.step_dev = no_step
+        try:
+            captured, note = A.capture_or_stay_eager(work[0][0])
+        finally:
+            del A.lpdm_opt.step_dev
+        torch.cuda.synchronize()
+        print(f"[failed capture] {note}")
+        assert captured is False and "capture failed (RuntimeError: injected: the optimizer step cannot be recorded)" in note
+        assert facts(A) == before and _read_epoch() == 0
+        assert all(torch.equal(a, b) for a, b in zip(held, tensors(A)))
+
+        la, ln = step(A, *work[1]), step(N, *work[1])
+        torch.cuda.synchronize()
+        assert torch.equal(la, ln), (float(la), float(ln))
+        for name, a, b in zip(("flat_param", "flat_grad", "_m", "_v"), tensors(A), tensors(N)):
+            assert torch.equal(a, b), name
+        assert facts(A)[1:] == facts(N)[1:] and A.lpdm_opt._t == 3
+
+        assert A.enable_graph(work[2][0]) and A._graph is not None and A.grads_mode == "sink" and not A.steal
+        p0 = A.flat_param.clone()
+        loss = float(A.train_step(work[2][0]))
+        torch.cuda.synchronize()
+        assert np.isfinite(loss) and not torch.equal(p0, A.flat_param)
+        assert int(A.lpdm_opt._t_dev) == 4 and A.lpdm_losses.count == 4 and _read_epoch() == 1
+        A._graph = None

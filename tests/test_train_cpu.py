@@ -318,3 +318,141 @@ def test_train_mode_inner_sampler_is_the_references_loop():
     assert np.isfinite(float(loss)) and ld["gen_feature"] > 0
     with pytest.raises(ValueError):
         build_trainer("cpu", inner="bogus")
+
+
+# ---------------------------------------------------------------------------------------------------- capture policy: atomic, and the ranks agree
+_FAKE_CAPTURE = r'''
+def fake_capture(self, batch, **draws):
+    """What GestureTrainer._capture changes on its way (and, unlike it, the loss count for good); `fails`: raises where the real one would be recording."""
+    self.grads_mode = "sink"
+    self.lpdm_losses.count += 1
+    if self.inner_sampler is not None:
+        self.inner_sampler.graph_safe = True
+        self.inner_sampler.calls += 1
+    if fails:
+        raise RuntimeError("injected: this rank cannot capture")
+    self._graph = {"sentinel": True}
+    return True
+'''
+
+_CAPTURE_WORKER = r'''
+import os, sys, types
+import torch, torch.distributed as dist
+sys.path.insert(0, sys.argv[1])
+from amuse_amd.train_gesture import build_trainer, synthetic_batch
+rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
+dist.init_process_group("gloo", rank=rank, world_size=world)
+torch.set_num_threads(2)
+fails = rank == 1
+''' + _FAKE_CAPTURE + r'''
+collectives, real_all_reduce = [0], dist.all_reduce
+def counted(*a, **k):
+    collectives[0] += 1
+    return real_all_reduce(*a, **k)
+dist.all_reduce = counted
+torch.manual_seed(100 + rank)
+tr = build_trainer("cpu", rank, world, inner="train", dropout=0.0)
+tr._capture = types.MethodType(fake_capture, tr)
+facts = lambda: (tr._graph, tr.grads_mode, tr.steal, tr.inner_sampler.graph_safe, tr.inner_sampler.calls, tr.lpdm_losses.count)
+before = facts()
+assert before == (None, "steal", True, False, 0, 0)
+captured, note = tr.capture_or_stay_eager(synthetic_batch(2, 40 + rank))
+assert captured is False, (rank, captured, note)
+assert ("injected: this rank cannot capture" in note) if fails else (note == "capture failed on another rank: eager"), (rank, note)
+assert facts() == before, (rank, facts())
+for i in range(2):                                      # different data and draws per rank, one all-reduce each
+    loss = tr.train_step(synthetic_batch(2, 50 + 10 * i + rank))
+    assert bool(torch.isfinite(loss))
+assert tr.lpdm_losses.count == 2 and tr.grads_mode == "steal" and tr._graph is None
+w = tr.flat_param.detach().clone()
+ws = [torch.empty_like(w) for _ in range(world)]
+dist.all_gather(ws, w)
+assert all(torch.equal(ws[0], x) for x in ws)
+n = torch.tensor([collectives[0]])
+ns = [torch.empty_like(n) for _ in range(world)]
+dist.all_gather(ns, n)
+assert [int(x) for x in ns] == [3] * world, ns          # the agreement + one per step, on both ranks
+assert tr.pop_allreduce_ms() == [] and tr._ar_events == []      # (event timing is the GPU's)
+print(f"CAPTURE_OK {rank}")
+dist.destroy_process_group()
+'''
+
+
+def test_two_rank_capture_failure_on_one_rank_keeps_both_eager_and_in_step(tmp_path):
+    """GestureTrainer.capture_or_stay_eager with the capture routine replaced: rank 0 "captures" (a sentinel graph, the state the real routine flips), rank 1 raises.
+    Both ranks answer not captured and are as they were before the attempt; two further steps leave bitwise equal parameters on both, after the same number of
+    collectives (the agreement and one all-reduce per step).  A rank left waiting in a collective its peer skipped would run into the communicate timeout."""
+    script = tmp_path / "worker.py"
+    script.write_text(_CAPTURE_WORKER)
+    env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29656", OMP_NUM_THREADS="2")
+    procs = [subprocess.Popen([sys.executable, str(script), str(REPO)], env=dict(env, RANK=str(r), WORLD_SIZE="2"),
+                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True) for r in range(2)]
+    outs = [p.communicate(timeout=900)[0] for p in procs]
+    assert all(p.returncode == 0 for p in procs), outs
+    assert "CAPTURE_OK 0" in outs[0] and "CAPTURE_OK 1" in outs[1]
+
+
+def test_a_raising_capture_leaves_a_steal_mode_trainer_as_it_was():
+    """A (grads_mode "steal") attempts a capture that flips the state the real routine flips and then raises - through the policy method and through enable_graph;
+    N, identically seeded, never tries.  A is as before each attempt, and the next step gives N's loss and parameters bitwise."""
+    import types
+    from amuse_amd.train_gesture import build_trainer, synthetic_batch
+    ns = {"fails": True}
+    exec(_FAKE_CAPTURE, ns)
+    A, N = (build_trainer("cpu", use_hip_sampler=False, grads_mode="steal") for _ in range(2))
+    assert torch.equal(A.flat_param, N.flat_param)
+    A._capture = types.MethodType(ns["fake_capture"], A)
+    facts = lambda tr: (tr._graph, tr.grads_mode, tr.steal, tr.lpdm_losses.count)
+    before = facts(A)
+    assert before == (None, "steal", True, 0)
+    captured, note = A.capture_or_stay_eager(synthetic_batch(2, 3))
+    assert captured is False and note.startswith("capture failed (RuntimeError: injected: this rank cannot capture)") and facts(A) == before
+    with pytest.raises(RuntimeError, match="injected"):
+        A.enable_graph(synthetic_batch(2, 3))
+    assert facts(A) == before == facts(N)
+    g = torch.Generator().manual_seed(4)
+    draws = dict(noise=torch.randn(2, 1, 128, generator=g), timesteps=torch.randint(0, 1000, (2,), generator=g),
+                 eps_enc=torch.randn(1, 2, 128, generator=g), eps_inf=torch.randn(1, 2, 128, generator=g))
+    out = []
+    for tr in (A, N):
+        torch.manual_seed(8)                             # the modules' dropout masks
+        out.append(tr.train_step(synthetic_batch(2, 6), **draws))
+    assert torch.equal(out[0], out[1]) and torch.equal(A.flat_param, N.flat_param) and torch.equal(A.flat_grad, N.flat_grad)
+    assert float(A.flat_grad.abs().max()) > 0 and facts(A) == facts(N) == (None, "steal", True, 1)
+    assert N.capture_or_stay_eager(synthetic_batch(2, 3)) == (False, "not capturable in this configuration: eager")   # the real routine: a CPU run
+    assert facts(N) == (None, "steal", True, 1)
+
+
+# literal copies of the bench line's config.inner_sampler texts (bench_main's if / elif ladder at the parent commit): recorded bench lines are compared across rounds
+_INNER_SAMPLER_TEXT = {
+    "train": "train: the reference's train-mode loop, dropout live (TrainModeInnerSampler)",
+    "train-hip-decode": "train-hip-decode: the persistent HIP sampler kernel with the Denoiser's dropouts live + the train-mode decode in the HIP "
+                        "decode kernels, both on the sampler's stream (the reference's semantics)",
+    "train-hip": "train-hip: the persistent HIP sampler kernel with the Denoiser's dropouts live + the train-mode prior.decode "
+                 "(the reference's semantics)",
+    "eval": "eval: the persistent HIP sampler kernel (dropout off - the reference's loop runs in train mode; opt in with "
+            "AMUSE_TRAIN_INNER=train-hip, or =train for the module loop)",
+}
+
+
+def test_inner_sampler_mode_table(capsys):
+    """One table entry per mode `--inner-sampler` accepts; the HIP modes refuse a CPU with the one stated sentence; the bench line's text per mode is the parent's."""
+    from amuse_amd import inner_sampler as ins, train_gesture as tg
+    assert sorted(ins.MODES) == sorted(_INNER_SAMPLER_TEXT) and len(ins.MODES) == 4
+    with pytest.raises(SystemExit):
+        tg.main(["--inner-sampler", "bogus"])
+    err = capsys.readouterr().err
+    assert "bogus" in err and all(name in err for name in ins.MODES)               # argparse lists the names it accepts: the table's
+    for name, text in _INNER_SAMPLER_TEXT.items():
+        assert ins.MODES[name].text == text and text.startswith(name + ": ")
+        assert ins.MODES_TEXT.count(text) == 1
+    for name in ("eval", "train-hip", "train-hip-decode"):
+        assert ins.MODES[name].needs_gpu
+        with pytest.raises(RuntimeError, match=f"inner sampler '{name}' runs on the HIP kernels: there is no CPU path"):
+            tg.build_trainer("cpu", inner=name)
+    assert not ins.MODES["train"].needs_gpu
+    tr = tg.build_trainer("cpu", inner="train")
+    assert tr.inner_sampler.mode == "train" and isinstance(tr.inner_sampler, tg.TrainModeInnerSampler) and isinstance(tr.inner_sampler, ins.InnerSampler)
+    assert tg.build_trainer("cpu", use_hip_sampler=False).inner_sampler is None                   # "no sampler" stays None
+    with pytest.raises(ValueError, match="bogus"):
+        tg.build_trainer("cpu", inner="bogus")

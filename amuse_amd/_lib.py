@@ -35,6 +35,7 @@ EXPORTS = [
     "amuse_body_create", "amuse_body_destroy", "amuse_body_set_subjects", "amuse_body_reserve", "amuse_body_forward", "amuse_body_vertex_loss", "amuse_body_info",
     "amuse_body_enable_grad", "amuse_body_vertex_loss_grad",
     "amuse_longform_plan", "amuse_stitch_windows",
+    "amuse_smooth_banks", "amuse_smooth_motion",
     "amuse_resample_plan", "amuse_resampler_create", "amuse_resampler_destroy", "amuse_resample", "amuse_debug_resample_bank",
     "amuse_render_plan", "amuse_renderer_create", "amuse_renderer_destroy", "amuse_render", "amuse_debug_render_raster",
     "amuse_motion_metrics_row", "amuse_motion_metrics",
@@ -234,6 +235,10 @@ def load() -> C.CDLL:
     lib.amuse_longform_plan.argtypes = [C.c_longlong, C.c_int, ip, ip, ip]
     lib.amuse_stitch_windows.argtypes = [fp, fp, C.c_int, ip, ip, C.c_int, C.c_int, fp, fp, fp, vp]
     lib.amuse_longform_plan.restype = lib.amuse_stitch_windows.restype = C.c_int
+    # motion smoothing (csrc/amuse_smooth.hip): the bank needs no GPU; the filter is context-free (frames and half_window are HOST arrays)
+    lib.amuse_smooth_banks.argtypes = [C.c_int, C.POINTER(C.c_float)]
+    lib.amuse_smooth_motion.argtypes = [fp, fp, C.c_int, ip, C.POINTER(C.c_ubyte), fp, fp, fp, vp]
+    lib.amuse_smooth_banks.restype = lib.amuse_smooth_motion.restype = C.c_int
     # sample-rate conversion (csrc/amuse_resample.hip): the plan and the bank need no GPU; one resampler per (GPU, rate pair)
     lib.amuse_resample_plan.argtypes = [C.c_int, C.c_int, C.c_longlong, ip, ip, ip, C.POINTER(C.c_longlong)]
     lib.amuse_resampler_create.restype = vp

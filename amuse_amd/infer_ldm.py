@@ -252,7 +252,7 @@ class PretrainedLPDM_v1:
         con, emo, sty = self.audio_engine.features_ragged(chunks)
         return [(con[k:k + 1], emo[k:k + 1], sty[k:k + 1]) for k in range(len(chunks))]
 
-    def infer_long(self, waves, hop_frames: int = 270, framerate=16000, baseline=False, sample_rate=None):
+    def infer_long(self, waves, hop_frames: int = 270, framerate=16000, baseline=False, sample_rate=None, smooth=None):
         """AN EXTENSION (the reference has no such path: it asks for 10 s WAVs, scripts/trainer.py:506): waveforms of ANY length -> [{"poses": (L, 55, 3),
         "trans": (L, 3)}, ...] with L = max(300, floor(3 n / 1600)) frames each (amuse_amd/longform.py).  `waves`: a list of (C, n) or (n,) 16 kHz waveforms.
         The mean of the WHOLE waveform is removed once (trainer.py:521), the waveform is cut into the plan's windows (stride hop_frames, the last one short),
@@ -262,7 +262,9 @@ class PretrainedLPDM_v1:
         process_single_seq + diffusion_backward.
         sample_rate (an extension of its own, amuse_amd/resample.py): the rate of `waves` in Hz.  None or 16000: the waveforms are read as 16 kHz, as everywhere
         on this path.  Another rate: channel 0 of every waveform goes through the HIP resampler first and everything above applies to its output.  (`framerate`
-        is NOT this: it mirrors the reference's argument, which nothing reads.)"""
+        is NOT this: it mirrors the reference's argument, which nothing reads.)
+        smooth (an extension of its own, amuse_amd/smooth.py; None: nothing changes by a bit): {"window", "order"[, "hands_window"]} - every joined motion goes
+        through the Savitzky-Golay filter on SO(3), as trainer.run_jobs(smooth=...) does it."""
         from . import longform
         if self.diffusion_only:
             raise NotImplementedError("infer_long is wired for the latent Denoiser; longform.stitch joins the pose-space variants' output as well")
@@ -285,6 +287,9 @@ class PretrainedLPDM_v1:
         cat = lambda k: torch.cat([torch.as_tensor(e[k]).to(self.device, torch.float32).reshape(1, -1) for e in embs])
         out = self.diffusion_backward(len(chunks), cat(0), cat(1), cat(2))
         poses, trans = longform.stitch(out["poses"], out["trans"], windows, frames, hop_frames, F=self.seq_len)
+        if smooth is not None:
+            from . import smooth as smooth_mod
+            poses, trans = smooth_mod.smooth(poses, trans, frames, **smooth_mod.options(**smooth))
         offs = np.concatenate([[0], np.cumsum(frames)]).astype(int)
         return [{"poses": poses[offs[k]:offs[k + 1]], "trans": trans[offs[k]:offs[k + 1]]} for k in range(len(frames))]
 

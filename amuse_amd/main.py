@@ -32,6 +32,8 @@ floor(30 x seconds) frames - overlapping 10 s windows, sampled independently, cr
 *_motion_smplx.npz, *_preview.png - a contact sheet of the posed SMPL-X mesh, rasterised in HIP (amuse_amd/render.py) - and with --preview-frames
 *_preview/frame_%04d.png.  A flat-shaded preview from a fixed front camera, not the reference's Blender render; the NPZ files keep their bytes.  Off by default.
 With --preview-video [--preview-quality 90] also *_preview.avi: every frame as Motion-JPEG, encoded in HIP (amuse_amd/video.py), with the speech as 16-bit PCM.
+`--fn infer_gesture | edit_gesture --smooth [--smooth-window 9] [--smooth-order 3] [--smooth-hands-window N]` passes every motion through a Savitzky-Golay
+filter on SO(3) before it is written, in a HIP kernel (amuse_amd/smooth.py): this project's own statement of the method.  Off by default.
 """
 from __future__ import annotations
 
@@ -266,6 +268,16 @@ def main(argv=None):
                          "<model_path>/viz/beat_align_<stamp>_E<epoch>.json is written (amuse_amd/beat_align.py).  An extension and this project's own statement of the "
                          "metric: not compared with librosa or with BEAT's code.  Needs the SMPL-X model files (--smplx-models DIR); the NPZ files keep their bytes; "
                          "works with --long-form, --resample, --gpus N")
+    ap.add_argument("--smooth", action="store_true",
+                    help="infer_gesture / edit_gesture: every motion goes through a Savitzky-Golay filter over time before it is written - on SO(3) for the joints (the "
+                         "polynomial fit in the tangent space at the frame being filtered, in a HIP kernel: amuse_amd/smooth.py), on R^3 for the translation; with "
+                         "--long-form after the join, so across the seams as well.  An extension, off by default, and this project's own statement of the method: "
+                         "pinned against no other implementation, except its Euclidean half against scipy.  The NPZ, --motion-metrics, --beat-align and --preview see "
+                         "the smoothed motion; works with --long-form, --resample, --gpus N.  `python -m amuse_amd.smooth` filters the NPZ of an earlier run")
+    ap.add_argument("--smooth-window", type=int, default=None, help="--smooth: frames per window, odd, 3..31 (default 9; with --smooth-order 3 at 30 fps a "
+                                                                     "recollection of common practice, not a measurement)")
+    ap.add_argument("--smooth-order", type=int, default=None, help="--smooth: polynomial order 0..5 (default 3)")
+    ap.add_argument("--smooth-hands-window", type=int, default=None, help="--smooth: another window for the 30 finger joints (default: --smooth-window)")
     args = ap.parse_args(argv)
     fn = args.fn[0]
     if fn not in ("infer_gesture", "edit_gesture", "train_gesture"):
@@ -306,6 +318,18 @@ def main(argv=None):
         if not body.models_present(args.smplx_models):      # checked before anything is loaded or sampled
             raise SystemExit(f"--beat-align: {', '.join(body.SMPLX_FILES.values())} were not all found in {args.smplx_models} (--smplx-models DIR names the "
                              "directory)")
+    smooth_opts = None
+    if not args.smooth and any(v is not None for v in (args.smooth_window, args.smooth_order, args.smooth_hands_window)):
+        raise SystemExit("--smooth-window / --smooth-order / --smooth-hands-window belong to --smooth")
+    if args.smooth:
+        if fn == "train_gesture":
+            raise SystemExit("--smooth belongs to --fn infer_gesture / edit_gesture: it filters the motions those write")
+        from . import smooth as smooth_mod
+        try:               # checked before anything is loaded or sampled
+            smooth_opts = smooth_mod.options(smooth_mod.DEFAULT_WINDOW if args.smooth_window is None else args.smooth_window,
+                                             smooth_mod.DEFAULT_ORDER if args.smooth_order is None else args.smooth_order, args.smooth_hands_window)
+        except ValueError as e:
+            raise SystemExit(f"--smooth: {e}")
     if args.long_form and fn != "infer_gesture":
         raise SystemExit("--long-form belongs to --fn infer_gesture: it joins the windows of one WAV into one motion; the edit tasks work on 10 s clips")
     if args.long_form:
@@ -391,6 +415,8 @@ def main(argv=None):
         tp["test"]["resample"] = True
     if args.long_form:       # (the keys are this path's own; without the switch the configuration is left as it is)
         tp["test"]["long_form"], tp["test"]["hop_frames"] = True, int(args.hop_frames)
+    if smooth_opts is not None:     # (as above: the key is this path's own)
+        tp["test"]["smooth"] = smooth_opts
     metric_models = None
     if args.motion_metrics:  # (the keys are this path's own; without the switch the configuration is left as it is)
         from . import body

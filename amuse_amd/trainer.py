@@ -265,11 +265,15 @@ def preview_audio_of_job(job: Optional[dict], n_files: int) -> list:
     return [None if w is None else ("ld_waveform", w, c) for c in range(int(n_files))]
 
 
-def run_jobs(model, jobs: List[dict], return_latents: bool = False, batched: bool = True, rank: int = 0, world: int = 1) -> List[Optional[dict]]:
+def run_jobs(model, jobs: List[dict], return_latents: bool = False, batched: bool = True, rank: int = 0, world: int = 1,
+             smooth: Optional[dict] = None) -> List[Optional[dict]]:
     """Sample every job; returns, per job and in job order, the reference's `rst` entry
     {"feats": (bsz,300,168), "audio", "info"[, "swap_info"]} (trainer.py:884-890) [+ "latents"].
     A job that carries "long_form": {"frames": L, "hop": h} is ONE waveform cut into bsz overlapping windows (an extension, amuse_amd/longform.py): its rows
     are sampled like any job's - one clip index per window - and joined before they are packed, so it yields feats (1, L, 168).
+    smooth (an extension, amuse_amd/smooth.py; None: nothing changes by a bit): {"window", "order"[, "hands_window"]} - every motion of every job goes through
+    the Savitzky-Golay filter on SO(3) after the long-form join and before it is packed, each clip (or joined motion) as a sequence of its own: whatever reads
+    the result - the NPZ, the metrics, the previews - sees the smoothed motion.  Per job, so a sharded run keeps the single-process bytes.
     batched=True: ONE diffusion_backward per group of jobs that share the set of condition tokens (a missing z_emo /
     z_sty drops a token, denoiser.py:159-171, which changes the kernel's tile shape); clip indices are assigned in job
     order exactly as the sequential calls would have drawn them.  batched=False: the reference's call pattern.
@@ -295,6 +299,9 @@ def run_jobs(model, jobs: List[dict], return_latents: bool = False, batched: boo
         if lf is not None:      # the job's rows are the windows of ONE waveform (amuse_amd/longform.py): joined into one motion of lf["frames"] frames
             from . import longform
             poses, trans = (t[None] for t in longform.stitch(poses, trans, [jobs[j]["bsz"]], [lf["frames"]], lf["hop"], F=poses.shape[1]))
+        if smooth is not None:  # amuse_amd/smooth.py: after the join, so the filter runs across the seams as well
+            from . import smooth as smooth_mod
+            poses, trans = smooth_mod.smooth_batch(poses, trans, smooth)
         r = {"feats": pack_feats(poses, trans), "audio": jobs[j]["audio"], "info": jobs[j]["info"]}
         if jobs[j].get("swap_info") is not None:
             r["swap_info"] = jobs[j]["swap_info"]
@@ -416,6 +423,10 @@ class trainer:
 
     def _embed(self, path, baseline=False):
         return self._embed_all([path], baseline)[0]
+
+    def _smooth_opts(self) -> Optional[dict]:
+        """TRAIN_PARAM.test.smooth (amuse_amd.main --smooth; an extension, amuse_amd/smooth.py): the filter's options, or None - the run as without the switch."""
+        return self.config["TRAIN_PARAM"]["test"].get("smooth") or None
 
     def _resample_on(self) -> bool:
         return bool(self.config["TRAIN_PARAM"]["test"].get("resample", False))
@@ -640,7 +651,7 @@ class trainer:
                 embs = self._embed_all(audios, baseline, needed=[k for k, m in enumerate(mine) if m])
                 jobs = [_job("scott", a.stem, *embs[k], 1, "scott", None, None, None) if mine[k] else _remote_job("scott", a.stem, 1, "scott")
                         for k, a in enumerate(audios)]
-            rst_all = run_jobs(self.model, jobs, batched=self.batched, rank=self.rank, world=self.world)
+            rst_all = run_jobs(self.model, jobs, batched=self.batched, rank=self.rank, world=self.world, smooth=self._smooth_opts())
             video_dump_r = target_path / f"Custom_audios_{self.stamp}_E{ldm_epoch}" / f"rep{rep_i}"
             assert self.viz_type in ["CaMN"], "[LDM EVAL] Invalid viz type: [%s]" % self.viz_type
             for k, sample_dict in enumerate(rst_all):
@@ -692,7 +703,7 @@ class trainer:
                 for name, run_info, jobs in tasks:
                     # (more than one rank: process_loader above ran on every rank - the latents of a take feed jobs of many ranks -
                     # and the sampling is cut here; metrics hold this rank's jobs)
-                    rst = run_jobs(self.model, jobs, batched=self.batched, rank=self.rank, world=self.world)
+                    rst = run_jobs(self.model, jobs, batched=self.batched, rank=self.rank, world=self.world, smooth=self._smooth_opts())
                     self.metrics[name] = [{"actor": j["actor"], "take": j["take"], "swap_info": j["swap_info"] or "",
                                            "rst_info": j["info"], "src_motion": j["src_motion"], "rst_motion": r["feats"],
                                            "audio": j["audio"], "z_con": j["z_con"], "z_emo": j["z_emo"], "z_sty": j["z_sty"]}
@@ -731,7 +742,7 @@ class trainer:
                 embs = self._embed_all(wavs, baseline, needed=need, exchange=exchange)
                 jobs = [_job(actor, wavs[a].stem, embs[a][0], embs[b][1], embs[a][2], 1, info) if m else _remote_job(actor, wavs[a].stem, 1, info)
                         for (info, a, b), m in zip(spec, mine)]
-                rst = run_jobs(self.model, jobs, batched=self.batched, rank=self.rank, world=self.world)   # fresh noise per job, like the two calls
+                rst = run_jobs(self.model, jobs, batched=self.batched, rank=self.rank, world=self.world, smooth=self._smooth_opts())   # fresh noise per job, like the two calls
                 video_dump_r = target_path / f"Custom_audios_{self.stamp}_E{ldm_epoch}" / f"rep{rep_i}"
                 assert self.viz_type in ["CaMN"], "[LDM EVAL] Invalid viz type: [%s]" % self.viz_type
                 for i, sample_dict in enumerate(rst):

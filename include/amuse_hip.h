@@ -681,6 +681,49 @@ int amuse_longform_plan(long long n_samples, int hop_frames, int* windows, int* 
 int amuse_stitch_windows(const float* poses, const float* trans, int S, const int* windows, const int* frames, int F, int hop, const float* blend,
                          float* poses_out, float* trans_out, void* stream);
 
+/* ------------------------------------------------------------------ motion smoothing (csrc/amuse_smooth_host.hpp, amuse_smooth.hip, k_smooth.hip; amuse_amd/smooth.py)
+ * AN EXTENSION, off by default: the reference writes the decoder's rows as they come, frame by frame.  A Savitzky-Golay filter over time, on SO(3) for the
+ * 55 joints and on R^3 for the translation.  It is this project's OWN statement of the method, in the manner of "geometric Savitzky-Golay filtering" on SO(3),
+ * written down from memory: pinned against no other implementation, except the Euclidean half (the bank and the translation) against scipy.signal
+ * (tests/test_smooth_cpu.py); the rotation half is checked against its own float64 restatement (tests/smooth_ref.py) only.  The product's default of a 9-frame
+ * window at order 3 (30 fps) is a RECOLLECTION of common practice, not a measurement.
+ *
+ * Parameters: a half-window m_j in 0..15 for each of the 55 joints and one for the translation (56 values), and ONE polynomial order p in 0..5.  The effective
+ * order at half-window m is p_m = min(p, 2 m).
+ * The bank: for m >= 1, H_m = A (A^T A)^-1 A^T with A[i][d] = (i - m)^d, i = 0 .. 2 m, d = 0 .. p_m - the (2 m + 1) x (2 m + 1) hat matrix of the local
+ * polynomial fit.  Row m is the classic central Savitzky-Golay kernel; the other rows evaluate the SAME fit at the window's other positions and are used at a
+ * sequence's two ends (scipy.signal.savgol_filter(mode="interp")).  Computed on the host in double (through an orthonormal basis of A's columns on the
+ * abscissae scaled to [-1, 1]: the same matrix, without the conditioning of A^T A) and rounded to fp32.
+ * amuse_smooth_banks: host only, no GPU, no context.  Writes H_1 .. H_15 back to back, row-major - 9 + 25 + ... + 961 = 5,455 floats; H_m starts at float
+ * n (4 n^2 + 12 n + 11) / 3, n = m - 1 - for p_m = min(order, 2 m).  AMUSE_EINVAL for an order outside 0..5 or a NULL pointer. */
+#define AMUSE_SMOOTH_MAX_HALF 15
+#define AMUSE_SMOOTH_BANK_FLOATS 5455
+int amuse_smooth_banks(int order, float* banks_out_host);
+/* The filter.  Context-free and stream-ordered; allocates nothing, copies nothing, never synchronises: it can be captured.  The per-sequence offsets and the 56
+ * half-windows travel by value in the kernel arguments, 32 sequences per launch; a call with more sequences takes ceil(S / 32) launches.
+ *   poses dev [sum L_s][55][3] axis-angle, trans dev [sum L_s][3]: S sequences back to back;  frames: HOST int [S], L_s;  half_window: HOST unsigned char [56],
+ *   m_0 .. m_54 of the joints and m_55 of the translation;  banks_dev: dev [5455], what amuse_smooth_banks wrote;  poses_out / trans_out: as the inputs.
+ *   trans and trans_out are NULL together (poses only).
+ * Output frame f of a sequence of L frames, joint j, m = m_j:
+ *   m == 0 or L < 2 m + 1   a BITWISE copy of the input row (angles beyond pi stay as they are)
+ *   otherwise               window start s = clamp(f - m, 0, L - 1 - 2 m), bank row r = f - s; every step in fp32:
+ *       q_k = the unit quaternion of input frame s + k, k = 0 .. 2 m: axis-angle a, t = |a|, (cos(t / 2), a sin(t / 2) / t), with sin(t / 2) / t taken as
+ *             1 / 2 - t^2 / 48 where t < 1e-6 (the decode tail's axis-angle arithmetic, read the other way; the stitch's)
+ *       q_c = q_r, the frame itself;  d_k = conj(q_c) q_k, negated where its real part is < 0
+ *       v_k = log(d_k) as a rotation vector: n = |vec d_k|, v_k = (2 atan2(n, w) / n) vec d_k, the factor taken as 2 where n < 1e-6
+ *       v = sum over k = 0 .. 2 m, in that order, of H_m[r][k] v_k
+ *       out = q_c exp(v) (exp: the axis-angle -> quaternion step above), normalised, negated if its real part is negative, -> axis-angle by the arithmetic of
+ *       the decode tail.  Smoothed rows therefore carry angles <= pi.
+ *   translation (m = m_55): sum over k = 0 .. 2 m, in that order, in fp32, of H_m[r][k] x[s + k], per component; the same copy rule.
+ * This is the polynomial fit in the tangent space AT THE FRAME BEING FILTERED - the only space in which the negative lobes of a Savitzky-Golay kernel mean
+ * anything; nothing is fitted to Euler angles or raw rotation vectors, which is wrong near pi and for large rotations.  A frame's result depends on the
+ * frames of its window alone: not on the sequence's place in the call, nor on the launch or tile it falls in (one code path for interior and edge frames).
+ * Checked before any HIP call, AMUSE_EINVAL otherwise: S >= 1; every L_s >= 1; every half_window[i] <= 15; 56 x sum L_s within an int; poses, frames,
+ * half_window, banks_dev, poses_out non-NULL and the trans pair as stated; no output range may overlap an input range (the filter reads a frame's
+ * neighbours: in place is refused). */
+int amuse_smooth_motion(const float* poses, const float* trans, int S, const int* frames, const unsigned char* half_window, const float* banks_dev,
+                        float* poses_out, float* trans_out, void* stream);
+
 /* ------------------------------------------------------------------ sample-rate conversion (csrc/amuse_resample_host.hpp, amuse_resample.hip, k_resample.hip; amuse_amd/resample.py)
  * AN EXTENSION, off by default: the reference never resamples - scripts/trainer.py:520 drops the file's rate and feeds whatever samples it holds to a 16 kHz fbank.
  * The filter is a band-limited, Hann-windowed sinc in polyphase form.  Its constants (6 zero crossings, roll-off 0.99) are a RECOLLECTION of

@@ -332,14 +332,22 @@ constexpr int gemm_units(int prec, int no, int nk) { return is_op16(prec) ? no *
 // between two registers, so (swap(v, v)[0] op swap(v, v)[1]) is the xor-16 resp. xor-32 butterfly without
 // the LDS round trip of ds_bpermute (__shfl_xor).  Every lane ends with the same value, combined in the
 // same order.
-// (Written as inline asm: ROCm 7.2 hipcc folds __builtin_amdgcn_permlane16_swap(u, u)[1] into [0] - it emits
-// v_add v, v3, v3 - whenever both operands carry the same value.  The s_nop covers the "VALU write ->
-// v_permlane*_swap read" hazard, which hipcc does not pad inside an asm statement.)
+// (ROCm 7.2 hipcc folds __builtin_amdgcn_permlane16_swap(u, u)[1] into [0] - it emits v_add v, v3, v3 - whenever
+// it can see that both operands carry the same value, so the second operand passes through an empty asm statement
+// first: an opaque copy, the v_mov the swap needs anyway.  The builtin, not an asm string with the instruction in
+// it: hipcc then pads the "VALU write -> v_permlane*_swap read" hazard itself (s_nop 1) and nothing else; behind an
+// asm statement it added a second, unneeded s_nop in front of the instruction that reads the result.)
 __device__ __forceinline__ void swap_rows16(float& a, float& b) {
-    asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
+    asm volatile("" : "+v"(b));
+    const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(b), false, false);
+    a = __uint_as_float(r[0]);
+    b = __uint_as_float(r[1]);
 }
 __device__ __forceinline__ void swap_rows32(float& a, float& b) {
-    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
+    asm volatile("" : "+v"(b));
+    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
+    a = __uint_as_float(r[0]);
+    b = __uint_as_float(r[1]);
 }
 __device__ __forceinline__ float allreduce_g_sum(float v) {
     float a = v, b = v;

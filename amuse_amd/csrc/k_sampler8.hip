@@ -366,11 +366,11 @@ __device__ __forceinline__ uint32_t sdrop8_row_bits(const SampleKernelArgs& a, c
 // xb: the residual stream as four packed bf16 operands (every wave); xo: this B wave's two feature tiles in fp32.
 // DROP: train-mode sampling - the A waves draw the attention bits in front of in_proj and their FFN bits in the out_proj combine's
 // waiting time, the B waves all of theirs (both combines, FFN) while the A waves run attention
-template <bool ROLEA, bool PROF, bool DROP>
+template <bool ROLEA, bool PROF, bool DROP, class Early = NoHook>
 __device__ __forceinline__ void encoder_block8(OPV (&xb)[4], f32x4 (&xo)[2], Ring& rg, const float* pv,
                                                const bool (&kvalid)[4], char* lds, int h, int lane, bool next_has_skip,
                                                const uint4* skip_next, Prof8& pf, const SampleKernelArgs& a,
-                                               const SDrop8& dr, int blk) {
+                                               const SDrop8& dr, int blk, Early early = {}) {
     constexpr int P = OP_PREC;
     const int g = lane >> 4, r = lane & 15;
     f32x4 part[kTiles];
@@ -420,6 +420,7 @@ __device__ __forceinline__ void encoder_block8(OPV (&xb)[4], f32x4 (&xo)[2], Rin
     } else {
         // ---- ring empty on entry: fetch this wave's FFN half while the A waves run attention
         ring_issue<kBEarly, kR8, 0>(rg);
+        early();   // work of the reducers' waiting time that no other wave's result feeds (role_loop8: the step's ancestral noise)
         // bits 0..7: dropout1 of tiles 2 h, 2 h + 1; 8..15: dropout2 of the same; 16..31: the FFN's inner dropout
         uint32_t bbits = 0;
         if constexpr (DROP)
@@ -477,6 +478,7 @@ __device__ __forceinline__ void role_loop8(const Args& a, char* smem, int w8, co
         // its own two tiles in fp32
         OPV xb[4];
         f32x4 xo[2] = {splat4(0.f), splat4(0.f)};
+        f32x4 zn[2] = {splat4(0.f), splat4(0.f)};   // B waves: this step's ancestral noise of their two tiles, drawn ahead of the tail (below)
         {
             const Lane8 L = lane_info(a, lane);
             auto assemble = [&](int t) { return assemble_tile(a, L, lane, g, tokrows, ttl, latl, step, t); };
@@ -526,8 +528,23 @@ __device__ __forceinline__ void role_loop8(const Args& a, char* smem, int w8, co
                 for (int c = 0; c < 4; ++c) xb[c] = __builtin_bit_cast(OPV, *reinterpret_cast<const uint4*>(a8_slot(smem, 7, c, lane)));
             }
             stamp8<PROF>(pf);  // 0: block start (after the skip linear, if any)
-            encoder_block8<ROLEA, PROF, DROP>(xb, xo, rg, pvl + blk * kEncPv, kvalid, smem, h, lane, blk >= 4 && blk < kLayers - 1,
-                                              skipbf + (7 - blk) * 4 * 64, pf, a, dr, blk);
+            // The noise of the scheduler update depends on (seed, clip, step, feature) alone, not on the network: Philox4x32-10 (80 integer multiplies in two
+            // serial chains) and Box-Muller for two tiles, which the tail used to walk with the whole workgroup waiting.  The reducers draw it in the LAST
+            // block instead, behind their early fetch, while they wait for the A waves' attention anyway; eight registers carry it to the tail.
+            auto early = [&]() {
+                if constexpr (!ROLEA && !DROP) {   // (the train-mode instantiations have no register to spare: they draw in the tail)
+                    if (blk == kLayers - 1 && !a.no_update && !a.step_noise) {
+                        const Lane8 L = lane_info(a, lane);
+                        if (a.coef[(size_t)step * 8 + 5] != 0.f && L.is_lat) {
+#pragma unroll
+                            for (int i = 0; i < 2; ++i)
+                                zn[i] = counter_normal4(a.seed, a.clip0 + (uint64_t)L.clip, (uint32_t)step, (uint32_t)(4 * (2 * h + i) + L.g), 1u);
+                        }
+                    }
+                }
+            };
+            encoder_block8<ROLEA, PROF, DROP, decltype(early)>(xb, xo, rg, pvl + blk * kEncPv, kvalid, smem, h, lane, blk >= 4 && blk < kLayers - 1,
+                                                               skipbf + (7 - blk) * 4 * 64, pf, a, dr, blk, early);
             if (!ROLEA && blk < 4 && w8 == 4) {
 #pragma unroll
                 for (int p = 0; p < 4; ++p) skipbf[(blk * 4 + p) * 64 + lane] = __builtin_bit_cast(uint4, xb[p]);
@@ -539,40 +556,62 @@ __device__ __forceinline__ void role_loop8(const Args& a, char* smem, int w8, co
         }
         // ---- final LayerNorm (SkipTransformerEncoder.norm) + scheduler.step (diffusers 0.17.1 DDIM / DDPM;
         // amuse_hip.h amuse_schedule) on the B waves' own tiles; the latent lives in LDS
+        // The reducers walk this tail alone on their SIMD (the A waves are parked at the step barrier), so every latency in it is
+        // step time.  The step's coefficients (global memory) are fetched BEFORE the barrier and land while the statistics are computed
+        // and exchanged; behind it the final LayerNorm's parameters and this wave's two latent tiles are read up front, beside the
+        // statistics, and the two tiles go through each stage side by side (eight independent update chains) instead of tile after
+        // tile.  Same operations on the same operands.
         if constexpr (!ROLEA) {
-            const float2 st = row_stats32(xo);
-            if (g == 0) stats[h * 16 + r] = st;
-        }
-        __syncthreads();
-        if constexpr (!ROLEA) {
-            const Lane8 L = lane_info(a, lane);
-            const float2 ms = row_stats_merge<true>(stats, L.r);
             const float* cf = a.coef + (size_t)step * 8;
             const float sb = cf[0], sa = cf[1], c0 = cf[2], cx = cf[3], ce = cf[4], sg = cf[5], clipv = cf[6];
+            const float2 st = row_stats32(xo);
+            if (g == 0) stats[h * 16 + r] = st;
+            __syncthreads();
+            const Lane8 L = lane_info(a, lane);
+            f32x4 ga[2], be[2], l[2];
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                ga[i] = ld4(pv_final + 16 * (2 * h + i) + 4 * L.g);
+                be[i] = ld4(pv_final + kD + 16 * (2 * h + i) + 4 * L.g);
+                l[i] = latl[(2 * h + i) * 64 + L.lane];
+            }
+            const float2 ms = row_stats_merge<true>(stats, L.r);
             const float inv_sa = 1.0f / sa;
+            f32x4 e[2];
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int m = 0; m < 4; ++m) e[i][m] = (xo[i][m] - ms.x) * ms.y * ga[i][m] + be[i][m];
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
                 const int t = 2 * h + i, f = 16 * t + 4 * L.g;
-                const f32x4 ga = ld4(pv_final + f), be = ld4(pv_final + kD + f);
-                f32x4 e;
+                if (tap && step == 0) store_tap_tile(a.tap_out, 10, t, e[i], L.g, L.r);
+                if (a.eps_out && L.is_lat && step == a.T - 1) st4(a.eps_out + (size_t)L.clip * kD + f, e[i]);
+            }
+            if (!a.no_update) {
+                // ancestral noise of the latent rows: counter (global clip, step, feature group) - the values amuse_counter_normal exposes
+                f32x4 z[2] = {zn[0], zn[1]};   // drawn in the last block (above) unless the caller supplies the noise
+                if (sg != 0.f && L.is_lat && (DROP || a.step_noise)) {
 #pragma unroll
-                for (int m = 0; m < 4; ++m) e[m] = (xo[i][m] - ms.x) * ms.y * ga[m] + be[m];
-                if (tap && step == 0) store_tap_tile(a.tap_out, 10, t, e, L.g, L.r);
-                if (a.eps_out && L.is_lat && step == a.T - 1) st4(a.eps_out + (size_t)L.clip * kD + f, e);
-                if (!a.no_update) {
-                    // ancestral noise of the latent rows: counter (global clip, step, feature group) - the values
-                    // amuse_counter_normal exposes.  (Fetched here: as a shared function it changes the register allocation of the kernels without stamps.)
-                    f32x4 z = splat4(0.f);
-                    if (sg != 0.f && L.is_lat)
-                        z = a.step_noise ? ld4(a.step_noise + ((size_t)step * a.B + L.clip) * kD + f)
-                                         : counter_normal4(a.seed, a.clip0 + (uint64_t)L.clip, (uint32_t)step, (uint32_t)(4 * t + L.g), 1u);
-                    f32x4 l = latl[t * 64 + L.lane];
+                    for (int i = 0; i < 2; ++i) {
+                        const int t = 2 * h + i, f = 16 * t + 4 * L.g;
+                        z[i] = a.step_noise ? ld4(a.step_noise + ((size_t)step * a.B + L.clip) * kD + f)
+                                            : counter_normal4(a.seed, a.clip0 + (uint64_t)L.clip, (uint32_t)step, (uint32_t)(4 * t + L.g), 1u);
+                    }
+                }
 #pragma unroll
-                    for (int m = 0; m < 4; ++m) l[m] = sched_update<true>(l[m], e[m], z[m], sb, sa, c0, cx, ce, sg, clipv, inv_sa);
-                    latl[t * 64 + L.lane] = l;
-                    if (a.traj_out && L.is_lat) st4(a.traj_out + ((size_t)step * a.B + L.clip) * kD + f, l);
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int m = 0; m < 4; ++m) l[i][m] = sched_update<true>(l[i][m], e[i][m], z[i][m], sb, sa, c0, cx, ce, sg, clipv, inv_sa);
+#pragma unroll
+                for (int i = 0; i < 2; ++i) {
+                    const int t = 2 * h + i, f = 16 * t + 4 * L.g;
+                    latl[t * 64 + L.lane] = l[i];
+                    if (a.traj_out && L.is_lat) st4(a.traj_out + ((size_t)step * a.B + L.clip) * kD + f, l[i]);
                 }
             }
+        } else {
+            __syncthreads();
         }
         stamp8<PROF>(pf);  // scheduler update done (B waves) / reached the step barrier
         __syncthreads();  // the updated latent is visible to every wave's token assembly

@@ -66,12 +66,22 @@ constexpr int kTT8Off = kLat8Off + kTiles * 64 * 16;           // [2][128] float
 static_assert(kTT8Off + 2 * kD * 4 == kSample8LdsBytes, "LDS layout");
 
 // Issue split of an A wave's 32 units inside the out_proj (C1) and linear2 (C2) combines: N0 before the first barrier
-// (C2 only - there the A waves arrive early), N1 / N2 after the first / second barrier, the rest after the gather.
-// Values from sweeps on MI355X (rounds 1-4, docs/history.md 4.1b); all splits of the same family land within 2 %.
-constexpr int kC1N1 = 12, kC1N2 = 12;
+// (C2 only - there the A waves arrive early), N1 / N2 after the first / second barrier, the rest after the gather (C1: none
+// since round 8 - kALate units go out from the FFN half instead).
+// Values from sweeps on MI355X (rounds 1-4 and 8, docs/history.md 4.1b); all splits of the same family land within 2 %.
+// kC1N2: 12 -> 10 together with kALate = 10 (N1, N2 = 16, 8 / 8, 16 with kALate = 8: 33.06 / 33.43 ms at 256 clips against 33.04 for 12, 12).
+constexpr int kC1N1 = 12, kC1N2 = 10;
+// kC2N0 swept again around the new FFN issue (8 / 12 / 16 / 20 / 24: 34.3 / 33.3 / 32.8 / 33.5 / 34.2 ms): stays.
 constexpr int kC2N0 = 16, kC2N1 = 12;
 // units a B wave issues during the A waves' attention phase; the rest of its 32 follow behind its first FFN MFMAs
-constexpr int kBEarly = 20;
+// (18 / 20 / 21 / 22 / 23 / 24 / 26 with kALate = 8: 33.5 / 33.0 / 33.1 / 32.8 / 32.9 / 33.4 / 33.7 ms)
+constexpr int kBEarly = 22;
+// units of an A wave's FFN half (its last ones, F2b and the tail of F2a) that go out behind ITS first FFN MFMAs instead of behind the out_proj
+// combine's gather.  The reducers leave that gather at the same moment and need their own late units first (F2a reads them ~0.7 k cycles
+// later, the A wave's F2b is the last thing it runs and it waits at the linear2 combine afterwards anyway): issued behind the gather, the A waves'
+// 4 x 8 units sat in the CU's load path in front of them.  Not issuing them at all bounds this at 1.25 ms of 33.5 (tools/probes/ksample8_ffn_pacing);
+// 0 / 4 / 8 / 10: 33.4 / 33.7 / 33.0 / 32.75 ms with kBEarly = 20 (0, 4, 8) and 22 (10).
+constexpr int kALate = 10;
 // VALU instructions scheduled behind each MFMA while one FFN quarter's GELU overlaps the other quarter's GEMM (ffn_half)
 constexpr int kFfnValuPerMfma = 7;
 
@@ -282,10 +292,10 @@ __device__ __forceinline__ void gelu_pair(f32x4 (&hq)[2], uint32_t dbits, float 
 // this wave's two FFN quarters (Q0, Q0 + 1 of head h's slice): linear1 for 2 hidden tiles each -> bias + GELU ->
 // linear2 split-K contribution of those 32 features, software-pipelined by one quarter.  Ring: F1a F1b F2a F2b in
 // slots 0..31, nothing re-armed.
-// LATE8: the last 8 units (F2b) are issued only now, behind the first GEMMs' MFMAs (B waves: their fetch window, the A
-// waves' attention phase, is a little too short for all 32)
+// NLATE: the last NLATE units (slots 32 - NLATE .. 31) are issued only now, behind the first GEMM's MFMAs (B waves: their
+// fetch window, the A waves' attention phase, is a little too short for all 32; A waves: kALate)
 // DROP: site 2 keep bits of the four hidden tiles in dbits (bits 4 k + m: tile k of the half)
-template <int Q0, bool LATE8, bool DROP = false>
+template <int Q0, int NLATE, bool DROP = false>
 __device__ __forceinline__ void ffn_half(f32x4 (&part)[kTiles], const OPV (&xb)[4], Ring& rg, const float* pv,
                                          int h, int g, uint32_t dbits = 0, float dscale = 1.f) {
     constexpr int P = OP_PREC;
@@ -293,7 +303,7 @@ __device__ __forceinline__ void ffn_half(f32x4 (&part)[kTiles], const OPV (&xb)[
     const float* b1 = pv + PV_L1_B + 16 * (kTiles * h + 2 * Q0) + 4 * g;
     f32x4 ha[2] = {ld4(b1), ld4(b1 + 16)}, hb[2] = {ld4(b1 + 32), ld4(b1 + 48)};
     gemm_xb<2, false, 0>(ha, xb, rg);
-    if constexpr (LATE8) ring_issue<32 - kBEarly, kR8, kBEarly>(rg);
+    ring_issue<NLATE, kR8, 32 - NLATE>(rg);
     __builtin_amdgcn_sched_barrier(0);
     // An in-order wave that issues its 8 MFMAs back to back waits out the matrix pipe (16 cycles each) before its
     // first VALU instruction; interleaved 1 : 6 the GELU of one quarter runs in the shadow of the other quarter's
@@ -406,14 +416,14 @@ __device__ __forceinline__ void encoder_block8(OPV (&xb)[4], f32x4 (&xo)[2], Rin
         // ---- out_proj combine (B reduces): meanwhile fetch this wave's FFN half
         if constexpr (DROP) {
             auto hook = [&]() { fbits = sdrop8_ffn_bits<0>(a, dr, blk, h, lane); };
-            combine_publish<0, kC1N1, kC1N2, 32 - kC1N1 - kC1N2, 0, true, decltype(hook)>(part, xb, lds, h, lane, rg, hook);
+            combine_publish<0, kC1N1, kC1N2, 32 - kC1N1 - kC1N2 - kALate, 0, true, decltype(hook)>(part, xb, lds, h, lane, rg, hook);
         } else {
-            combine_publish<0, kC1N1, kC1N2, 32 - kC1N1 - kC1N2, 0>(part, xb, lds, h, lane, rg);
+            combine_publish<0, kC1N1, kC1N2, 32 - kC1N1 - kC1N2 - kALate, 0>(part, xb, lds, h, lane, rg);
         }
         stamp8<PROF>(pf);  // 2: combine 1
 #pragma unroll
         for (int t = 0; t < kTiles; ++t) part[t] = splat4(0.f);
-        ffn_half<0, false, DROP>(part, xb, rg, pv, h, g, fbits, dr.scale);
+        ffn_half<0, kALate, DROP>(part, xb, rg, pv, h, g, fbits, dr.scale);
         stamp8<PROF>(pf);  // 3: FFN
         // ---- linear2 combine (B reduces): meanwhile fetch the next block's attention weights
         combine_publish_c2<kC2N0, kC2N1, 32 - kC2N0 - kC2N1>(part, xb, lds, h, lane, rg, next_has_skip, skip_next);
@@ -431,7 +441,7 @@ __device__ __forceinline__ void encoder_block8(OPV (&xb)[4], f32x4 (&xo)[2], Rin
         for (int t = 0; t < kTiles; ++t) part[t] = splat4(0.f);
         combine_reduce<4, true, true, DROP>(part, xo, xb, pv + PV_OUT_B, pv + PV_LN1_W, pv + PV_LN1_B, lds, h, lane, bbits, dr.scale);
         stamp8<PROF>(pf);
-        ffn_half<2, (kBEarly < 32), DROP>(part, xb, rg, pv, h, g, bbits >> 16, dr.scale);
+        ffn_half<2, 32 - kBEarly, DROP>(part, xb, rg, pv, h, g, bbits >> 16, dr.scale);
         stamp8<PROF>(pf);  // 3: FFN
         if (next_has_skip) ring_issue<8, kR8, 0>(rg);  // the x half of this wave's two output tiles of the next block's skip linear
         combine_reduce<8, true, true, DROP>(part, xo, xb, pv + PV_L2_B, pv + PV_LN2_W, pv + PV_LN2_B, lds, h, lane, bbits >> 8, dr.scale);

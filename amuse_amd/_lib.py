@@ -36,6 +36,7 @@ EXPORTS = [
     "amuse_body_enable_grad", "amuse_body_vertex_loss_grad",
     "amuse_longform_plan", "amuse_stitch_windows",
     "amuse_smooth_banks", "amuse_smooth_motion",
+    "amuse_bvh_layout", "amuse_bvh_format", "amuse_bvh_motion", "amuse_bvh_decode",
     "amuse_resample_plan", "amuse_resampler_create", "amuse_resampler_destroy", "amuse_resample", "amuse_debug_resample_bank",
     "amuse_render_plan", "amuse_renderer_create", "amuse_renderer_destroy", "amuse_render", "amuse_debug_render_raster",
     "amuse_motion_metrics_row", "amuse_motion_metrics",
@@ -239,6 +240,12 @@ def load() -> C.CDLL:
     lib.amuse_smooth_banks.argtypes = [C.c_int, C.POINTER(C.c_float)]
     lib.amuse_smooth_motion.argtypes = [fp, fp, C.c_int, ip, C.POINTER(C.c_ubyte), fp, fp, fp, vp]
     lib.amuse_smooth_banks.restype = lib.amuse_smooth_motion.restype = C.c_int
+    # BVH export (csrc/amuse_bvh.hip): the layout needs no GPU; the formatter, the exporter and the decoder are context-free (frames and dfs are HOST arrays)
+    lib.amuse_bvh_layout.argtypes = [ip, C.c_int, ip]
+    lib.amuse_bvh_format.argtypes = [fp, C.c_longlong, C.c_int, vp, vp, vp]
+    lib.amuse_bvh_motion.argtypes = [fp, fp, fp, C.c_int, ip, ip, C.c_int, C.c_float, C.c_int, fp, vp, vp, vp]
+    lib.amuse_bvh_decode.argtypes = [fp, C.c_int, ip, ip, C.c_int, C.c_float, fp, fp, fp, vp]
+    lib.amuse_bvh_layout.restype = lib.amuse_bvh_format.restype = lib.amuse_bvh_motion.restype = lib.amuse_bvh_decode.restype = C.c_int
     # sample-rate conversion (csrc/amuse_resample.hip): the plan and the bank need no GPU; one resampler per (GPU, rate pair)
     lib.amuse_resample_plan.argtypes = [C.c_int, C.c_int, C.c_longlong, ip, ip, ip, C.POINTER(C.c_longlong)]
     lib.amuse_resampler_create.restype = vp

@@ -34,6 +34,9 @@ floor(30 x seconds) frames - overlapping 10 s windows, sampled independently, cr
 With --preview-video [--preview-quality 90] also *_preview.avi: every frame as Motion-JPEG, encoded in HIP (amuse_amd/video.py), with the speech as 16-bit PCM.
 `--fn infer_gesture | edit_gesture --smooth [--smooth-window 9] [--smooth-order 3] [--smooth-hands-window N]` passes every motion through a Savitzky-Golay
 filter on SO(3) before it is written, in a HIP kernel (amuse_amd/smooth.py): this project's own statement of the method.  Off by default.
+`--fn infer_gesture | edit_gesture --bvh --smplx-models DIR [--bvh-order ZYX] [--bvh-scale 100] [--bvh-unwrap]` writes, beside every *_motion_smplx.npz,
+*_motion.bvh: the same motion as Biovision BVH of the SMPL-X skeleton, its MOTION block - Euler channels, as text - written by HIP kernels (amuse_amd/bvh.py).
+The NPZ files keep their bytes.  Off by default.
 """
 from __future__ import annotations
 
@@ -278,6 +281,15 @@ def main(argv=None):
                                                                      "recollection of common practice, not a measurement)")
     ap.add_argument("--smooth-order", type=int, default=None, help="--smooth: polynomial order 0..5 (default 3)")
     ap.add_argument("--smooth-hands-window", type=int, default=None, help="--smooth: another window for the 30 finger joints (default: --smooth-window)")
+    ap.add_argument("--bvh", action="store_true",
+                    help="infer_gesture / edit_gesture: beside every *_motion_smplx.npz write *_motion.bvh (and *_motion.bvh.json: gender, betas, scale) - what the NPZ "
+                         "holds as Biovision BVH of the SMPL-X skeleton, Euler channels in degrees, the MOTION block converted and formatted in HIP kernels "
+                         "(amuse_amd/bvh.py) - an extension: the SMPL-X skeleton itself, not the reference's Blender retargeting; no BVH importer is pinned.  Needs "
+                         "--smplx-models DIR (the rest joints).  Works with --long-form, --resample, --smooth, --gpus N.  `python -m amuse_amd.bvh` converts the "
+                         "NPZ of an earlier run, and back")
+    ap.add_argument("--bvh-order", default=None, help="--bvh: rotation channel order, one of XYZ XZY YXZ YZX ZXY ZYX (default ZYX)")
+    ap.add_argument("--bvh-scale", type=float, default=None, help="--bvh: length units per metre (default 100: centimetres)")
+    ap.add_argument("--bvh-unwrap", action="store_true", help="--bvh: continuous curves - each frame takes the Euler triple nearest the frame before")
     args = ap.parse_args(argv)
     fn = args.fn[0]
     if fn not in ("infer_gesture", "edit_gesture", "train_gesture"):
@@ -330,6 +342,23 @@ def main(argv=None):
                                              smooth_mod.DEFAULT_ORDER if args.smooth_order is None else args.smooth_order, args.smooth_hands_window)
         except ValueError as e:
             raise SystemExit(f"--smooth: {e}")
+    bvh_opts = None
+    if not args.bvh and (args.bvh_order is not None or args.bvh_scale is not None or args.bvh_unwrap):
+        raise SystemExit("--bvh-order / --bvh-scale / --bvh-unwrap belong to --bvh")
+    if args.bvh:
+        if fn == "train_gesture":
+            raise SystemExit("--bvh belongs to --fn infer_gesture / edit_gesture: it converts the NPZ files those write")
+        if not args.smplx_models:
+            raise SystemExit("--bvh needs --smplx-models DIR: the hierarchy's offsets are the rest joints of the SMPL-X body models")
+        from . import body
+        from . import bvh as bvh_mod
+        if not body.models_present(args.smplx_models):      # checked before anything is loaded or sampled
+            raise SystemExit(f"--bvh: {', '.join(body.SMPLX_FILES.values())} were not all found in {args.smplx_models} (--smplx-models DIR names the directory)")
+        try:
+            bvh_opts = bvh_mod.options(bvh_mod.DEFAULT_ORDER if args.bvh_order is None else args.bvh_order,
+                                       bvh_mod.DEFAULT_SCALE if args.bvh_scale is None else args.bvh_scale, args.bvh_unwrap)
+        except ValueError as e:
+            raise SystemExit(f"--bvh: {e}")
     if args.long_form and fn != "infer_gesture":
         raise SystemExit("--long-form belongs to --fn infer_gesture: it joins the windows of one WAV into one motion; the edit tasks work on 10 s clips")
     if args.long_form:
@@ -450,6 +479,14 @@ def main(argv=None):
             pv.close()
         n_avi = sum(1 for f in drawn if Path(f).suffix == ".avi")
         print(f"[amuse_amd] --preview: {len(drawn) - n_avi} PNG files" + (f" and {n_avi} AVI files" if n_avi else "") + f" beside {len(written)} NPZ files")
+    if bvh_opts is not None:            # this rank's own files, in one batch: what the NPZ holds (after the lower-body freeze, the stitch and the smoothing)
+        from . import body
+        from . import bvh as bvh_mod
+        try:
+            n_bvh = len(bvh_mod.motion_to_bvh_batch(written, body.load_models(args.smplx_models), device=device, **bvh_opts))
+        except bvh_mod.BvhRangeError as e:
+            raise SystemExit(f"--bvh: {e}")
+        print(f"[amuse_amd] --bvh: {n_bvh} BVH files beside {len(written)} NPZ files")
     print(f"AMUSE: ({fn}) completed in: {(time.time() - tic) / 3600} hrs; {len(written)} NPZ files" + (f" on rank {rank} of {world}" if world > 1 else ""))
     if world > 1 and os.environ.get("AMUSE_MANIFEST_DIR"):      # the launcher collects what the ranks wrote
         Path(os.environ["AMUSE_MANIFEST_DIR"], f"rank{rank}.json").write_text(json.dumps([str(p) for p in written]))

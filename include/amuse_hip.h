@@ -724,6 +724,55 @@ int amuse_smooth_banks(int order, float* banks_out_host);
 int amuse_smooth_motion(const float* poses, const float* trans, int S, const int* frames, const unsigned char* half_window, const float* banks_dev,
                         float* poses_out, float* trans_out, void* stream);
 
+/* ------------------------------------------------------------------ BVH export (csrc/amuse_bvh_host.hpp, amuse_bvh.hip, k_bvh.hip; amuse_amd/bvh.py)
+ * AN EXTENSION, off by default: the reference retargets its NPZ output to BVH through Blender; this writes the SMPL-X skeleton itself as BVH - the hierarchy on
+ * the host, the MOTION block (Euler channels in degrees, as text) on the GPU.  No BVH importer is pinned anywhere in this project: the files are checked against
+ * the format's grammar through the project's own reader and their numbers against scipy (tests/test_gpu_bvh.py).
+ *
+ * A MOTION row is 168 numbers: the root's three position channels, then three rotation channels per joint, joints in the DEPTH-FIRST order of the parent list
+ * with children in ascending index.  Every number is the 11 characters of C's "%11.6f" and one separator byte - a space, '\n' after a row's last number - so a
+ * row is 168 x 12 = 2,016 bytes and a clip of F frames is F x 2,016 bytes at a known offset: there is no size pass.
+ *
+ * amuse_bvh_layout: host only, no GPU, no context.  dfs_out[c] = the joint of column c for parents[0] = -1, 0 <= parents[j] < j.  AMUSE_EINVAL otherwise, for
+ * n outside 1..65536 and for NULL pointers. */
+#define AMUSE_BVH_COLS 168
+#define AMUSE_BVH_FIELD 12
+enum { AMUSE_BVH_XYZ = 0, AMUSE_BVH_XZY = 1, AMUSE_BVH_YXZ = 2, AMUSE_BVH_YZX = 3, AMUSE_BVH_ZXY = 4, AMUSE_BVH_ZYX = 5 };
+int amuse_bvh_layout(const int* parents, int n, int* dfs_out);
+/* The formatter on its own.  Context-free and stream-ordered; allocates nothing, copies nothing, never synchronises: it can be captured.
+ *   values dev fp32 [n];  text_out dev bytes [12 n], 4-byte aligned;  status dev int [1].
+ * Field i is exactly C's "%11.6f" of values[i] - round-half-even at the sixth decimal, "-0.000000" for -0 and for negatives that round to zero - followed by
+ * '\n' where i % per_row == per_row - 1 and by a space elsewhere.  (An fp32 times 1e6 is exact in double, so rint(double(x) * 1e6) is the integer printf prints.)
+ * A value that does not fit - |x| rounding to 1000 or more, NaN, infinity - has its 11 characters filled with '#' and sets *status to 1 by a plain store;
+ * status is never cleared here.  No byte outside [0, 12 n) is written.
+ * AMUSE_EINVAL before any HIP call: n < 1, per_row < 1, a NULL pointer, text_out not 4-byte aligned. */
+int amuse_bvh_format(const float* values, long long n, int per_row, void* text_out, int* status, void* stream);
+/* The exporter.  Context-free, stream-ordered, capturable; the per-sequence offsets and the column order travel by value in the kernel arguments, 32 sequences
+ * per launch.
+ *   poses dev [rows][55][3] axis-angle, trans dev [rows][3] or NULL (zero): S sequences back to back, rows = sum F_s;  root_rest dev [S][3]: J_rest[0] of each
+ *   sequence's body;  frames HOST int [S], every F_s >= 1;  dfs HOST int [55]: what amuse_bvh_layout wrote;  order: AMUSE_BVH_*, channel list "A B C" meaning
+ *   R = R_A R_B R_C;  scale > 0;  euler_out dev fp32 [rows][168] or NULL;  text_out dev bytes [rows][2016] or NULL, 4-byte aligned;  status dev int [S],
+ *   cleared by the caller.
+ * Columns 0..2 of a row: (root_rest[s] + trans) x scale.  Columns 3 + 3 c ..: joint dfs[c], in fp32 and without a rotation matrix:
+ *   unit quaternion (w, q): t = |a|, w = cos(t / 2), q = a sin(t / 2) / t with the factor taken as 1 / 2 - t^2 / 48 where t < 1e-3
+ *   for channel axes (i, j, k) and e = the sign of the permutation (k, j, i):  a = w - q_j, b = q_k + e q_i, c = q_j + w, d = e q_i - q_k
+ *   middle angle 2 atan2(hypot(c, d), hypot(a, b)) - pi / 2;  hs = atan2(b, a), hd = atan2(d, c);  first angle e (hs + hd), third hs - hd, both wrapped
+ *   into [-180, 180) degrees.  At exact gimbal lock the pair that vanishes takes the other's angle, so the third channel is 0.
+ * This keeps the ROTATION accurate where the individual angles are ill-conditioned.
+ * unwrap != 0: a second launch walks each (sequence, joint) in frame order; at frame t > 0 it weighs (alpha, beta, gamma) against (alpha + 180, 180 - beta,
+ * gamma + 180) - the same rotation - each channel moved by the multiple of 360 nearest to the value emitted at t - 1, and keeps the one with the smaller sum of
+ * absolute channel differences (ties: the first).  Frame 0 keeps its principal values.
+ * euler_out holds exactly the fp32 values that are formatted, and the text is amuse_bvh_format of them.  A sequence's bytes depend on its own rows alone.
+ * A sequence with a value that does not fit the field gets status[s] = 1 (and '#' fields).
+ * AMUSE_EINVAL before any HIP call: S < 1, an F_s outside 1..(INT_MAX - 256) / 56, an order outside 0..5, dfs not a permutation of 0..54, scale not positive
+ * and finite, poses / root_rest / frames / dfs / status NULL, euler_out and text_out both NULL, text_out not 4-byte aligned. */
+int amuse_bvh_motion(const float* poses, const float* trans, const float* root_rest, int S, const int* frames, const int* dfs, int order, float scale, int unwrap,
+                     float* euler_out, void* text_out, int* status, void* stream);
+/* The inverse.  channels dev fp32 [rows][168] as euler_out above;  poses_out dev [rows][55][3], trans_out dev [rows][3].  Degrees -> three axis quaternions
+ * multiplied in channel order -> axis-angle by the decode tail's own arithmetic, angle <= pi;  trans = position / scale - root_rest[s].  Same checks. */
+int amuse_bvh_decode(const float* channels, int S, const int* frames, const int* dfs, int order, float scale, const float* root_rest, float* poses_out,
+                     float* trans_out, void* stream);
+
 /* ------------------------------------------------------------------ sample-rate conversion (csrc/amuse_resample_host.hpp, amuse_resample.hip, k_resample.hip; amuse_amd/resample.py)
  * AN EXTENSION, off by default: the reference never resamples - scripts/trainer.py:520 drops the file's rate and feeds whatever samples it holds to a 16 kHz fbank.
  * The filter is a band-limited, Hann-windowed sinc in polyphase form.  Its constants (6 zero crossings, roll-off 0.99) are a RECOLLECTION of

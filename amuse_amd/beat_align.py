@@ -14,10 +14,13 @@ from __future__ import annotations
 
 import ctypes as C
 import json
+from contextlib import closing
 from pathlib import Path
 from typing import Dict, Optional, Sequence
 
 import numpy as np
+
+from .motion_metrics import _plain      # (JSON-ready values: one definition for both reports)
 
 NJ = 55
 FPS = 30.0                   # the NPZ's mocap_frame_rate (npz_writer.smplx_npz_fields)
@@ -247,14 +250,6 @@ class BeatAlign:
         return out
 
 
-def _plain(v):
-    if isinstance(v, np.ndarray):
-        return [_plain(x) for x in v.tolist()]
-    if isinstance(v, float) and not np.isfinite(v):
-        return None
-    return v
-
-
 def clip_seconds(n_samples: int, frames: int, fps: float = FPS):
     """(seconds of audio the onsets were taken over, seconds of motion the beats were taken over): the audio is cut at the motion's end, as the onsets are"""
     motion_s = max(frames - 1, 0) / fps
@@ -278,28 +273,20 @@ def score_pairs(pairs, models: dict, device="cuda:0", params: Optional[dict] = N
     scored against its WAV.  load_wave(path) -> float32 [n] at 16 kHz replaces the default reader (the trainer passes the front-end's).  Needs no checkpoint.
     -> {"per_file": {npz: values}, "overall": values, "state": the additive state}"""
     import torch
-    from . import body
+    from . import body, motion_file
     par = dict(default_params(), **(params or {}))
     fps = float(par["fps"])
-    beat = BeatEngine(device)
-    engines: Dict[str, body.BodyEngine] = {}
     total, per_file = BeatAlign(), {}
-    try:
+    with closing(BeatEngine(device)) as beat, closing(body.Poser(models, device)) as poser:
         for npz, wav in pairs:
-            with np.load(npz, allow_pickle=False) as z:
-                g = str(z["gender"])
-                if g not in models:
-                    raise SystemExit(f"beat_align: {npz} names the gender '{g}'; the body models are {', '.join(models)}")
-                poses, trans, betas = np.asarray(z["poses"], np.float32), np.asarray(z["trans"], np.float32), np.asarray(z["betas"], np.float32)
-            F = int(poses.shape[0])
+            m = motion_file.read(npz)
+            if m.gender not in models:
+                raise SystemExit(f"beat_align: {npz} names the gender '{m.gender}'; the body models are {', '.join(models)}")
+            F = int(m.poses.shape[0])
             if F < 2:
                 raise SystemExit(f"beat_align: {npz} holds {F} frames; a speed needs two")
-            if g not in engines:
-                engines[g] = body.BodyEngine(device, models[g])
-            eng, nb = engines[g], models[g].n_betas
-            eng.set_subjects(np.pad(betas.reshape(-1)[:nb], (0, max(0, nb - betas.size)))[None])
-            J = eng.joints(torch.from_numpy(poses.reshape(1, F, NJ, 3)).to(device).contiguous(), torch.from_numpy(trans.reshape(1, F, 3)).to(device).contiguous(),
-                           torch.zeros(1, dtype=torch.int32, device=device), "aa")
+            eng, rot, tr = poser.pose(m)
+            J = eng.joints(rot, tr)
             wave = load_wave(wav) if load_wave is not None else load_wave_16k(wav, device)
             wave = torch.as_tensor(wave).reshape(-1).to(device, torch.float32)
             n = int(wave.numel())
@@ -314,10 +301,6 @@ def score_pairs(pairs, models: dict, device="cuda:0", params: Optional[dict] = N
             total.merge(one)
             per_file[str(npz)] = {"wav": str(wav), "samples": n, "frames": F,
                                   **{k: _plain(v) for k, v in one.compute(joints).items() if not k.endswith("_per_joint")}}
-    finally:
-        beat.close()
-        for e in engines.values():
-            e.close()
     return {"per_file": per_file, "overall": {k: _plain(v) for k, v in total.compute(joints).items()}, "state": total.state(), "params": par}
 
 
@@ -355,9 +338,7 @@ def main(argv=None):
     if min(args.joints) < 0 or max(args.joints) >= NJ:
         raise SystemExit(f"beat_align: --joints are indices in 0..{NJ - 1}")
     from . import body
-    if not body.models_present(args.smplx_models):
-        raise SystemExit(f"beat_align: {', '.join(body.SMPLX_FILES.values())} were not all found in {args.smplx_models}")
-    rep = score_pairs(pairs, body.load_models(args.smplx_models), args.device, {"sigma_s": args.sigma} if args.sigma is not None else None, args.joints)
+    rep = score_pairs(pairs, body.require_models(args.smplx_models, "beat_align: "), args.device, {"sigma_s": args.sigma} if args.sigma is not None else None, args.joints)
     rep.pop("state")
     rep["note"] = "this project's own statement of beat alignment; not compared with librosa or with BEAT's code"
     for name, v in rep["per_file"].items():

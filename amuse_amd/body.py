@@ -321,6 +321,48 @@ def load_models(directory, num_betas: int = 300) -> dict:
     return {g: BodyModel.from_npz(Path(directory) / f, num_betas) for g, f in SMPLX_FILES.items()}
 
 
+def require_models(directory, who: str = "", hint: str = "(--smplx-models DIR names the directory)", faces: bool = False, load: bool = True) -> Optional[dict]:
+    """What every command line calls: the three files are in `directory` - else SystemExit names them and the directory, `who` ("--bvh: ") in front and `hint`
+    behind - and are loaded (load=False: checked only); faces: every model must carry its triangles (the preview renderer's need)."""
+    if not models_present(directory):
+        raise SystemExit(f"{who}{', '.join(SMPLX_FILES.values())} were not all found in {directory} {hint}")
+    models = load_models(directory) if load else None
+    for g, m in (models or {}).items():
+        if faces and m.faces is None:
+            raise SystemExit(f"{who}{Path(directory) / SMPLX_FILES[g]} lacks the key 'f' (the mesh's triangles, [T][3]): without them there is nothing to rasterise")
+    return models
+
+
+def fit_betas(betas, n_betas: int) -> np.ndarray:
+    """a motion file's betas as a model takes them: float32 [n_betas], cut to the model's count, zero-padded if the file holds fewer"""
+    b = np.asarray(betas, dtype=np.float32).reshape(-1)[:n_betas]
+    return np.pad(b, (0, n_betas - b.size))
+
+
+class Poser:
+    """What a module that poses motion files owns: the BodyEngine of every gender over `models` ({gender: BodyModel}), created on first use, closed by close()"""
+
+    def __init__(self, models: dict, device="cuda:0"):
+        self.models, self.device, self.engines = models, device, {}
+
+    def engine(self, gender: str) -> BodyEngine:
+        if gender not in self.engines:
+            self.engines[gender] = BodyEngine(self.device, self.models[gender])
+        return self.engines[gender]
+
+    def pose(self, motion):
+        """a motion_file.read record -> (its gender's engine with the file's betas set as subject 0, rot [1, F, 55, 3], trans [1, F, 3] on the device), ready for
+        engine.joints(rot, trans) / .vertices(rot, trans).  A gender without a model is a KeyError: whether to refuse or to fall back is the caller's."""
+        eng = self.engine(motion.gender)
+        eng.set_subjects(fit_betas(motion.betas, eng.model.n_betas)[None])
+        return eng, torch.from_numpy(motion.poses[None]).to(eng.device), torch.from_numpy(motion.trans[None]).to(eng.device)
+
+    def close(self) -> None:
+        for e in self.engines.values():
+            e.close()
+        self.engines = {}
+
+
 class BodyLosses:
     """The `body` of train_gesture.LatentPriorLosses: the reference's _get_vertices + the two SmoothL1 terms (latent_losses.py:135-146,173-250) as VALUES (the
     reference computes them under no_grad).  Dataset version "v0": every clip goes through the male or the female model by its actor's gender; "v1": all through

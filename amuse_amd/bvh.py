@@ -25,13 +25,12 @@ from __future__ import annotations
 import argparse
 import ctypes as C
 import json
-import os
 from pathlib import Path
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 
-from . import _lib
+from . import _lib, motion_file
 
 NJ, COLS, FIELD = 55, 168, 12
 ROW_BYTES = COLS * FIELD
@@ -57,9 +56,9 @@ def _order_index(order: str) -> int:
     return ORDERS.index(o)
 
 
-def options(order: str = DEFAULT_ORDER, scale: float = DEFAULT_SCALE, unwrap: bool = False) -> dict:
-    """The checked per-run options."""
-    scale = float(scale)
+def options(order: Optional[str] = None, scale: Optional[float] = None, unwrap: bool = False) -> dict:
+    """The checked per-run options; None: the default."""
+    order, scale = DEFAULT_ORDER if order is None else order, float(DEFAULT_SCALE if scale is None else scale)
     if not (np.isfinite(scale) and scale > 0):
         raise ValueError(f"scale {scale}: positive and finite")
     return {"order": ORDERS[_order_index(order)], "scale": scale, "unwrap": bool(unwrap)}
@@ -122,14 +121,11 @@ def sidecar_path(bvh_path) -> Path:
 
 
 def write_bvh(path, header: str, block: bytes, meta: Optional[dict] = None) -> Path:
-    """header ++ block -> path, through a .part file and os.replace, as npz_writer.write_sample writes; meta -> path + ".json" the same way."""
+    """header ++ block -> path, atomically, as every motion file is written; meta -> path + ".json" the same way."""
     path = Path(path)
-    path.parent.mkdir(parents=True, exist_ok=True)
     for dst, data in ((path, header.encode("ascii") + bytes(block)),) + (((sidecar_path(path), json.dumps(meta).encode("ascii")),) if meta is not None else ()):
-        tmp = dst.with_name(dst.name + ".part")
-        with open(tmp, "wb") as fh:
+        with motion_file.atomic(dst) as fh:
             fh.write(data)
-        os.replace(tmp, dst)
     return path
 
 
@@ -295,30 +291,12 @@ def decode(channels, frames: Sequence[int], dfs, order: str, scale: float, root_
 # ------------------------------------------------------------------ files
 def bvh_path(npz_path, out_dir=None) -> Path:
     """*_motion_smplx.npz -> *_motion.bvh, beside it or in out_dir"""
-    src = Path(npz_path)
-    name = src.name
-    stem = name[:-len("_smplx.npz")] if name.endswith("_motion_smplx.npz") else src.stem + "_motion"
-    return (Path(out_dir) if out_dir is not None else src.parent) / f"{stem}.bvh"
+    return motion_file.sibling(npz_path, "_motion.bvh", out_dir)
 
 
 def npz_path_of(bvh_file, out_dir=None) -> Path:
     """*_motion.bvh -> *_from_bvh_motion_smplx.npz (never the name of the NPZ the BVH was made from)"""
-    src = Path(bvh_file)
-    stem = src.name[:-len("_motion.bvh")] if src.name.endswith("_motion.bvh") else src.stem
-    return (Path(out_dir) if out_dir is not None else src.parent) / f"{stem}_from_bvh_motion_smplx.npz"
-
-
-def _load_npz(p: Path) -> dict:
-    with np.load(p) as z:
-        poses = np.asarray(z["poses"], dtype=np.float32)
-        poses = poses.reshape(poses.shape[0], -1, 3)
-        if poses.shape[1] != NJ or poses.shape[0] < 1:
-            raise ValueError(f"{p}: poses hold {poses.shape[0]} frames of {poses.shape[1]} joints, not SMPL-X's 55")
-        F = poses.shape[0]
-        trans = np.asarray(z["trans"], dtype=np.float32).reshape(F, 3) if "trans" in z.files else np.zeros((F, 3), np.float32)
-        return {"poses": poses, "trans": trans, "gender": str(z["gender"]) if "gender" in z.files else "neutral",
-                "betas": np.asarray(z["betas"], dtype=np.float64).reshape(-1) if "betas" in z.files else np.zeros(300),
-                "fps": float(z["mocap_frame_rate"]) if "mocap_frame_rate" in z.files else 30.0}
+    return motion_file.sibling(bvh_file, "_from_bvh_motion_smplx.npz", out_dir, strip="_motion.bvh")
 
 
 def motion_to_bvh_batch(npz_paths: Sequence, models: dict, out_dir=None, order: str = DEFAULT_ORDER, scale: float = DEFAULT_SCALE, unwrap: bool = False,
@@ -335,39 +313,36 @@ def motion_to_bvh_batch(npz_paths: Sequence, models: dict, out_dir=None, order: 
     i = 0
     while i < len(paths):
         group, rows = [], 0
-        while i < len(paths) and (not group or rows + group[-1]["poses"].shape[0] <= MAX_ROWS_PER_CALL):
-            d = _load_npz(paths[i])
-            if d["gender"] not in models:
-                raise ValueError(f"{paths[i]}: no SMPL-X model for gender {d['gender']!r} among {sorted(models)}")
-            key = (d["gender"], d["betas"].tobytes())
+        while i < len(paths) and (not group or rows + group[-1][0].poses.shape[0] <= MAX_ROWS_PER_CALL):
+            m = motion_file.read(paths[i])
+            if m.gender not in models:
+                raise ValueError(f"{paths[i]}: no SMPL-X model for gender {m.gender!r} among {sorted(models)}")
+            key = (m.gender, m.betas.tobytes())
             if key not in rest:
-                rest[key] = rest_joints(models[d["gender"]], d["betas"])
-            if d["gender"] not in dfs_of:
-                dfs_of[d["gender"]] = layout(models[d["gender"]].parents)
-            d["J"], d["src"] = rest[key], paths[i]
-            rows += d["poses"].shape[0]
-            group.append(d)
+                rest[key] = rest_joints(models[m.gender], m.betas)
+            if m.gender not in dfs_of:
+                dfs_of[m.gender] = layout(models[m.gender].parents)
+            rows += m.poses.shape[0]
+            group.append((m, rest[key]))
             i += 1
         # one call per parent list (the SMPL-X models of the three genders share theirs: one call)
         by_dfs: Dict[bytes, list] = {}
-        for d in group:
-            by_dfs.setdefault(dfs_of[d["gender"]].tobytes(), []).append(d)
+        for m, J in group:
+            by_dfs.setdefault(dfs_of[m.gender].tobytes(), []).append((m, J))
         for part in by_dfs.values():
-            g = part[0]["gender"]
-            frames = [d["poses"].shape[0] for d in part]
-            _, text, status = motion_channels(torch.from_numpy(np.concatenate([d["poses"] for d in part])).to(device),
-                                              torch.from_numpy(np.concatenate([d["trans"] for d in part])).to(device),
-                                              torch.from_numpy(np.stack([d["J"][0] for d in part]).astype(np.float32)), frames, dfs_of[g], **o)
+            frames = [m.poses.shape[0] for m, _ in part]
+            _, text, status = motion_channels(torch.from_numpy(np.concatenate([m.poses for m, _ in part])).to(device),
+                                              torch.from_numpy(np.concatenate([m.trans for m, _ in part])).to(device),
+                                              torch.from_numpy(np.stack([J[0] for _, J in part]).astype(np.float32)), frames, dfs_of[part[0][0].gender], **o)
             text, status = text.cpu().numpy(), status.cpu().numpy()
             r0 = 0
-            for d, F, st in zip(part, frames, status):
+            for (m, J), F, st in zip(part, frames, status):
                 if st:
-                    raise BvhRangeError(f"{d['src']}: a channel of this motion does not fit the BVH field (|value| >= 1000 at six decimals): lower --bvh-scale"
+                    raise BvhRangeError(f"{m.path}: a channel of this motion does not fit the BVH field (|value| >= 1000 at six decimals): lower --bvh-scale"
                                         + (", or drop --bvh-unwrap (an unwrapped curve may wind past 1000 degrees)" if o["unwrap"] else ""))
-                parents = models[d["gender"]].parents
-                meta = {"gender": d["gender"], "betas": [float(b) for b in d["betas"]], "scale": o["scale"], "order": o["order"],
-                        "root_rest": [float(x) for x in d["J"][0]], "mocap_frame_rate": d["fps"]}
-                out.append(write_bvh(bvh_path(d["src"], out_dir), header_text(parents, d["J"], F, d["fps"], o["order"], o["scale"]),
+                meta = {"gender": m.gender, "betas": [float(b) for b in m.betas], "scale": o["scale"], "order": o["order"],
+                        "root_rest": [float(x) for x in J[0]], "mocap_frame_rate": m.fps}
+                out.append(write_bvh(bvh_path(m.path, out_dir), header_text(models[m.gender].parents, J, F, m.fps, o["order"], o["scale"]),
                                      text[r0 * ROW_BYTES:(r0 + F) * ROW_BYTES].tobytes(), meta))
                 r0 += F
     return out
@@ -384,15 +359,9 @@ def bvh_to_motion(bvh_files: Sequence, out_dir=None, device="cuda", scale: Optio
         sc = float(m.get("scale", DEFAULT_SCALE if scale is None else scale))
         poses, trans = decode(torch.from_numpy(b["channels"].astype(np.float32)).to(device), [b["frames"]], b["dfs"], b["order"], sc,
                               np.asarray(m.get("root_rest", [0.0, 0.0, 0.0]), dtype=np.float32)[None])
-        dst = npz_path_of(f, out_dir)
-        dst.parent.mkdir(parents=True, exist_ok=True)
-        tmp = dst.with_name(dst.name + ".part")
-        with open(tmp, "wb") as fh:
-            np.savez(fh, poses=poses.cpu().numpy(), trans=trans.cpu().numpy().astype(np.float64), gender=np.array(m.get("gender", "neutral"), dtype="<U7"),
-                     betas=np.asarray(m.get("betas", np.zeros(300)), dtype=np.float64),
-                     mocap_frame_rate=np.array(m.get("mocap_frame_rate", round(1.0 / b["frame_time"], 2)), dtype="float64"))
-        os.replace(tmp, dst)
-        out.append(dst)
+        out.append(motion_file.save(npz_path_of(f, out_dir), poses=poses.cpu().numpy(), trans=trans.cpu().numpy().astype(np.float64),
+                                    gender=np.array(m.get("gender", "neutral"), dtype="<U7"), betas=np.asarray(m.get("betas", np.zeros(300)), dtype=np.float64),
+                                    mocap_frame_rate=np.array(m.get("mocap_frame_rate", round(1.0 / b["frame_time"], 2)), dtype="float64")))
     return out
 
 
@@ -415,7 +384,7 @@ def parse_args(argv=None):
         if not args.smplx_models:
             ap.error("--smplx-models DIR is needed: the hierarchy's offsets are the rest joints of the SMPL-X body models")
         try:
-            options(DEFAULT_ORDER if args.order is None else args.order, DEFAULT_SCALE if args.scale is None else args.scale)
+            options(args.order, args.scale)
         except ValueError as e:
             ap.error(str(e))
     return args
@@ -430,11 +399,8 @@ def main(argv=None) -> List[Path]:
         written = bvh_to_motion(args.files, args.out_dir, args.device, args.scale)
     else:
         from . import body
-        if not body.models_present(args.smplx_models):
-            raise SystemExit(f"{', '.join(body.SMPLX_FILES.values())} were not all found in {args.smplx_models} (--smplx-models DIR names the directory)")
         try:
-            written = motion_to_bvh_batch(args.files, body.load_models(args.smplx_models), args.out_dir, DEFAULT_ORDER if args.order is None else args.order,
-                                          DEFAULT_SCALE if args.scale is None else args.scale, args.unwrap, args.device)
+            written = motion_to_bvh_batch(args.files, body.require_models(args.smplx_models), args.out_dir, args.order, args.scale, args.unwrap, args.device)
         except BvhRangeError as e:
             raise SystemExit(str(e).replace("--bvh-scale", "--scale").replace("--bvh-unwrap", "--unwrap"))
     for p in written:

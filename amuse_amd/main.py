@@ -45,6 +45,7 @@ import json
 import os
 import random
 import time
+from contextlib import closing
 from pathlib import Path
 
 import numpy as np
@@ -111,12 +112,10 @@ def train_gesture_entry(args, dirname: Path, config: dict):
     if ld.get("vtex_displacement", False) and not args.skip_vtex_loss:
         from . import body
         smplx_dir = Path(args.smplx_models) if args.smplx_models else dirname / "body_models" / "codebase" / "models" / "smplx"
-        if not body.models_present(smplx_dir):
-            raise SystemExit("train_gesture: TRAIN_PARAM.latent_diffusion.vtex_displacement is True (scripts/overrides/train_gesture.yaml:25): the "
-                             "rec / gen vertex-displacement loss terms need the licensed SMPL-X body models (latent_losses.py:173-250), and "
-                             f"{', '.join(body.SMPLX_FILES.values())} were not all found in {smplx_dir} (--smplx-models DIR names another directory).  "
-                             "Pass --skip-vtex-loss to train WITHOUT those two terms (checkpoint names then read vtexR0.0000 / "
-                             "vtexG0.0000), or set vtex_displacement: False")
+        body.require_models(smplx_dir, "train_gesture: TRAIN_PARAM.latent_diffusion.vtex_displacement is True (scripts/overrides/train_gesture.yaml:25): the "
+                            "rec / gen vertex-displacement loss terms need the licensed SMPL-X body models (latent_losses.py:173-250), and ",
+                            "(--smplx-models DIR names another directory).  Pass --skip-vtex-loss to train WITHOUT those two terms (checkpoint names then read "
+                            "vtexR0.0000 / vtexG0.0000), or set vtex_displacement: False", load=False)
     elif ld.get("vtex_displacement", False):
         print("[LPDM-T] WARNING: vtex_displacement is True in the configuration but --skip-vtex-loss drops both vertex-displacement terms", flush=True)
     ldm_cfg = config.get("_ldm_cfg")
@@ -194,7 +193,7 @@ def _launch_ranks(args, argv, dirname: Path):
     return written
 
 
-def main(argv=None):
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description="AMUSE (MI355X path)")
     ap.add_argument("--fn", nargs="*", required=True, help="infer_gesture, edit_gesture, train_gesture")
     ap.add_argument("--cfg", default=None, help="config file (default <root>/configs/base_new.json)")
@@ -290,7 +289,19 @@ def main(argv=None):
     ap.add_argument("--bvh-order", default=None, help="--bvh: rotation channel order, one of XYZ XZY YXZ YZX ZXY ZYX (default ZYX)")
     ap.add_argument("--bvh-scale", type=float, default=None, help="--bvh: length units per metre (default 100: centimetres)")
     ap.add_argument("--bvh-unwrap", action="store_true", help="--bvh: continuous curves - each frame takes the Euler triple nearest the frame before")
-    args = ap.parse_args(argv)
+    return ap
+
+
+def _needs_smplx(args, flag: str, reason: str) -> None:
+    """`flag` poses bodies: --smplx-models DIR must be given and hold the three model files - checked before anything is loaded or sampled"""
+    from . import body
+    if not args.smplx_models:
+        raise SystemExit(f"{flag} needs --smplx-models DIR: {reason}")
+    body.require_models(args.smplx_models, f"{flag}: ", load=False)
+
+
+def check_switches(args):
+    """Every refusal a command line gets before the configuration is read, in a fixed order -> the checked options of --smooth and --bvh (None: switch off)"""
     fn = args.fn[0]
     if fn not in ("infer_gesture", "edit_gesture", "train_gesture"):
         raise SystemExit(f"--fn {fn}: infer_gesture, edit_gesture and train_gesture run on this path")
@@ -312,24 +323,14 @@ def main(argv=None):
     if args.motion_metrics:
         if fn == "train_gesture":
             raise SystemExit("--motion-metrics belongs to --fn infer_gesture / edit_gesture: it evaluates the pairs the edit tasks collect")
-        if not args.smplx_models:
-            raise SystemExit("--motion-metrics needs --smplx-models DIR: APE / AVE are taken on the joints the SMPL-X body models pose")
-        from . import body
-        if not body.models_present(args.smplx_models):      # checked before anything is loaded or sampled
-            raise SystemExit(f"--motion-metrics: {', '.join(body.SMPLX_FILES.values())} were not all found in {args.smplx_models} (--smplx-models DIR names the "
-                             "directory)")
+        _needs_smplx(args, "--motion-metrics", "APE / AVE are taken on the joints the SMPL-X body models pose")
         if args.metrics_diversity_times < 1:
             raise SystemExit(f"--metrics-diversity-times {args.metrics_diversity_times}: at least 1")
     if args.beat_align:
         if fn != "infer_gesture":
             raise SystemExit("--beat-align belongs to --fn infer_gesture: it scores every WAV against the motion generated from it (which WAV an edited motion "
                              "should align with is a separate question)")
-        if not args.smplx_models:
-            raise SystemExit("--beat-align needs --smplx-models DIR: the motion beats are taken on the joints the SMPL-X body models pose")
-        from . import body
-        if not body.models_present(args.smplx_models):      # checked before anything is loaded or sampled
-            raise SystemExit(f"--beat-align: {', '.join(body.SMPLX_FILES.values())} were not all found in {args.smplx_models} (--smplx-models DIR names the "
-                             "directory)")
+        _needs_smplx(args, "--beat-align", "the motion beats are taken on the joints the SMPL-X body models pose")
     smooth_opts = None
     if not args.smooth and any(v is not None for v in (args.smooth_window, args.smooth_order, args.smooth_hands_window)):
         raise SystemExit("--smooth-window / --smooth-order / --smooth-hands-window belong to --smooth")
@@ -338,8 +339,7 @@ def main(argv=None):
             raise SystemExit("--smooth belongs to --fn infer_gesture / edit_gesture: it filters the motions those write")
         from . import smooth as smooth_mod
         try:               # checked before anything is loaded or sampled
-            smooth_opts = smooth_mod.options(smooth_mod.DEFAULT_WINDOW if args.smooth_window is None else args.smooth_window,
-                                             smooth_mod.DEFAULT_ORDER if args.smooth_order is None else args.smooth_order, args.smooth_hands_window)
+            smooth_opts = smooth_mod.options(args.smooth_window, args.smooth_order, args.smooth_hands_window)
         except ValueError as e:
             raise SystemExit(f"--smooth: {e}")
     bvh_opts = None
@@ -348,15 +348,10 @@ def main(argv=None):
     if args.bvh:
         if fn == "train_gesture":
             raise SystemExit("--bvh belongs to --fn infer_gesture / edit_gesture: it converts the NPZ files those write")
-        if not args.smplx_models:
-            raise SystemExit("--bvh needs --smplx-models DIR: the hierarchy's offsets are the rest joints of the SMPL-X body models")
-        from . import body
+        _needs_smplx(args, "--bvh", "the hierarchy's offsets are the rest joints of the SMPL-X body models")
         from . import bvh as bvh_mod
-        if not body.models_present(args.smplx_models):      # checked before anything is loaded or sampled
-            raise SystemExit(f"--bvh: {', '.join(body.SMPLX_FILES.values())} were not all found in {args.smplx_models} (--smplx-models DIR names the directory)")
         try:
-            bvh_opts = bvh_mod.options(bvh_mod.DEFAULT_ORDER if args.bvh_order is None else args.bvh_order,
-                                       bvh_mod.DEFAULT_SCALE if args.bvh_scale is None else args.bvh_scale, args.bvh_unwrap)
+            bvh_opts = bvh_mod.options(args.bvh_order, args.bvh_scale, args.bvh_unwrap)
         except ValueError as e:
             raise SystemExit(f"--bvh: {e}")
     if args.long_form and fn != "infer_gesture":
@@ -367,6 +362,32 @@ def main(argv=None):
             longform.plan(0, args.hop_frames)      # the library's own check of the hop, before anything is loaded
         except _lib.AmuseHipError as e:
             raise SystemExit(f"--hop-frames {args.hop_frames}: {e}")
+    return smooth_opts, bvh_opts
+
+
+def post_run(args, tr, written, models, bvh_opts, device) -> None:
+    """This rank's own NPZ files after the run: the preview, then the BVH export - of what the files hold (lower body frozen, the stitch, the smoothing)"""
+    if args.preview:
+        from . import render
+        from .video import preview_wav
+        with closing(render.Previewer(models, device, args.preview_size, args.preview_stride, args.preview_frames, video=args.preview_video,
+                                      quality=90 if args.preview_quality is None else args.preview_quality)) as pv:
+            drawn = [f for p in written for f in pv.preview(p, wav=preview_wav(tr.preview_audio.get(str(p))) if args.preview_video else None)]
+        n_avi = sum(1 for f in drawn if Path(f).suffix == ".avi")
+        print(f"[amuse_amd] --preview: {len(drawn) - n_avi} PNG files" + (f" and {n_avi} AVI files" if n_avi else "") + f" beside {len(written)} NPZ files")
+    if bvh_opts is not None:            # in one batch
+        from . import bvh as bvh_mod
+        try:
+            n_bvh = len(bvh_mod.motion_to_bvh_batch(written, models, device=device, **bvh_opts))
+        except bvh_mod.BvhRangeError as e:
+            raise SystemExit(f"--bvh: {e}")
+        print(f"[amuse_amd] --bvh: {n_bvh} BVH files beside {len(written)} NPZ files")
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    fn = args.fn[0]
+    smooth_opts, bvh_opts = check_switches(args)
     tic = time.time()
     dirname = Path(args.root) if args.root else Path.cwd().parent
     config, ldm_cfg = load_config(dirname, fn, args.cfg)
@@ -374,10 +395,10 @@ def main(argv=None):
     if fn == "train_gesture":
         config["_ldm_cfg"] = ldm_cfg
         return train_gesture_entry(args, dirname, config)
-    preview_models = None
+    models = None             # the SMPL-X body models of --preview / --motion-metrics / --beat-align / --bvh: one directory, read once for all of them
     if args.preview:          # checked before anything is loaded or sampled: the model files, and their triangles
         from . import render
-        preview_models = render.load_preview_models(Path(args.smplx_models) if args.smplx_models else dirname / "body_models" / "codebase" / "models" / "smplx")
+        models = render.load_preview_models(Path(args.smplx_models) if args.smplx_models else dirname / "body_models" / "codebase" / "models" / "smplx")
         if args.preview_size < 1 or args.preview_size > 1024 or args.preview_stride < 1:
             raise SystemExit(f"--preview-size {args.preview_size} (1..1024: the renderer takes 2048 samples per axis at 2 x supersampling) / --preview-stride "
                              f"{args.preview_stride} (>= 1)")
@@ -446,15 +467,13 @@ def main(argv=None):
         tp["test"]["long_form"], tp["test"]["hop_frames"] = True, int(args.hop_frames)
     if smooth_opts is not None:     # (as above: the key is this path's own)
         tp["test"]["smooth"] = smooth_opts
-    metric_models = None
     if args.motion_metrics:  # (the keys are this path's own; without the switch the configuration is left as it is)
-        from . import body
         tp["test"]["motion_metrics"], tp["test"]["metrics_diversity_times"] = True, int(args.metrics_diversity_times)
-        metric_models = body.load_models(args.smplx_models)
     if args.beat_align:      # (as above: the key is this path's own)
-        from . import body
         tp["test"]["beat_align"] = True
-        metric_models = metric_models or body.load_models(args.smplx_models)
+    if models is None and (args.motion_metrics or args.beat_align or args.bvh):
+        from . import body
+        models = body.require_models(args.smplx_models, "--smplx-models: ")
     model.precision = args.precision
     print(f"[amuse_amd] sampler / decoder precision: {args.precision}; audio front-end precision: {args.audio_precision}"
           + (" (split-fp16 AST encoders: with --precision fp32 / fp32x the run is in parity from the waveform)" if args.audio_precision == "fp32x"
@@ -464,29 +483,11 @@ def main(argv=None):
     eval_loader = torch.load(args.eval_data, weights_only=False) if args.eval_data else None
     tr = trainer(config, device, train_loader=eval_loader, model_path=model_path, tag="LPDM_infer", logger_cfg=None,
                  model=model, processed=processed, metricsmodel=None, b_path=None, EXEC_ON_CLUSTER=False,
-                 debug=tp.get("debug", True), pretrained_infer=True, rank=rank, world=world, body_models=metric_models)
+                 debug=tp.get("debug", True), pretrained_infer=True, rank=rank, world=world, body_models=models if args.motion_metrics or args.beat_align else None)
     written = tr.eval_prior_latdiff_forward_backward_v1(baseline, ldm_epoch, audio_list, short_audio_list,
                                                         modelversion=modelversion, ammetric=True)
     torch.cuda.synchronize()
-    if preview_models is not None:      # this rank's own files: what the NPZ holds (lower body frozen, zero translation), as the reference renders the NPZ
-        from . import render
-        pv = render.Previewer(preview_models, device, args.preview_size, args.preview_stride, args.preview_frames, video=args.preview_video,
-                              quality=90 if args.preview_quality is None else args.preview_quality)
-        try:
-            from .video import preview_wav
-            drawn = [f for p in written for f in pv.preview(p, wav=preview_wav(tr.preview_audio.get(str(p))) if args.preview_video else None)]
-        finally:
-            pv.close()
-        n_avi = sum(1 for f in drawn if Path(f).suffix == ".avi")
-        print(f"[amuse_amd] --preview: {len(drawn) - n_avi} PNG files" + (f" and {n_avi} AVI files" if n_avi else "") + f" beside {len(written)} NPZ files")
-    if bvh_opts is not None:            # this rank's own files, in one batch: what the NPZ holds (after the lower-body freeze, the stitch and the smoothing)
-        from . import body
-        from . import bvh as bvh_mod
-        try:
-            n_bvh = len(bvh_mod.motion_to_bvh_batch(written, body.load_models(args.smplx_models), device=device, **bvh_opts))
-        except bvh_mod.BvhRangeError as e:
-            raise SystemExit(f"--bvh: {e}")
-        print(f"[amuse_amd] --bvh: {n_bvh} BVH files beside {len(written)} NPZ files")
+    post_run(args, tr, written, models, bvh_opts, device)
     print(f"AMUSE: ({fn}) completed in: {(time.time() - tic) / 3600} hrs; {len(written)} NPZ files" + (f" on rank {rank} of {world}" if world > 1 else ""))
     if world > 1 and os.environ.get("AMUSE_MANIFEST_DIR"):      # the launcher collects what the ranks wrote
         Path(os.environ["AMUSE_MANIFEST_DIR"], f"rank{rank}.json").write_text(json.dumps([str(p) for p in written]))

@@ -14,6 +14,7 @@ What is here restates the accumulation (val_metrics.py:63-137) without torchmetr
 from __future__ import annotations
 
 import json
+from contextlib import closing
 from pathlib import Path
 from typing import Dict, Optional
 
@@ -306,40 +307,35 @@ def compare_directories(gen_dir, ref_dir, models: dict, device="cuda:0") -> dict
     """The joint half for two directories of *_motion_smplx.npz matched by file name (the reference's own outputs included): each pair is one clip, posed by the
     body model of the reference file's gender with that file's betas.  Needs no checkpoint."""
     import torch
-    from . import body
+    from . import body, motion_file
     gen_dir, ref_dir = Path(gen_dir), Path(ref_dir)
     names = sorted(p.name for p in gen_dir.glob("*_motion_smplx.npz") if (ref_dir / p.name).is_file())
     if not names:
         raise SystemExit(f"motion_metrics: no *_motion_smplx.npz of {gen_dir} has a file of the same name in {ref_dir}")
     by_gender: Dict[str, list] = {}
     for n in names:
-        with np.load(ref_dir / n, allow_pickle=False) as zr, np.load(gen_dir / n, allow_pickle=False) as zg:
-            g = str(zr["gender"])
-            if g not in models:
-                raise SystemExit(f"motion_metrics: {ref_dir / n} names the gender '{g}'; the body models are {', '.join(models)}")
-            if zg["poses"].shape != zr["poses"].shape:
-                raise SystemExit(f"motion_metrics: {n}: {zg['poses'].shape[0]} generated and {zr['poses'].shape[0]} reference frames")
-            by_gender.setdefault(g, []).append((n, np.asarray(zg["poses"], np.float32), np.asarray(zg["trans"], np.float32), np.asarray(zr["poses"], np.float32),
-                                                np.asarray(zr["trans"], np.float32), np.asarray(zr["betas"], np.float32)))
+        r, g = motion_file.read(ref_dir / n), motion_file.read(gen_dir / n)
+        if r.gender not in models:
+            raise SystemExit(f"motion_metrics: {ref_dir / n} names the gender '{r.gender}'; the body models are {', '.join(models)}")
+        if g.poses.shape != r.poses.shape:
+            raise SystemExit(f"motion_metrics: {n}: {g.poses.shape[0]} generated and {r.poses.shape[0]} reference frames")
+        by_gender.setdefault(r.gender, []).append((n, g, r))
     jm, per_file = JointMetrics(), {}
-    for g, items in by_gender.items():
-        eng = body.BodyEngine(device, models[g])
-        try:
-            for F in sorted({it[1].shape[0] for it in items}):      # one call per clip length: a call's clips share F
-                grp = [it for it in items if it[1].shape[0] == F]
-                nb = models[g].n_betas      # the file's betas cut to the model's count (zero-padded if the file holds fewer)
-                betas = np.stack([np.pad(it[5].reshape(-1)[:nb], (0, max(0, nb - it[5].size))) for it in grp])
-                eng.set_subjects(betas)
+    with closing(body.Poser(models, device)) as poser:
+        for gender, items in by_gender.items():
+            eng = poser.engine(gender)
+            for F in sorted({r.poses.shape[0] for _, _, r in items}):      # one call per clip length: a call's clips share F
+                grp = [it for it in items if it[2].poses.shape[0] == F]
+                eng.set_subjects(np.stack([body.fit_betas(r.betas, eng.model.n_betas) for _, _, r in grp]))      # one betas row per file: the reference file's
                 sub = torch.arange(len(grp), dtype=torch.int32, device=device)
-                t = lambda k: torch.from_numpy(np.stack([it[k] for it in grp])).to(device).contiguous()
-                rows = joint_rows(eng.joints(t(1), t(2), sub, "aa"), eng.joints(t(3), t(4), sub, "aa"))
+                t = lambda arrays: torch.from_numpy(np.stack(arrays)).to(device).contiguous()
+                rows = joint_rows(eng.joints(t([g.poses for _, g, _ in grp]), t([g.trans for _, g, _ in grp]), sub, "aa"),
+                                  eng.joints(t([r.poses for _, _, r in grp]), t([r.trans for _, _, r in grp]), sub, "aa"))
                 jm.update(rows, [F] * len(grp))
-                for it, r in zip(grp, rows.cpu().numpy()):
+                for (n, _, _), row in zip(grp, rows.cpu().numpy()):
                     one = JointMetrics()
-                    one.update(r, [F])
-                    per_file[it[0]] = {k: _plain(v) for k, v in one.compute().items() if not k.endswith("_per_joint")}
-        finally:
-            eng.close()
+                    one.update(row, [F])
+                    per_file[n] = {k: _plain(v) for k, v in one.compute().items() if not k.endswith("_per_joint")}
     return {"files": len(names), "count": jm.count, "count_seq": jm.count_seq, **{k: _plain(v) for k, v in jm.compute().items()}, "per_file": per_file}
 
 
@@ -353,9 +349,7 @@ def main(argv=None):
     ap.add_argument("--out", default=None, help="write the JSON here instead of printing it")
     args = ap.parse_args(argv)
     from . import body
-    if not body.models_present(args.smplx_models):
-        raise SystemExit(f"motion_metrics: {', '.join(body.SMPLX_FILES.values())} were not all found in {args.smplx_models}")
-    rep = compare_directories(args.gen_dir, args.ref_dir, body.load_models(args.smplx_models), args.device)
+    rep = compare_directories(args.gen_dir, args.ref_dir, body.require_models(args.smplx_models, "motion_metrics: "), args.device)
     text = json.dumps(rep, indent=1, allow_nan=False)
     if args.out:
         Path(args.out).write_text(text)

@@ -3,7 +3,6 @@ packing of its call sites (scripts/trainer.py:524-526).  Rendering (Blender / ff
 draws a preview of what these files hold (poses, trans, betas, gender), opt-in."""
 from __future__ import annotations
 
-import os
 import random
 import string
 from pathlib import Path
@@ -11,6 +10,8 @@ from typing import Optional
 
 import numpy as np
 import torch
+
+from . import motion_file
 
 LOWER_BODY_JOINTS = [1, 2, 4, 5, 7, 8, 10, 11]  # "Lock below hips" (visualizer.py:346)
 # dm/utils/ldm_evals.py:67-71 subject2genderbeta: the BEAT actors by gender, and the per-actor SMPL-X shape vectors
@@ -73,15 +74,7 @@ def write_sample(feats: torch.Tensor, out_dir: Path, subject: str = "scott", rng
     if betas is None:
         betas = fetchbetas(subject)
     for i, feat in enumerate(feats):
-        d = Path(out_dir) / f"seq_{i}"
-        d.mkdir(parents=True, exist_ok=True)
         tag = "".join(rng.choice(string.ascii_uppercase + string.ascii_lowercase + string.digits) for _ in range(6))
-        p = d / f"{subject}_seq_{i}_{tag}_motion_smplx.npz"
-        # written beside the target and moved over it: a reader that still holds an older file of the same name open (two runs inside one second share the
-        # time-stamped directory and the seeded tags) keeps reading that file, never a half-written or replaced one
-        tmp = p.with_name(p.name + ".part")
-        with open(tmp, "wb") as fh:
-            np.savez(fh, **smplx_npz_fields(feat.detach().cpu().numpy(), subject2gender(subject), betas))
-        os.replace(tmp, p)
-        paths.append(p)
+        paths.append(motion_file.save(Path(out_dir) / f"seq_{i}" / f"{subject}_seq_{i}_{tag}_motion_smplx.npz",
+                                      **smplx_npz_fields(feat.detach().cpu().numpy(), subject2gender(subject), betas)))
     return paths

@@ -14,13 +14,14 @@ from __future__ import annotations
 import ctypes as C
 import struct
 import zlib
+from contextlib import closing
 from pathlib import Path
 from typing import Optional
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, body, motion_file
 
 LENS_MM, SENSOR_MM = 75.0, 36.0     # the reference's Blender camera: a 75 mm lens on the default 36 mm sensor
 FLESH_PAD = 0.15                    # metres added around the joints' bounding box: the joints lie inside the body
@@ -167,24 +168,12 @@ def contact_sheet(frames, cols: int = SHEET_COLS):
 # ------------------------------------------------------------------ NPZ -> pictures
 def load_preview_models(directory) -> dict:
     """{"male" | "female" | "neutral": BodyModel with faces} from a directory of the user's SMPL-X files; SystemExit names what is missing."""
-    from . import body
-    directory = Path(directory)
-    if not body.models_present(directory):
-        raise SystemExit(f"preview: {', '.join(body.SMPLX_FILES.values())} were not all found in {directory} (--smplx-models DIR names another directory): the "
-                         "preview poses the licensed SMPL-X body models")
-    models = body.load_models(directory)
-    for g, m in models.items():
-        if m.faces is None:
-            raise SystemExit(f"preview: {directory / body.SMPLX_FILES[g]} lacks the key 'f' (the mesh's triangles, [T][3]): without them there is nothing to rasterise")
-    return models
+    return body.require_models(directory, "preview: ", "(--smplx-models DIR names another directory): the preview poses the licensed SMPL-X body models", faces=True)
 
 
 def preview_paths(npz_path, out_dir=None):
     """(sheet, frames directory) of an NPZ: <name>_motion_smplx.npz -> <name>_preview.png, <name>_preview/"""
-    p = Path(npz_path)
-    stem = p.name[:-len("_motion_smplx.npz")] if p.name.endswith("_motion_smplx.npz") else p.stem
-    d = Path(out_dir) if out_dir is not None else p.parent
-    return d / f"{stem}_preview.png", d / f"{stem}_preview"
+    return motion_file.sibling(npz_path, "_preview.png", out_dir), motion_file.sibling(npz_path, "_preview", out_dir)
 
 
 class Previewer:
@@ -198,20 +187,13 @@ class Previewer:
             raise SystemExit(f"preview: --quality {quality} outside 1..100")
         self.models, self.device, self.size, self.stride, self.frames, self.ss, self.batch = models, torch.device(device), int(size), int(stride), bool(frames), ss, batch
         self.video, self.quality, self._enc = bool(video), int(quality), None
-        self._eng = {}
-
-    def _engine(self, gender):
-        from . import body
-        if gender not in self._eng:
-            m = self.models[gender]
-            self._eng[gender] = (body.BodyEngine(self.device, m), Renderer(self.device, m.faces, m.V, self.size, self.size, self.ss))
-        return self._eng[gender]
+        self._poser, self._ren = body.Poser(models, self.device), {}
 
     def close(self):
-        for e, r in self._eng.values():
-            e.close()
+        self._poser.close()
+        for r in self._ren.values():
             r.close()
-        self._eng = {}
+        self._ren = {}
         if self._enc is not None:
             self._enc.close()
             self._enc = None
@@ -226,20 +208,16 @@ class Previewer:
 
     def preview(self, npz_path, out_dir=None, wav=None):
         """-> the paths written (the sheet first; with video=True the AVI last)"""
-        with np.load(str(npz_path), allow_pickle=False) as z:
-            poses, trans = np.asarray(z["poses"], np.float32), np.asarray(z["trans"], np.float32)
-            betas, gender = np.asarray(z["betas"], np.float32).reshape(-1), str(z["gender"])
-        gender = gender if gender in self.models else "neutral"
-        model = self.models[gender]
+        m = motion_file.read(npz_path)
+        if m.gender not in self.models:
+            m = m._replace(gender="neutral")
+        model = self.models[m.gender]
         if model.faces is None:
-            raise SystemExit(f"preview: the {gender} body model lacks the key 'f' (the mesh's triangles)")
-        eng, ren = self._engine(gender)
-        F = int(poses.shape[0])
-        b = np.zeros(model.n_betas, np.float32)
-        b[:min(model.n_betas, betas.size)] = betas[:model.n_betas]
-        eng.set_subjects(b[None])
-        rot = torch.from_numpy(np.ascontiguousarray(poses.reshape(1, F, 55, 3))).to(self.device)
-        tr = torch.from_numpy(np.ascontiguousarray(trans.reshape(1, F, 3))).to(self.device)
+            raise SystemExit(f"preview: the {m.gender} body model lacks the key 'f' (the mesh's triangles)")
+        eng, rot, tr = self._poser.pose(m)
+        if m.gender not in self._ren:
+            self._ren[m.gender] = Renderer(self.device, model.faces, model.V, self.size, self.size, self.ss)
+        ren, F = self._ren[m.gender], int(rot.shape[1])
         cam = Camera.front(eng.joints(rot, tr).cpu().numpy(), self.size, self.size)      # one camera for the clip: framed on every frame's joints
         sheet_path, frames_dir = preview_paths(npz_path, out_dir)
         sheet_path.parent.mkdir(parents=True, exist_ok=True)
@@ -284,11 +262,8 @@ def preview_npz(npz_path, models, out_dir=None, size: int = 512, stride: int = 1
     """One NPZ (this project's or the reference's own): models = {"male" | "female" | "neutral": BodyModel} or a directory holding the SMPL-X files."""
     if not isinstance(models, dict):
         models = load_preview_models(models)
-    p = Previewer(models, device, size, stride, frames, video=video, quality=quality)
-    try:
+    with closing(Previewer(models, device, size, stride, frames, video=video, quality=quality)) as p:
         return p.preview(npz_path, out_dir, wav)
-    finally:
-        p.close()
 
 
 def main(argv=None):
@@ -318,13 +293,8 @@ def main(argv=None):
     for n in args.npz:
         if not Path(n).is_file():
             raise SystemExit(f"preview: {n} does not exist")
-    p = Previewer(models, args.device, args.size, args.stride, args.frames, video=args.video, quality=quality)
-    written = []
-    try:
-        for n in args.npz:
-            written += p.preview(n, args.out_dir, args.audio)
-    finally:
-        p.close()
+    with closing(Previewer(models, args.device, args.size, args.stride, args.frames, video=args.video, quality=quality)) as p:
+        written = [f for n in args.npz for f in p.preview(n, args.out_dir, args.audio)]
     n_avi = sum(1 for w in written if Path(w).suffix == ".avi")
     print(f"preview: wrote {len(written) - n_avi} PNG files" + (f" and {n_avi} AVI files" if n_avi else "") + f"; first {written[0]}")
     return written

@@ -16,14 +16,13 @@ from __future__ import annotations
 
 import argparse
 import ctypes as C
-import os
 from pathlib import Path
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, motion_file
 
 MAX_HALF, MAX_ORDER, BANK_FLOATS, SLOTS = 15, 5, 5455, 56
 HAND_JOINTS = range(25, 55)      # the SMPL-X fingers: 15 joints of the left hand, 15 of the right
@@ -113,9 +112,9 @@ def smooth(poses: torch.Tensor, trans: Optional[torch.Tensor], frames: Sequence[
     return poses_out, trans_out
 
 
-def options(window: int = DEFAULT_WINDOW, order: int = DEFAULT_ORDER, hands_window: Optional[int] = None) -> dict:
-    """The checked per-run options as trainer.run_jobs / PretrainedLPDM_v1.infer_long take them (`smooth=`) and TRAIN_PARAM.test.smooth stores them."""
-    o = {"window": check_window(window), "order": check_order(order)}
+def options(window: Optional[int] = None, order: Optional[int] = None, hands_window: Optional[int] = None) -> dict:
+    """The checked per-run options as trainer.run_jobs / PretrainedLPDM_v1.infer_long take them (`smooth=`) and TRAIN_PARAM.test.smooth stores them; None: the default."""
+    o = {"window": check_window(DEFAULT_WINDOW if window is None else window), "order": check_order(DEFAULT_ORDER if order is None else order)}
     if hands_window is not None:
         o["hands_window"] = check_window(hands_window, "hands_window")
     return o
@@ -131,32 +130,17 @@ def smooth_batch(poses: torch.Tensor, trans: Optional[torch.Tensor], opts: dict)
 
 # ------------------------------------------------------------------ python -m amuse_amd.smooth
 def output_path(src: Path, out_dir: Optional[Path] = None) -> Path:
-    name = src.name
-    stem = name[:-len("_motion_smplx.npz")] if name.endswith("_motion_smplx.npz") else src.stem
-    return (Path(out_dir) if out_dir is not None else src.parent) / f"{stem}_smoothed_motion_smplx.npz"
+    return motion_file.sibling(src, "_smoothed_motion_smplx.npz", out_dir)
 
 
 def smooth_npz(src, out_dir=None, window: int = DEFAULT_WINDOW, order: int = DEFAULT_ORDER, hands_window: Optional[int] = None, device="cuda") -> Path:
     """One *_motion_smplx.npz -> *_smoothed_motion_smplx.npz, written through npz_writer.smplx_npz_fields: the lower-body lock and the zero `trans` hold as in
     every NPZ of this project; betas, gender and frame rate are carried over."""
     from .npz_writer import smplx_npz_fields
-    src = Path(src)
-    with np.load(src) as z:
-        poses = np.asarray(z["poses"], dtype=np.float32)
-        gender = str(z["gender"]) if "gender" in z.files else "neutral"
-        betas = np.asarray(z["betas"], dtype=np.float64) if "betas" in z.files else None
-        fps = float(z["mocap_frame_rate"]) if "mocap_frame_rate" in z.files else 30.0
-    poses = poses.reshape(poses.shape[0], -1, 3)
-    if poses.shape[1] != 55:
-        raise ValueError(f"{src}: poses hold {poses.shape[1]} joints, not SMPL-X's 55")
-    out, _ = smooth(torch.from_numpy(poses).to(device), None, [poses.shape[0]], window, order, hands_window)
-    dst = output_path(src, out_dir)
-    dst.parent.mkdir(parents=True, exist_ok=True)
-    tmp = dst.with_name(dst.name + ".part")
-    with open(tmp, "wb") as fh:
-        np.savez(fh, **smplx_npz_fields(out.cpu().numpy().reshape(poses.shape[0], 165), gender, betas, fps))
-    os.replace(tmp, dst)
-    return dst
+    m = motion_file.read(src)
+    F = m.poses.shape[0]
+    out, _ = smooth(torch.from_numpy(m.poses).to(device), None, [F], window, order, hands_window)
+    return motion_file.save(output_path(m.path, out_dir), **smplx_npz_fields(out.cpu().numpy().reshape(F, 165), m.gender, m.betas, m.fps))
 
 
 def parse_args(argv=None):

@@ -566,23 +566,30 @@ class trainer:
             if n:
                 self._mm_tasks[name].update(rst[:n], src[:n], [(m["actor"],)] * n)
 
-    def _motion_metrics_write(self, ldm_epoch) -> Optional[Path]:
-        """<model_path>/viz/motion_metrics_<stamp>_E<epoch>.json.  More than one rank: the additive states are all-gathered and rank 0 writes; ranks that run
-        without a process group each write their own share, named by rank."""
-        from . import motion_metrics as mm
-        states = {name: ev.state() for name, ev in self._mm_tasks.items()}
-        suffix = ""
+    def _gather_report(self, payload, name: str, ldm_epoch):
+        """Who writes <model_path>/viz/<name>_<stamp>_E<epoch>.json, from what.  One rank: (None, path), its own payload is the report.  More, with a process group:
+        the picklable payloads are all-gathered, rank 0 gets (the list of them, path), the others None - they do not write; without one: (None, path + _rank<r>)."""
+        parts, suffix = None, ""
         if self.world > 1:
             if _dist_ready():
                 import torch.distributed as dist
                 parts = [None] * self.world
-                dist.all_gather_object(parts, states)
+                dist.all_gather_object(parts, payload)
                 if self.rank != 0:
                     return None
-                states = {name: mm.merge_states([p[name] for p in parts if name in p]) for name in sorted({k for p in parts for k in p})}
             else:
                 suffix = f"_rank{self.rank}"
-        path = self.model_path / "viz" / f"motion_metrics_{self.stamp}_E{ldm_epoch}{suffix}.json"
+        return parts, self.model_path / "viz" / f"{name}_{self.stamp}_E{ldm_epoch}{suffix}.json"
+
+    def _motion_metrics_write(self, ldm_epoch) -> Optional[Path]:
+        """<model_path>/viz/motion_metrics_<stamp>_E<epoch>.json (_gather_report: the additive states of all ranks, merged per task)"""
+        from . import motion_metrics as mm
+        states = {name: ev.state() for name, ev in self._mm_tasks.items()}
+        if (got := self._gather_report(states, "motion_metrics", ldm_epoch)) is None:
+            return None
+        parts, path = got
+        if parts is not None:
+            states = {name: mm.merge_states([p[name] for p in parts if name in p]) for name in sorted({k for p in parts for k in p})}
         times = int(self.config["TRAIN_PARAM"]["test"].get("metrics_diversity_times", 300))
         self.motion_metrics_path = mm.write_report(path, states, str(getattr(self.model, "precision", "")), times, seed=self.config["TRAIN_PARAM"].get("seed", 0))
         print(f"[amuse_amd] motion metrics: {self.motion_metrics_path}")
@@ -596,29 +603,23 @@ class trainer:
         """TRAIN_PARAM.test.beat_align: every WAV of the audio list against the motion its NPZ holds - stitched or not, as the file holds it (lower body frozen,
         zero translation), posed by the NPZ's own gender and betas; the waveform is the one the front-end read (_load_wave: resampled under
         TRAIN_PARAM.test.resample, the mean removed).  Writes <model_path>/viz/beat_align_<stamp>_E<epoch>.json; reads the NPZ files, changes none.  More than
-        one rank: as the motion metrics - the additive states are all-gathered and rank 0 writes; ranks without a process group each write their own share."""
+        one rank: _gather_report, the per-file entries joined and the additive states merged."""
         from . import beat_align as ba
 
         def front_end_wave(path):
             w = self._load_wave(path)
             return (w - w.mean())[0]
         res = ba.score_pairs(self.beat_pairs, self.body_models, self.device, load_wave=front_end_wave)
-        per_file, state, suffix = res["per_file"], res["state"], ""
-        if self.world > 1:
-            if _dist_ready():
-                import torch.distributed as dist
-                parts = [None] * self.world
-                dist.all_gather_object(parts, (per_file, state))
-                if self.rank != 0:
-                    return None
-                per_file = {k: v for p, _ in parts for k, v in p.items()}
-                state = ba.BeatAlign()
-                for _, st in parts:
-                    state.merge(st)
-                state = state.state()
-            else:
-                suffix = f"_rank{self.rank}"
-        path = self.model_path / "viz" / f"beat_align_{self.stamp}_E{ldm_epoch}{suffix}.json"
+        per_file, state = res["per_file"], res["state"]
+        if (got := self._gather_report((per_file, state), "beat_align", ldm_epoch)) is None:
+            return None
+        parts, path = got
+        if parts is not None:
+            per_file = {k: v for p, _ in parts for k, v in p.items()}
+            state = ba.BeatAlign()
+            for _, st in parts:
+                state.merge(st)
+            state = state.state()
         self.beat_align_path = ba.write_report(path, per_file, state, res["params"], str(getattr(self.model, "precision", "")))
         print(f"[amuse_amd] beat alignment: {self.beat_align_path}")
         return self.beat_align_path

@@ -262,3 +262,46 @@ def test_trainer_iteration_with_body():
         print(f"replay on the swapped genders, term {i}: {float(out[i]):.9g} float64 twin {float(want[i]):.9g} relative {rel:.3e} bar {FLOOR:.3e}")
         assert rel <= FLOOR
     bl.close()
+
+
+def test_poser_matches_a_hand_driven_engine(tmp_path):
+    """body.Poser on motion_file.read records against BodyEngine driven by hand as beat_align.score_pairs drove it before there was a Poser - bit for bit: two
+    files of two genders and lengths, stored betas one short of and one past the model's 300, the first file again after the other subject was set."""
+    from amuse_amd import body, motion_file
+    models = {g: body.BodyModel.from_dict(bc.make_model(V=203, n_betas=300, seed=s)) for g, s in (("male", 0), ("female", 7))}
+    files = []
+    for k, (g, F, nb) in enumerate((("male", 2, 299), ("female", 3, 301))):
+        aa, tr, _ = bc.make_motion(1, F, seed=40 + k)
+        files.append(tmp_path / f"{g}_motion_smplx.npz")
+        np.savez(files[-1], poses=aa[0].reshape(F, 165), trans=tr[0].astype(np.float64), gender=np.array(g, dtype="<U7"),
+                 betas=np.random.default_rng(50 + k).standard_normal(nb) * 0.5, mocap_frame_rate=np.array(30.0))
+
+    def by_hand(path, engines):
+        with np.load(path, allow_pickle=False) as z:
+            g = str(z["gender"])
+            poses, trans, betas = np.asarray(z["poses"], np.float32), np.asarray(z["trans"], np.float32), np.asarray(z["betas"], np.float32)
+        F, n = int(poses.shape[0]), models[g].n_betas
+        if g not in engines:
+            engines[g] = body.BodyEngine(DEV, models[g])
+        engines[g].set_subjects(np.pad(betas.reshape(-1)[:n], (0, max(0, n - betas.size)))[None])
+        return engines[g].joints(torch.from_numpy(poses.reshape(1, F, 55, 3)).to(DEV).contiguous(), torch.from_numpy(trans.reshape(1, F, 3)).to(DEV).contiguous(),
+                                 torch.zeros(1, dtype=torch.int32, device=DEV), "aa").clone()
+
+    order = [files[0], files[1], files[0]]
+    hand = {}
+    want = [by_hand(p, hand) for p in order]
+    for e in hand.values():
+        e.close()
+    poser = body.Poser(models, DEV)
+    got = []
+    for p in order:
+        eng, rot, tr = poser.pose(motion_file.read(p))
+        assert tuple(rot.shape) == (1, rot.shape[1], 55, 3) and tuple(tr.shape) == (1, rot.shape[1], 3) and rot.is_cuda and eng.n_subjects == 1
+        got.append(eng.joints(rot, tr).clone())
+    torch.cuda.synchronize()
+    assert [tuple(j.shape) for j in got] == [(1, 2, 55, 3), (1, 3, 55, 3), (1, 2, 55, 3)]
+    assert all(torch.equal(a, b) for a, b in zip(got, want)) and torch.equal(got[0], got[2]) and bool(torch.isfinite(got[1]).all())
+    engines = list(poser.engines.values())
+    assert len(engines) == 2
+    poser.close()
+    assert poser.engines == {} and all(e.ctx is None for e in engines)

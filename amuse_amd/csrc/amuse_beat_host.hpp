@@ -15,12 +15,10 @@
 #include <vector>
 
 #include "../../include/amuse_hip.h"
-
-__attribute__((visibility("hidden"), format(printf, 2, 3))) int amuse_failf(int code, const char* fmt, ...);
+#include "amuse_seq_host.hpp"
 
 namespace amuse {
 
-constexpr int kBeatJoints = 55;                          // SMPL-X joints of a frame: 165 contiguous floats
 constexpr int kBeatMel = 128, kBeatBins = 257;           // the fbank tables of audio.kaldi_tables()
 constexpr int kBeatWin = 400, kBeatHop = 160, kBeatFft = 512, kBeatRate = 16000;
 constexpr int kBeatRun = 16;                             // consecutive frames of one clip a workgroup of the envelope kernel takes (+ the one before them)

@@ -8,8 +8,7 @@
 #include <vector>
 
 #include "../../include/amuse_hip.h"
-
-__attribute__((visibility("hidden"), format(printf, 2, 3))) int amuse_failf(int code, const char* fmt, ...);
+#include "amuse_seq_host.hpp"
 #define fail(...) amuse_failf(__VA_ARGS__)
 #define HIP_TRY(expr)                                                                                   \
     do {                                                                                                \

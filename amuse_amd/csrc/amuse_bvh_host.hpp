@@ -2,8 +2,7 @@
 // k_bvh.hip (the kernels and their launchers), amuse_bvh.hip (the C entry points) and tests/bvh_host (the same host code on stand-in launchers, under sanitizers):
 //   - the layout: the depth-first column order of a parent list, children in ascending index;
 //   - the argument checks of the formatter, the exporter and the decoder, made before any HIP call;
-//   - the packing of a call's sequences into launches: per-sequence offsets and the 55 column joints travel BY VALUE in the kernel arguments (no device table, no
-//     copy, no allocation, so a call can sit inside a captured graph), kBvhMaxSeq sequences per launch, further sequences in further launches.
+//   - a call's sequences, packed into launches by amuse_seq_host.hpp; the 55 column joints travel by value beside them.
 // Context-free: nothing here reads or keeps state.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -15,21 +14,17 @@
 #include <vector>
 
 #include "../../include/amuse_hip.h"
-
-__attribute__((visibility("hidden"), format(printf, 2, 3))) int amuse_failf(int code, const char* fmt, ...);
+#include "amuse_seq_host.hpp"
 
 namespace amuse {
 
-constexpr int kBvhJoints = 55;                            // SMPL-X joints of a pose row
 constexpr int kBvhCols = AMUSE_BVH_COLS;                  // numbers of a MOTION row: 3 root positions + 55 x 3 angles
 constexpr int kBvhField = AMUSE_BVH_FIELD;                // bytes of a number: %11.6f and its separator
 constexpr int kBvhRowBytes = kBvhCols * kBvhField;        // 2,016: a multiple of 4, so every field of every row is dword-aligned from an aligned base
-constexpr int kBvhSlots = 56;                             // lanes per frame: one per column joint, one for the root's position
-constexpr int kBvhMaxSeq = 32;                            // sequences per launch: 32 x 16 B of offsets + 55 B of columns + 6 pointers, far inside 4 KiB
 constexpr int kBvhBlock = 256;
-constexpr int kBvhMaxFrames = (INT_MAX - kBvhBlock) / kBvhSlots;   // a launch's (frame, slot) index, rounded up to whole workgroups, is an int
+constexpr int kBvhMaxFrames = (INT_MAX - kBvhBlock) / kMotionSlots;   // a launch's (frame, slot) index, rounded up to whole workgroups, is an int
 constexpr int kBvhWalkBlock = 64;                         // the unwrap walk: one lane per (sequence, column joint), one wave per workgroup
-static_assert(kBvhRowBytes % 4 == 0 && kBvhCols == 3 + 3 * kBvhJoints, "row layout");
+static_assert(kBvhRowBytes % 4 == 0 && kBvhCols == 3 + 3 * kSmplxJoints, "row layout");
 
 struct BvhSeq {
     long long row0;   // first frame of the sequence (index into poses / trans / euler_out rows; text_out byte offset / 2016)
@@ -48,8 +43,8 @@ struct BvhArgs {
     int ai, aj, ak;           // the axes of the three channels, in channel order: R = R_ai R_aj R_ak
     float e;                  // the permutation sign of (ak, aj, ai)
     int unwrap, nseq, max_F;
-    unsigned char dfs[kBvhJoints];   // column c holds joint dfs[c]
-    BvhSeq seq[kBvhMaxSeq];
+    unsigned char dfs[kSmplxJoints];   // column c holds joint dfs[c]
+    BvhSeq seq[kSeqPerLaunch];
 };
 
 struct BvhDecodeArgs {
@@ -59,8 +54,8 @@ struct BvhDecodeArgs {
     float* trans_out;         // [rows][3]
     float scale;
     int ai, aj, ak, nseq, max_F;
-    unsigned char dfs[kBvhJoints];
-    BvhSeq seq[kBvhMaxSeq];
+    unsigned char dfs[kSmplxJoints];
+    BvhSeq seq[kSeqPerLaunch];
 };
 
 // k_bvh.hip (tests/bvh_host: stand-ins that record the arguments)
@@ -109,9 +104,9 @@ inline bool bvh_order_axes(int order, int (&ax)[3], float* e) {
 }
 
 inline bool bvh_dfs_ok(const int* dfs) {
-    bool seen[kBvhJoints] = {};
-    for (int c = 0; c < kBvhJoints; ++c) {
-        if (dfs[c] < 0 || dfs[c] >= kBvhJoints || seen[dfs[c]]) return false;
+    bool seen[kSmplxJoints] = {};
+    for (int c = 0; c < kSmplxJoints; ++c) {
+        if (dfs[c] < 0 || dfs[c] >= kSmplxJoints || seen[dfs[c]]) return false;
         seen[dfs[c]] = true;
     }
     return true;
@@ -126,6 +121,18 @@ inline int bvh_frames_check(const char* who, int S, const int* frames) {
         if (frames[s] < 1 || frames[s] > kBvhMaxFrames) return amuse_failf(AMUSE_EINVAL, "%s: sequence %d has %d frames (1..%d)", who, s, frames[s], kBvhMaxFrames);
     return AMUSE_OK;
 }
+
+// the exporter's and the decoder's sequences: rows back to back, each with its index in the call
+struct BvhFill {
+    const int* frames;
+    long long row0 = 0;
+    template <class Args>
+    void operator()(Args& a, int k, int s) {
+        a.seq[k] = BvhSeq{row0, frames[s], s};
+        row0 += frames[s];
+        if (frames[s] > a.max_F) a.max_F = frames[s];
+    }
+};
 
 inline int bvh_format(const float* values, long long n, int per_row, unsigned char* text, int* status, hipStream_t stream) {
     if (n < 1 || n > (long long)INT_MAX * kBvhBlock) return amuse_failf(AMUSE_EINVAL, "amuse_bvh_format: n %lld outside 1..%lld", n, (long long)INT_MAX * kBvhBlock);
@@ -148,22 +155,11 @@ inline int bvh_motion(const float* poses, const float* trans, const float* root_
     if (!poses || !root_rest || !status) return amuse_failf(AMUSE_EINVAL, "amuse_bvh_motion: poses, root_rest and status must be given");
     if (!euler && !text) return amuse_failf(AMUSE_EINVAL, "amuse_bvh_motion: euler_out and text_out are both NULL: nothing to write");
     if (reinterpret_cast<uintptr_t>(text) % 4) return amuse_failf(AMUSE_EINVAL, "amuse_bvh_motion: text_out must be 4-byte aligned (a field is stored as three dwords)");
-    long long row0 = 0;
-    for (int s0 = 0; s0 < S; s0 += kBvhMaxSeq) {
-        BvhArgs a{};
-        a.poses = poses; a.trans = trans; a.root_rest = root_rest; a.euler = euler; a.text = text; a.status = status;
-        a.scale = scale; a.ai = ax[0]; a.aj = ax[1]; a.ak = ax[2]; a.e = e; a.unwrap = unwrap ? 1 : 0;
-        for (int c = 0; c < kBvhJoints; ++c) a.dfs[c] = (unsigned char)dfs[c];
-        a.nseq = S - s0 < kBvhMaxSeq ? S - s0 : kBvhMaxSeq;
-        for (int k = 0; k < a.nseq; ++k) {
-            a.seq[k] = BvhSeq{row0, frames[s0 + k], s0 + k};
-            row0 += frames[s0 + k];
-            if (frames[s0 + k] > a.max_F) a.max_F = frames[s0 + k];
-        }
-        const hipError_t err = launch_bvh_motion(a, stream);
-        if (err != hipSuccess) return amuse_failf(AMUSE_EHIP, "amuse_bvh_motion: launch failed: %s", hipGetErrorString(err));
-    }
-    return AMUSE_OK;
+    BvhArgs p{};
+    p.poses = poses; p.trans = trans; p.root_rest = root_rest; p.euler = euler; p.text = text; p.status = status;
+    p.scale = scale; p.ai = ax[0]; p.aj = ax[1]; p.ak = ax[2]; p.e = e; p.unwrap = unwrap ? 1 : 0;
+    for (int c = 0; c < kSmplxJoints; ++c) p.dfs[c] = (unsigned char)dfs[c];
+    return launch_sequences("amuse_bvh_motion", S, p, BvhFill{frames}, launch_bvh_motion, stream);
 }
 
 inline int bvh_decode(const float* channels, int S, const int* frames, const int* dfs, int order, float scale, const float* root_rest, float* poses_out,
@@ -174,22 +170,11 @@ inline int bvh_decode(const float* channels, int S, const int* frames, const int
     if (!dfs || !bvh_dfs_ok(dfs)) return amuse_failf(AMUSE_EINVAL, "amuse_bvh_decode: dfs must be a permutation of 0..54 (amuse_bvh_layout)");
     if (!(scale > 0.f) || !std::isfinite(scale)) return amuse_failf(AMUSE_EINVAL, "amuse_bvh_decode: scale %g must be positive and finite", (double)scale);
     if (!channels || !root_rest || !poses_out || !trans_out) return amuse_failf(AMUSE_EINVAL, "amuse_bvh_decode: channels, root_rest, poses_out and trans_out must be given");
-    long long row0 = 0;
-    for (int s0 = 0; s0 < S; s0 += kBvhMaxSeq) {
-        BvhDecodeArgs a{};
-        a.channels = channels; a.root_rest = root_rest; a.poses_out = poses_out; a.trans_out = trans_out;
-        a.scale = scale; a.ai = ax[0]; a.aj = ax[1]; a.ak = ax[2];
-        for (int c = 0; c < kBvhJoints; ++c) a.dfs[c] = (unsigned char)dfs[c];
-        a.nseq = S - s0 < kBvhMaxSeq ? S - s0 : kBvhMaxSeq;
-        for (int k = 0; k < a.nseq; ++k) {
-            a.seq[k] = BvhSeq{row0, frames[s0 + k], s0 + k};
-            row0 += frames[s0 + k];
-            if (frames[s0 + k] > a.max_F) a.max_F = frames[s0 + k];
-        }
-        const hipError_t err = launch_bvh_decode(a, stream);
-        if (err != hipSuccess) return amuse_failf(AMUSE_EHIP, "amuse_bvh_decode: launch failed: %s", hipGetErrorString(err));
-    }
-    return AMUSE_OK;
+    BvhDecodeArgs p{};
+    p.channels = channels; p.root_rest = root_rest; p.poses_out = poses_out; p.trans_out = trans_out;
+    p.scale = scale; p.ai = ax[0]; p.aj = ax[1]; p.ak = ax[2];
+    for (int c = 0; c < kSmplxJoints; ++c) p.dfs[c] = (unsigned char)dfs[c];
+    return launch_sequences("amuse_bvh_decode", S, p, BvhFill{frames}, launch_bvh_decode, stream);
 }
 
 }  // namespace amuse

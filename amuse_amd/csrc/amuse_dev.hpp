@@ -816,6 +816,7 @@ __device__ __forceinline__ void rot6d_to_axis_angle(const float* d6, int quat_mo
         qw /= den; qx /= den; qy /= den; qz /= den;
     }
     // quaternion_to_axis_angle (rotation_conversions.py:480-509)
+    // (amuse_rot.hpp quat_to_aa is the other statement of these lines: the motion kernels use that one, the decode units keep this one and their ISA)
     const float nrm = sqrtf(qx * qx + qy * qy + qz * qz);
     const float half = atan2f(nrm, qw);
     const float ang = 2.0f * half;

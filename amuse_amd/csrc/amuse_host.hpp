@@ -15,9 +15,8 @@
 #include "../../include/amuse_hip.h"
 #include "amuse_dev.hpp"
 #include "amuse_kernels.hpp"
+#include "amuse_seq_host.hpp"
 
-// error slot of the C ABI (thread-local text behind amuse_last_error; defined in amuse_api.hip)
-__attribute__((visibility("hidden"), format(printf, 2, 3))) int amuse_failf(int code, const char* fmt, ...);
 #define fail(...) amuse_failf(__VA_ARGS__)
 
 namespace amuse {

@@ -13,12 +13,10 @@
 #include <cstddef>
 
 #include "../../include/amuse_hip.h"
-
-__attribute__((visibility("hidden"), format(printf, 2, 3))) int amuse_failf(int code, const char* fmt, ...);
+#include "amuse_seq_host.hpp"
 
 namespace amuse {
 
-constexpr int kMetricsJoints = 55;                      // SMPL-X joints of a frame: 165 contiguous floats
 constexpr int kMetricsWaves = 8;                        // waves of a clip's workgroup: each walks a contiguous eighth of the clip's frames
 constexpr int kMetricsBlock = 64 * kMetricsWaves;
 constexpr int kMetricsPartials = 19;                    // doubles a lane hands over after the first pass (the second pass reuses 12 of the slots)

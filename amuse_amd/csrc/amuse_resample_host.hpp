@@ -15,8 +15,7 @@
 #include <vector>
 
 #include "../../include/amuse_hip.h"
-
-__attribute__((visibility("hidden"), format(printf, 2, 3))) int amuse_failf(int code, const char* fmt, ...);
+#include "amuse_seq_host.hpp"
 
 namespace amuse {
 

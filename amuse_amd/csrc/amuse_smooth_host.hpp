@@ -2,8 +2,7 @@
 // and its launcher), amuse_smooth.hip (the two C entry points) and tests/smooth_host (the same host code on a stand-in launcher, under sanitizers):
 //   - the bank: the hat matrices H_1 .. H_15 of the local polynomial fit, in double, rounded to fp32;
 //   - the argument checks of the filter, made before any HIP call;
-//   - the packing of the call's sequences into launches: per-sequence offsets and the 56 half-windows travel BY VALUE in the kernel arguments (no device table,
-//     no copy, no allocation, so the call can sit inside a captured graph), kSmoothMaxSeq sequences per launch, further sequences in further launches.
+//   - the call's sequences, packed into launches by amuse_seq_host.hpp; the 56 half-windows travel by value beside them.
 // Context-free: nothing here reads or keeps state.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -11,17 +10,12 @@
 #include <climits>
 #include <cmath>
 #include <cstddef>
-#include <cstdint>
 
 #include "../../include/amuse_hip.h"
-
-__attribute__((visibility("hidden"), format(printf, 2, 3))) int amuse_failf(int code, const char* fmt, ...);
+#include "amuse_seq_host.hpp"
 
 namespace amuse {
 
-constexpr int kSmoothMaxSeq = 32;                         // sequences per launch: 32 x 8 B of offsets + 56 B of half-windows + 5 pointers, far inside 4 KiB
-constexpr int kSmoothJoints = 55;                         // SMPL-X joints of a pose row
-constexpr int kSmoothSlots = 56;                          // per frame: one slot per joint, one for the translation
 constexpr int kSmoothMaxHalf = AMUSE_SMOOTH_MAX_HALF;     // m <= 15: windows up to 31 frames
 constexpr int kSmoothMaxOrder = 5;
 constexpr int kSmoothBankFloats = AMUSE_SMOOTH_BANK_FLOATS;
@@ -46,8 +40,8 @@ struct SmoothArgs {
     float* poses_out;        // [frames][55][3]
     float* trans_out;        // [frames][3] or null
     int nseq, max_L, halo;   // halo: the largest half-window a slot of this call filters with (rows loaded on either side of a tile)
-    unsigned char hw[kSmoothSlots];
-    SmoothSeq seq[kSmoothMaxSeq];
+    unsigned char hw[kMotionSlots];
+    SmoothSeq seq[kSeqPerLaunch];
 };
 
 // k_smooth.hip (tests/smooth_host: a stand-in that records the arguments)
@@ -93,11 +87,6 @@ inline int smooth_banks(int order, float* out) {
 }
 
 // ---- the filter's argument checks: everything that can be refused without touching the GPU
-inline bool smooth_overlap(const float* a, long long a_floats, const float* b, long long b_floats) {
-    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
-    return pa < pb + (uintptr_t)b_floats * sizeof(float) && pb < pa + (uintptr_t)a_floats * sizeof(float);
-}
-
 inline int smooth_check(const float* poses, const float* trans, int S, const int* frames, const unsigned char* half_window, const float* banks, float* poses_out,
                         float* trans_out) {
     if (S < 1) return amuse_failf(AMUSE_EINVAL, "amuse_smooth_motion: S %d < 1", S);
@@ -107,44 +96,37 @@ inline int smooth_check(const float* poses, const float* trans, int S, const int
         if (frames[s] < 1) return amuse_failf(AMUSE_EINVAL, "amuse_smooth_motion: sequence %d has %d frames", s, frames[s]);
         total += frames[s];
         // frames and the (frame, slot) index are ints in the kernel; it forms its element offsets in 64 bits
-        if (total * kSmoothSlots > INT_MAX) return amuse_failf(AMUSE_EINVAL, "amuse_smooth_motion: more frames in one call than the kernel's int indices hold");
+        if (total * kMotionSlots > INT_MAX) return amuse_failf(AMUSE_EINVAL, "amuse_smooth_motion: more frames in one call than the kernel's int indices hold");
     }
-    for (int i = 0; i < kSmoothSlots; ++i)
+    for (int i = 0; i < kMotionSlots; ++i)
         if (half_window[i] > kSmoothMaxHalf)
             return amuse_failf(AMUSE_EINVAL, "amuse_smooth_motion: half_window[%d] = %d above %d", i, (int)half_window[i], kSmoothMaxHalf);
     if (!poses || !poses_out || !banks) return amuse_failf(AMUSE_EINVAL, "amuse_smooth_motion: poses, poses_out and banks_dev must be given");
     if ((trans == nullptr) != (trans_out == nullptr)) return amuse_failf(AMUSE_EINVAL, "amuse_smooth_motion: trans and trans_out are NULL together");
     // the filter reads a frame's neighbours: an output that overlaps an input would be read after it was written
-    const long long np = total * kSmoothJoints * 3, nt = total * 3;
-    bool ov = smooth_overlap(poses_out, np, poses, np);
-    if (trans) ov = ov || smooth_overlap(trans_out, nt, trans, nt) || smooth_overlap(poses_out, np, trans, nt) || smooth_overlap(trans_out, nt, poses, np);
+    const long long np = total * kSmplxJoints * 3, nt = total * 3;
+    bool ov = ranges_overlap(poses_out, np, poses, np);
+    if (trans) ov = ov || ranges_overlap(trans_out, nt, trans, nt) || ranges_overlap(poses_out, np, trans, nt) || ranges_overlap(trans_out, nt, poses, np);
     if (ov) return amuse_failf(AMUSE_EINVAL, "amuse_smooth_motion: an output range overlaps an input range (the filter reads a frame's neighbours: not in place)");
     return AMUSE_OK;
 }
 
-// ---- checks, then the sequences in launches of up to kSmoothMaxSeq
-inline int smooth_motion(const float* poses, const float* trans, int S, const int* frames, const unsigned char* half_window, const float* banks, float* poses_out,
+// ---- checks, then the sequences in launches (hidden: only the C entry point calls it, and the library exports no new name for it)
+__attribute__((visibility("hidden"))) inline int smooth_motion(const float* poses, const float* trans, int S, const int* frames, const unsigned char* half_window, const float* banks, float* poses_out,
                          float* trans_out, hipStream_t stream) {
     if (int rc = smooth_check(poses, trans, S, frames, half_window, banks, poses_out, trans_out)) return rc;
-    int halo = 0;
-    for (int i = 0; i < (trans ? kSmoothSlots : kSmoothJoints); ++i)
-        if (half_window[i] > halo) halo = half_window[i];
+    SmoothArgs p{};
+    p.poses = poses; p.trans = trans; p.banks = banks; p.poses_out = poses_out; p.trans_out = trans_out;
+    for (int i = 0; i < (trans ? kMotionSlots : kSmplxJoints); ++i)
+        if (half_window[i] > p.halo) p.halo = half_window[i];
+    for (int i = 0; i < kMotionSlots; ++i) p.hw[i] = half_window[i];
     int row0 = 0;
-    for (int s0 = 0; s0 < S; s0 += kSmoothMaxSeq) {
-        SmoothArgs a{};
-        a.poses = poses; a.trans = trans; a.banks = banks; a.poses_out = poses_out; a.trans_out = trans_out;
-        a.halo = halo;
-        for (int i = 0; i < kSmoothSlots; ++i) a.hw[i] = half_window[i];
-        a.nseq = S - s0 < kSmoothMaxSeq ? S - s0 : kSmoothMaxSeq;
-        for (int k = 0; k < a.nseq; ++k) {
-            a.seq[k] = SmoothSeq{row0, frames[s0 + k]};
-            row0 += frames[s0 + k];
-            if (frames[s0 + k] > a.max_L) a.max_L = frames[s0 + k];
-        }
-        const hipError_t e = launch_smooth(a, stream);
-        if (e != hipSuccess) return amuse_failf(AMUSE_EHIP, "amuse_smooth_motion: launch failed: %s", hipGetErrorString(e));
-    }
-    return AMUSE_OK;
+    auto fill = [&](SmoothArgs& a, int k, int s) {
+        a.seq[k] = SmoothSeq{row0, frames[s]};
+        row0 += frames[s];
+        if (frames[s] > a.max_L) a.max_L = frames[s];
+    };
+    return launch_sequences("amuse_smooth_motion", S, p, fill, launch_smooth, stream);
 }
 
 }  // namespace amuse

@@ -2,8 +2,7 @@
 // kernel and its launcher), amuse_stitch.hip (the two C entry points) and tests/stitch_host (the same host code on a stand-in launcher, under sanitizers):
 //   - the window plan: the ONE statement of how a waveform of n samples is cut into overlapping clips;
 //   - the argument checks of the join, made before any HIP call;
-//   - the packing of the call's sequences into launches: per-sequence offsets travel BY VALUE in the kernel arguments (no device table, no copy, no allocation,
-//     so the call can sit inside a captured graph), kStitchMaxSeq sequences per launch, further sequences in further launches.
+//   - the call's sequences, packed into launches by amuse_seq_host.hpp.
 // Context-free: nothing here reads or keeps state.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -12,14 +11,10 @@
 #include <cstddef>
 
 #include "../../include/amuse_hip.h"
-
-__attribute__((visibility("hidden"), format(printf, 2, 3))) int amuse_failf(int code, const char* fmt, ...);
+#include "amuse_seq_host.hpp"
 
 namespace amuse {
 
-constexpr int kStitchMaxSeq = 32;     // sequences per launch: 32 x 16 B of offsets + 7 pointers / sizes stay far inside the 4 KiB of kernel arguments
-constexpr int kStitchJoints = 55;     // SMPL-X joints of a pose row
-constexpr int kStitchSlots = 56;      // threads per output frame: one per joint, one for the translation
 constexpr int kStitchBlock = 256;
 
 constexpr int kClipFrames = 300;          // the model's clip (dm/dm.py:91)
@@ -39,7 +34,7 @@ struct StitchArgs {
     float* poses_out;      // [frames][55][3]
     float* trans_out;      // [frames][3] or null
     int F, hop, nseq, max_L;
-    StitchSeq seq[kStitchMaxSeq];
+    StitchSeq seq[kSeqPerLaunch];
 };
 
 // k_stitch.hip (tests/stitch_host: a stand-in that records the arguments)
@@ -78,7 +73,7 @@ inline int stitch_check(const float* poses, const float* trans, int S, const int
         wins += W;
         out += L;
         // window rows, output frames and the (frame, slot) thread index are ints in the kernel; it forms its element offsets in 64 bits
-        if (wins * F > INT_MAX || out * kStitchSlots > INT_MAX) return amuse_failf(AMUSE_EINVAL, "amuse_stitch_windows: more frames in one call than the kernel's int indices hold");
+        if (wins * F > INT_MAX || out * kMotionSlots > INT_MAX) return amuse_failf(AMUSE_EINVAL, "amuse_stitch_windows: more frames in one call than the kernel's int indices hold");
     }
     if (!poses || !poses_out) return amuse_failf(AMUSE_EINVAL, "amuse_stitch_windows: poses and poses_out must be given");
     if (!blend && hop < F) return amuse_failf(AMUSE_EINVAL, "amuse_stitch_windows: blend is NULL with an overlap of %d frames", F - hop);
@@ -86,26 +81,21 @@ inline int stitch_check(const float* poses, const float* trans, int S, const int
     return AMUSE_OK;
 }
 
-// ---- checks, then the sequences in launches of up to kStitchMaxSeq
-inline int stitch_windows(const float* poses, const float* trans, int S, const int* windows, const int* frames, int F, int hop, const float* blend, float* poses_out,
+// ---- checks, then the sequences in launches (hidden: only the C entry point calls it, and the library exports no new name for it)
+__attribute__((visibility("hidden"))) inline int stitch_windows(const float* poses, const float* trans, int S, const int* windows, const int* frames, int F, int hop, const float* blend, float* poses_out,
                           float* trans_out, hipStream_t stream) {
     if (int rc = stitch_check(poses, trans, S, windows, frames, F, hop, blend, poses_out, trans_out)) return rc;
+    StitchArgs p{};
+    p.poses = poses; p.trans = trans; p.blend = blend; p.poses_out = poses_out; p.trans_out = trans_out;
+    p.F = F; p.hop = hop;
     int win0 = 0, out0 = 0;
-    for (int s0 = 0; s0 < S; s0 += kStitchMaxSeq) {
-        StitchArgs a{};
-        a.poses = poses; a.trans = trans; a.blend = blend; a.poses_out = poses_out; a.trans_out = trans_out;
-        a.F = F; a.hop = hop;
-        a.nseq = S - s0 < kStitchMaxSeq ? S - s0 : kStitchMaxSeq;
-        for (int k = 0; k < a.nseq; ++k) {
-            a.seq[k] = StitchSeq{win0, out0, windows[s0 + k], frames[s0 + k]};
-            win0 += windows[s0 + k];
-            out0 += frames[s0 + k];
-            if (frames[s0 + k] > a.max_L) a.max_L = frames[s0 + k];
-        }
-        const hipError_t e = launch_stitch(a, stream);
-        if (e != hipSuccess) return amuse_failf(AMUSE_EHIP, "amuse_stitch_windows: launch failed: %s", hipGetErrorString(e));
-    }
-    return AMUSE_OK;
+    auto fill = [&](StitchArgs& a, int k, int s) {
+        a.seq[k] = StitchSeq{win0, out0, windows[s], frames[s]};
+        win0 += windows[s];
+        out0 += frames[s];
+        if (frames[s] > a.max_L) a.max_L = frames[s];
+    };
+    return launch_sequences("amuse_stitch_windows", S, p, fill, launch_stitch, stream);
 }
 
 }  // namespace amuse

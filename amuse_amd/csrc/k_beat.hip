@@ -163,11 +163,11 @@ __global__ void __launch_bounds__(kBeatAlignBlock) k_beat_align(const BeatAlignA
     const int n = blockIdx.x, lane = threadIdx.x;
     const int L = a.lengths[n];
     double* __restrict__ row = a.rows + (size_t)n * kBeatRow;
-    unsigned char* __restrict__ bm = a.beat_mask ? a.beat_mask + (size_t)n * a.F * kBeatJoints : nullptr;
+    unsigned char* __restrict__ bm = a.beat_mask ? a.beat_mask + (size_t)n * a.F * kSmplxJoints : nullptr;
     if (L < 2 || L > a.F) {                              // (uniform over the workgroup)
         for (int i = lane; i < kBeatRow; i += kBeatAlignBlock) row[i] = __builtin_nan("");
         if (bm)
-            for (size_t i = lane; i < (size_t)a.F * kBeatJoints; i += kBeatAlignBlock) bm[i] = 0;
+            for (size_t i = lane; i < (size_t)a.F * kSmplxJoints; i += kBeatAlignBlock) bm[i] = 0;
         return;
     }
     const double fps = a.p.fps, two_s2 = 2.0 * a.p.sigma_s * a.p.sigma_s;
@@ -193,9 +193,9 @@ __global__ void __launch_bounds__(kBeatAlignBlock) k_beat_align(const BeatAlignA
     }
     __syncthreads();
 
-    const bool live = lane < kBeatJoints;
+    const bool live = lane < kSmplxJoints;
     const int j = live ? lane : 0;                       // the nine idle lanes walk joint 0 and write nothing
-    const float* __restrict__ X = a.joints + (size_t)n * a.F * (kBeatJoints * 3) + j * 3;
+    const float* __restrict__ X = a.joints + (size_t)n * a.F * (kSmplxJoints * 3) + j * 3;
     const int k = a.p.motion_order, R = 2 * k + 1, last = L - 2;
     double x0 = (double)X[0], y0 = (double)X[1], z0 = (double)X[2];
     int ptr = next_onset(bits, 0, t_end);                // the lane's next unsettled onset
@@ -203,7 +203,7 @@ __global__ void __launch_bounds__(kBeatAlignBlock) k_beat_align(const BeatAlignA
     double a2m = 0.0, m2a = 0.0;
     for (int f = 0; f <= last + k; ++f) {
         if (f <= last) {                                 // frames below L only: anything may sit beyond
-            const float* __restrict__ p = X + (size_t)(f + 1) * (kBeatJoints * 3);
+            const float* __restrict__ p = X + (size_t)(f + 1) * (kSmplxJoints * 3);
             const double x1 = (double)p[0], y1 = (double)p[1], z1 = (double)p[2];
             const double dx = x1 - x0, dy = y1 - y0, dz = z1 - z0;
             ring[f % R][lane] = sqrt(dx * dx + dy * dy + dz * dz) * fps;
@@ -217,7 +217,7 @@ __global__ void __launch_bounds__(kBeatAlignBlock) k_beat_align(const BeatAlignA
             const int lo = g - i < 0 ? 0 : g - i, hi = g + i > last ? last : g + i;     // clipped onto g itself: c < c fails
             beat = beat && c < ring[lo % R][lane] && c < ring[hi % R][lane];
         }
-        if (bm && live) bm[(size_t)g * kBeatJoints + j] = beat ? 1 : 0;
+        if (bm && live) bm[(size_t)g * kSmplxJoints + j] = beat ? 1 : 0;
         if (!beat) continue;
         const double tm = ((double)g + 0.5) / fps;
         while (ptr < t_end) {                            // the onsets since the last beat, up to this one: each is nearest to one of the two
@@ -247,7 +247,7 @@ __global__ void __launch_bounds__(kBeatAlignBlock) k_beat_align(const BeatAlignA
         }
     }
     if (bm)
-        for (size_t i = (size_t)(L - 1) * kBeatJoints + lane; i < (size_t)a.F * kBeatJoints; i += kBeatAlignBlock) bm[i] = 0;
+        for (size_t i = (size_t)(L - 1) * kSmplxJoints + lane; i < (size_t)a.F * kSmplxJoints; i += kBeatAlignBlock) bm[i] = 0;
     if (!live) return;
     if (j == 0) row[kBeatRowOnsets] = (double)n_on;
     row[kBeatRowBeats + j] = (double)nb;

@@ -14,6 +14,7 @@
 // A sequence's bytes depend on its own rows alone: every value is computed by one lane from that lane's inputs, with no reduction and no exchange.
 #include "amuse_bvh_host.hpp"
 #include "amuse_dev.hpp"
+#include "amuse_rot.hpp"
 
 namespace amuse {
 
@@ -56,16 +57,6 @@ __global__ void __launch_bounds__(kBvhBlock) k_bvh_format(const float* __restric
     unsigned* dst = text + i * 3;
     dst[0] = w[0]; dst[1] = w[1]; dst[2] = w[2];
     if (!ok) *status = 1;
-}
-
-// axis-angle -> unit quaternion: half-angle sine and cosine, the sine term by its series below 1e-3 (sin(t / 2) / t = 1 / 2 - t^2 / 48 + ...: the next term is
-// below 2^-24 of the first there)
-__device__ __forceinline__ void bvh_aa_to_quat(float x, float y, float z, float (&q)[3], float& w) {
-    const float ang = sqrtf(x * x + y * y + z * z);
-    const float half = 0.5f * ang;
-    const float s = (ang < 1e-3f) ? (0.5f - (ang * ang) / 48.0f) : (sinf(half) / ang);
-    w = cosf(half);
-    q[0] = x * s; q[1] = y * s; q[2] = z * s;
 }
 
 // (selects, not an indexed register array: no scratch)
@@ -114,11 +105,11 @@ __device__ __forceinline__ void bvh_emit3(const BvhArgs& a, long long row, int c
 __global__ void __launch_bounds__(kBvhBlock) k_bvh_motion(const BvhArgs a) {
     const BvhSeq sq = a.seq[blockIdx.y];
     const int i = blockIdx.x * kBvhBlock + threadIdx.x;                  // (F <= kBvhMaxFrames: checked on the host)
-    if (i >= sq.F * kBvhSlots) return;
-    const int f = i / kBvhSlots, c = i - f * kBvhSlots;
+    if (i >= sq.F * kMotionSlots) return;
+    const int f = i / kMotionSlots, c = i - f * kMotionSlots;
     const long long row = sq.row0 + f;
     float v[3];
-    if (c == kBvhJoints) {                                               // the root's position: (J_rest[0] + trans) x scale
+    if (c == kSmplxJoints) {                                               // the root's position: (J_rest[0] + trans) x scale
         const float* rr = a.root_rest + 3 * sq.s;
         float t0 = 0.f, t1 = 0.f, t2 = 0.f;
         if (a.trans) { const float* t = a.trans + row * 3; t0 = t[0]; t1 = t[1]; t2 = t[2]; }
@@ -126,10 +117,10 @@ __global__ void __launch_bounds__(kBvhBlock) k_bvh_motion(const BvhArgs a) {
         bvh_emit3(a, row, 0, v, sq.s);
         return;
     }
-    const float* p = a.poses + (row * kBvhJoints + a.dfs[c]) * 3;
-    float q[3], w;
-    bvh_aa_to_quat(p[0], p[1], p[2], q, w);
-    bvh_euler(q, w, a.ai, a.aj, a.ak, a.e, v);
+    const float* p = a.poses + (row * kSmplxJoints + a.dfs[c]) * 3;
+    const Quat qu = aa_to_quat(p[0], p[1], p[2], 1e-3f);              // the series from 1e-3 down (its next term is below 2^-24 there): the bits the export was pinned with
+    const float q[3] = {qu.x, qu.y, qu.z};
+    bvh_euler(q, qu.w, a.ai, a.aj, a.ak, a.e, v);
     const int col = 3 + 3 * c;
     if (!a.unwrap) {
         bvh_emit3(a, row, col, v, sq.s);
@@ -147,8 +138,8 @@ __device__ __forceinline__ float bvh_near(float x, float prev) { return x + 360.
 
 __global__ void __launch_bounds__(kBvhWalkBlock) k_bvh_walk(const BvhArgs a) {
     const int i = blockIdx.x * kBvhWalkBlock + threadIdx.x;
-    if (i >= a.nseq * kBvhJoints) return;
-    const int k = i / kBvhJoints, c = i - k * kBvhJoints;
+    if (i >= a.nseq * kSmplxJoints) return;
+    const int k = i / kSmplxJoints, c = i - k * kSmplxJoints;
     const BvhSeq sq = a.seq[k];
     const int col = 3 + 3 * c;
     float prev[3] = {0.f, 0.f, 0.f};
@@ -179,11 +170,11 @@ __global__ void __launch_bounds__(kBvhWalkBlock) k_bvh_walk(const BvhArgs a) {
 __global__ void __launch_bounds__(kBvhBlock) k_bvh_decode(const BvhDecodeArgs a) {
     const BvhSeq sq = a.seq[blockIdx.y];
     const int i = blockIdx.x * kBvhBlock + threadIdx.x;
-    if (i >= sq.F * kBvhSlots) return;
-    const int f = i / kBvhSlots, c = i - f * kBvhSlots;
+    if (i >= sq.F * kMotionSlots) return;
+    const int f = i / kMotionSlots, c = i - f * kMotionSlots;
     const long long row = sq.row0 + f;
     const float* src = a.channels + row * kBvhCols;
-    if (c == kBvhJoints) {                                               // trans = position / scale - J_rest[0]
+    if (c == kSmplxJoints) {                                               // trans = position / scale - J_rest[0]
         const float* rr = a.root_rest + 3 * sq.s;
         float* dst = a.trans_out + row * 3;
         dst[0] = src[0] / a.scale - rr[0]; dst[1] = src[1] / a.scale - rr[1]; dst[2] = src[2] / a.scale - rr[2];
@@ -214,7 +205,7 @@ __global__ void __launch_bounds__(kBvhBlock) k_bvh_decode(const BvhDecodeArgs a)
         const float g = (n - 6.283185307179586f) / n;
         aa[0] *= g; aa[1] *= g; aa[2] *= g;
     }
-    float* dst = a.poses_out + (row * kBvhJoints + a.dfs[c]) * 3;
+    float* dst = a.poses_out + (row * kSmplxJoints + a.dfs[c]) * 3;
     dst[0] = aa[0]; dst[1] = aa[1]; dst[2] = aa[2];
 }
 
@@ -227,16 +218,16 @@ hipError_t launch_bvh_format(const float* values, long long n, int per_row, unsi
 }
 
 hipError_t launch_bvh_motion(const BvhArgs& a, hipStream_t stream) {
-    const dim3 grid((unsigned)(((long long)a.max_F * kBvhSlots + kBvhBlock - 1) / kBvhBlock), (unsigned)a.nseq);
+    const dim3 grid((unsigned)(((long long)a.max_F * kMotionSlots + kBvhBlock - 1) / kBvhBlock), (unsigned)a.nseq);
     hipLaunchKernelGGL(k_bvh_motion, grid, dim3(kBvhBlock), 0, stream, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || !a.unwrap) return e;
-    hipLaunchKernelGGL(k_bvh_walk, dim3((unsigned)((a.nseq * kBvhJoints + kBvhWalkBlock - 1) / kBvhWalkBlock)), dim3(kBvhWalkBlock), 0, stream, a);
+    hipLaunchKernelGGL(k_bvh_walk, dim3((unsigned)((a.nseq * kSmplxJoints + kBvhWalkBlock - 1) / kBvhWalkBlock)), dim3(kBvhWalkBlock), 0, stream, a);
     return hipGetLastError();
 }
 
 hipError_t launch_bvh_decode(const BvhDecodeArgs& a, hipStream_t stream) {
-    const dim3 grid((unsigned)(((long long)a.max_F * kBvhSlots + kBvhBlock - 1) / kBvhBlock), (unsigned)a.nseq);
+    const dim3 grid((unsigned)(((long long)a.max_F * kMotionSlots + kBvhBlock - 1) / kBvhBlock), (unsigned)a.nseq);
     hipLaunchKernelGGL(k_bvh_decode, grid, dim3(kBvhBlock), 0, stream, a);
     return hipGetLastError();
 }

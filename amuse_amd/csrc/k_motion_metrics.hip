@@ -30,10 +30,10 @@ __global__ void __launch_bounds__(kMetricsBlock) k_motion_metrics(const MotionMe
         for (int i = threadIdx.x; i < kMetricsRow; i += kMetricsBlock) row[i] = __builtin_nan("");
         return;
     }
-    const bool live = lane < kMetricsJoints;
+    const bool live = lane < kSmplxJoints;
     const int j = live ? lane : 0;                       // the nine idle lanes walk joint 0 and write nothing
-    const float* __restrict__ G = a.gen + (size_t)n * a.F * (kMetricsJoints * 3);
-    const float* __restrict__ R = a.ref + (size_t)n * a.F * (kMetricsJoints * 3);
+    const float* __restrict__ G = a.gen + (size_t)n * a.F * (kSmplxJoints * 3);
+    const float* __restrict__ R = a.ref + (size_t)n * a.F * (kSmplxJoints * 3);
     const int chunk = (L + kMetricsWaves - 1) / kMetricsWaves;
     const int f0 = wave * chunk < L ? wave * chunk : L, f1 = f0 + chunk < L ? f0 + chunk : L;   // frames below L only: anything may sit beyond
 

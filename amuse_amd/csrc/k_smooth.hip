@@ -14,57 +14,40 @@
 // the same bytes.  55,552 B let two workgroups share a CU (2 waves per SIMD); the register bound of tests/test_smooth_isa_cpu.py keeps that.
 // Bank rows are read through L2, not staged: the lanes of a frame that share m read the SAME row (one address per load, a broadcast), and every interior frame
 // of the call reads row m of its H_m - a few hundred bytes that stay in the caches.
-// No atomics, no double, no matrix-core instruction, no scratch.  amuse_dev.hpp holds no quaternion helper of its own (its rotation code, rot6d_to_axis_angle,
-// starts from 6D and ends in the decode tail's quaternion -> axis-angle lines): as in k_stitch.hip that arithmetic is restated here, in a unit of its own.
+// No atomics, no double, no matrix-core instruction, no scratch.  The quaternion arithmetic is amuse_rot.hpp's; the tile stays float4 (.x = w, .y .z .w = the
+// vector part) and is converted where it is stored and loaded.
+#include "amuse_rot.hpp"
 #include "amuse_smooth_host.hpp"
 
 namespace amuse {
 
 namespace {
 
-// axis-angle -> unit quaternion (w, x, y, z): the decode tail's series read the other way (sin(a / 2) / a -> 1 / 2 - a^2 / 48), as k_stitch.hip has it
-__device__ __forceinline__ float4 smooth_aa_to_quat(float x, float y, float z) {
-    const float ang = sqrtf(x * x + y * y + z * z);
-    const float half = 0.5f * ang;
-    const float s = (ang < 1e-6f) ? (0.5f - (ang * ang) / 48.0f) : (sinf(half) / ang);
-    return make_float4(cosf(half), x * s, y * s, z * s);
-}
+__device__ __forceinline__ Quat tile_quat(const float4 v) { return Quat{v.x, v.y, v.z, v.w}; }
 
-// one joint of one frame: qc the frame's own quaternion, win the first float4 of its window (stride kSmoothSlots), h the bank row, n = 2 m + 1
-__device__ __forceinline__ void smooth_joint(const float4 qc, const float4* win, const float* __restrict__ h, int n, float (&out)[3]) {
+// one joint of one frame: qc the frame's own quaternion, win the first float4 of its window (stride kMotionSlots), h the bank row, n = 2 m + 1
+__device__ __forceinline__ void smooth_joint(const Quat qc, const float4* win, const float* __restrict__ h, int n, float (&out)[3]) {
     float vx = 0.f, vy = 0.f, vz = 0.f;
     for (int k = 0; k < n; ++k) {
-        const float4 q = win[k * kSmoothSlots];
-        // d = conj(qc) q
-        float dw = qc.x * q.x + qc.y * q.y + qc.z * q.z + qc.w * q.w;      // (float4 .x = w, .y .z .w = the vector part)
-        float dx = qc.x * q.y - qc.y * q.x - qc.z * q.w + qc.w * q.z;
-        float dy = qc.x * q.z + qc.y * q.w - qc.z * q.x - qc.w * q.y;
-        float dz = qc.x * q.w - qc.y * q.z + qc.z * q.y - qc.w * q.x;
+        const Quat d = quat_conj_mul(qc, tile_quat(win[k * kMotionSlots]));
+        float dw = d.w, dx = d.x, dy = d.y, dz = d.z;
         if (dw < 0.f) { dw = -dw; dx = -dx; dy = -dy; dz = -dz; }          // the shorter arc
         const float nv = sqrtf(dx * dx + dy * dy + dz * dz);
         const float fac = (nv < 1e-6f) ? 2.0f : (2.0f * atan2f(nv, dw)) / nv;
         const float w = h[k] * fac;
         vx += w * dx; vy += w * dy; vz += w * dz;
     }
-    const float4 e = smooth_aa_to_quat(vx, vy, vz);
-    // qc e
-    float qw = qc.x * e.x - qc.y * e.y - qc.z * e.z - qc.w * e.w;
-    float qx = qc.x * e.y + qc.y * e.x + qc.z * e.w - qc.w * e.z;
-    float qy = qc.x * e.z - qc.y * e.w + qc.z * e.x + qc.w * e.y;
-    float qz = qc.x * e.w + qc.y * e.z - qc.z * e.y + qc.w * e.x;
-    float inv = 1.f / sqrtf(qw * qw + qx * qx + qy * qy + qz * qz);
-    if (qw < 0.f) inv = -inv;                                               // smoothed frames carry the short representation
-    qw *= inv; qx *= inv; qy *= inv; qz *= inv;
-    // quaternion_to_axis_angle (amuse_dev.hpp rot6d_to_axis_angle; rotation_conversions.py:480-509)
-    const float nrm = sqrtf(qx * qx + qy * qy + qz * qz);
-    const float half = atan2f(nrm, qw);
-    const float ang = 2.0f * half;
-    const float s = (fabsf(ang) < 1e-6f) ? (0.5f - (ang * ang) / 48.0f) : (sinf(half) / ang);
-    out[0] = qx / s; out[1] = qy / s; out[2] = qz / s;
+    const Quat e = aa_to_quat(vx, vy, vz);
+    // qc e, written out: behind a helper the compiler sums qz's first two products the other way round, the FMA takes the other one and the bits move
+    const float qw = qc.w * e.w - qc.x * e.x - qc.y * e.y - qc.z * e.z;
+    const float qx = qc.w * e.x + qc.x * e.w + qc.y * e.z - qc.z * e.y;
+    const float qy = qc.w * e.y - qc.x * e.z + qc.y * e.w + qc.z * e.x;
+    const float qz = qc.w * e.z + qc.x * e.y - qc.y * e.x + qc.z * e.w;
+    quat_to_aa(quat_unit_short(Quat{qw, qx, qy, qz}), out);                // smoothed frames carry the short representation
 }
 
 __global__ void __launch_bounds__(kSmoothBlock) k_smooth(const SmoothArgs a) {
-    __shared__ float4 s_q[kSmoothLdsRows * kSmoothSlots];
+    __shared__ float4 s_q[kSmoothLdsRows * kMotionSlots];
     const SmoothSeq sq = a.seq[blockIdx.y];
     const int t0 = blockIdx.x * kSmoothTile;
     if (t0 >= sq.L) return;                                    // (uniform: the grid's x covers the launch's longest sequence)
@@ -76,27 +59,28 @@ __global__ void __launch_bounds__(kSmoothBlock) k_smooth(const SmoothArgs a) {
     const int hi = t0 + kSmoothTile + a.halo < sq.L ? t0 + kSmoothTile + a.halo : sq.L;
     const int nt = sq.L - t0 < kSmoothTile ? sq.L - t0 : kSmoothTile;
     const size_t row_lo = (size_t)sq.row0 + lo;
-    const float* __restrict__ src = a.poses + row_lo * (kSmoothJoints * 3);
-    for (int i = threadIdx.x; i < (hi - lo) * kSmoothSlots; i += kSmoothBlock) {
-        const int row = i / kSmoothSlots, j = i - row * kSmoothSlots;
-        if (j < kSmoothJoints) {
-            const float* p = src + (row * kSmoothJoints + j) * 3;
-            s_q[i] = smooth_aa_to_quat(p[0], p[1], p[2]);
+    const float* __restrict__ src = a.poses + row_lo * (kSmplxJoints * 3);
+    for (int i = threadIdx.x; i < (hi - lo) * kMotionSlots; i += kSmoothBlock) {
+        const int row = i / kMotionSlots, j = i - row * kMotionSlots;
+        if (j < kSmplxJoints) {
+            const float* p = src + (row * kSmplxJoints + j) * 3;
+            const Quat q = aa_to_quat(p[0], p[1], p[2]);
+            s_q[i] = make_float4(q.w, q.x, q.y, q.z);
         } else if (has_trans) {
             const float* p = a.trans + (row_lo + row) * 3;
             s_q[i] = make_float4(p[0], p[1], p[2], 0.f);
         }
     }
     __syncthreads();
-    for (int i = threadIdx.x; i < nt * kSmoothSlots; i += kSmoothBlock) {
-        const int fl = i / kSmoothSlots, j = i - fl * kSmoothSlots;
-        const bool is_trans = j == kSmoothJoints;
+    for (int i = threadIdx.x; i < nt * kMotionSlots; i += kSmoothBlock) {
+        const int fl = i / kMotionSlots, j = i - fl * kMotionSlots;
+        const bool is_trans = j == kSmplxJoints;
         if (is_trans && !has_trans) continue;
         const int f = t0 + fl, m = a.hw[j], n = 2 * m + 1;
         const size_t row_o = (size_t)sq.row0 + f;
-        float* dst = is_trans ? a.trans_out + row_o * 3 : a.poses_out + (row_o * kSmoothJoints + j) * 3;
+        float* dst = is_trans ? a.trans_out + row_o * 3 : a.poses_out + (row_o * kSmplxJoints + j) * 3;
         if (m == 0 || sq.L < n) {                               // not filtered: the input's bits
-            const float* p = is_trans ? a.trans + row_o * 3 : a.poses + (row_o * kSmoothJoints + j) * 3;
+            const float* p = is_trans ? a.trans + row_o * 3 : a.poses + (row_o * kSmplxJoints + j) * 3;
             const float b0 = p[0], b1 = p[1], b2 = p[2];
             dst[0] = b0; dst[1] = b1; dst[2] = b2;
             continue;
@@ -106,18 +90,18 @@ __global__ void __launch_bounds__(kSmoothBlock) k_smooth(const SmoothArgs a) {
         if (s < 0) s = 0;
         const int r = f - s;                                    // the frame's place in its window: m in the interior, 0 .. 2 m at the two ends
         const float* __restrict__ h = a.banks + smooth_bank_offset(m) + r * n;
-        const float4* win = s_q + (s - lo) * kSmoothSlots + j;  // s >= min(t0 - m, L - 1 - 2 m) >= lo and s + 2 m <= max(min(f + m, L - 1), 2 m) < hi: inside the loaded rows
+        const float4* win = s_q + (s - lo) * kMotionSlots + j;  // s >= min(t0 - m, L - 1 - 2 m) >= lo and s + 2 m <= max(min(f + m, L - 1), 2 m) < hi: inside the loaded rows
         if (is_trans) {
             float x = 0.f, y = 0.f, z = 0.f;
             for (int k = 0; k < n; ++k) {
-                const float4 v = win[k * kSmoothSlots];
+                const float4 v = win[k * kMotionSlots];
                 x += h[k] * v.x; y += h[k] * v.y; z += h[k] * v.z;
             }
             dst[0] = x; dst[1] = y; dst[2] = z;
             continue;
         }
         float o[3];
-        smooth_joint(s_q[(f - lo) * kSmoothSlots + j], win, h, n, o);
+        smooth_joint(tile_quat(s_q[(f - lo) * kMotionSlots + j]), win, h, n, o);
         dst[0] = o[0]; dst[1] = o[1]; dst[2] = o[2];
     }
 }

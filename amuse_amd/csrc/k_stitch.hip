@@ -2,25 +2,15 @@
 // ONE motion.  A frame only one window produced - or the later window's part past the overlap - is a bitwise copy of that window's row; a frame two neighbouring
 // windows both produced is their rotation crossfade, joint by joint: axis-angle -> unit quaternion, shorter arc, slerp at the caller's weight, back to axis-angle
 // (the translation: a lerp).  One thread per (output frame, joint | translation): at most 24 B in and 12 B out each, nothing shared, no LDS; the sequence is the
-// grid's y, its offsets sit in the kernel arguments.  A translation unit of its own: the few lines of rotation arithmetic it shares with the decode tail
-// (amuse_dev.hpp rot6d_to_axis_angle's quaternion_to_axis_angle) and with train_gesture.axis_angle_to_rotation_6d's quaternion are restated here.
+// grid's y, its offsets sit in the kernel arguments.  A translation unit of its own; the quaternion conversions are amuse_rot.hpp's.
+#include "amuse_rot.hpp"
 #include "amuse_stitch_host.hpp"
 
 namespace amuse {
 
 namespace {
 
-struct Quat { float w, x, y, z; };
-
-// axis-angle -> unit quaternion, the small-angle series of train_gesture.axis_angle_to_rotation_6d (sin(a / 2) / a -> 1 / 2 - a^2 / 48)
-__device__ __forceinline__ Quat aa_to_quat(float x, float y, float z) {
-    const float ang = sqrtf(x * x + y * y + z * z);
-    const float half = 0.5f * ang;
-    const float s = (ang < 1e-6f) ? (0.5f - (ang * ang) / 48.0f) : (sinf(half) / ang);
-    return Quat{cosf(half), x * s, y * s, z * s};
-}
-
-__device__ __forceinline__ void stitch_joint(const float* __restrict__ a, const float* __restrict__ b, float w, float* __restrict__ out) {
+__device__ __forceinline__ void stitch_joint(const float* __restrict__ a, const float* __restrict__ b, float w, float (&out)[3]) {
     const Quat qa = aa_to_quat(a[0], a[1], a[2]);
     Quat qb = aa_to_quat(b[0], b[1], b[2]);
     float d = qa.w * qb.w + qa.x * qb.x + qa.y * qb.y + qa.z * qb.z;
@@ -31,38 +21,30 @@ __device__ __forceinline__ void stitch_joint(const float* __restrict__ a, const 
     const float so = sinf(omega);
     float ca = 1.f - w, cb = w;                                                           // sin Omega too small to divide by: the slerp's own limit
     if (so >= 1e-4f) { ca = sinf((1.f - w) * omega) / so; cb = sinf(w * omega) / so; }
-    float qw = ca * qa.w + cb * qb.w, qx = ca * qa.x + cb * qb.x, qy = ca * qa.y + cb * qb.y, qz = ca * qa.z + cb * qb.z;
-    float inv = 1.f / sqrtf(qw * qw + qx * qx + qy * qy + qz * qz);
-    if (qw < 0.f) inv = -inv;                                                             // blended frames carry the short representation
-    qw *= inv; qx *= inv; qy *= inv; qz *= inv;
-    // quaternion_to_axis_angle (amuse_dev.hpp rot6d_to_axis_angle; rotation_conversions.py:480-509)
-    const float nrm = sqrtf(qx * qx + qy * qy + qz * qz);
-    const float half = atan2f(nrm, qw);
-    const float ang = 2.0f * half;
-    const float s = (fabsf(ang) < 1e-6f) ? (0.5f - (ang * ang) / 48.0f) : (sinf(half) / ang);
-    out[0] = qx / s; out[1] = qy / s; out[2] = qz / s;
+    const float qw = ca * qa.w + cb * qb.w, qx = ca * qa.x + cb * qb.x, qy = ca * qa.y + cb * qb.y, qz = ca * qa.z + cb * qb.z;
+    quat_to_aa(quat_unit_short(Quat{qw, qx, qy, qz}), out);                               // blended frames carry the short representation
 }
 
 __global__ void __launch_bounds__(kStitchBlock) k_stitch(const StitchArgs a) {
     const StitchSeq sq = a.seq[blockIdx.y];
     const int idx = blockIdx.x * kStitchBlock + threadIdx.x;
-    const int f = idx / kStitchSlots, j = idx - f * kStitchSlots;
+    const int f = idx / kMotionSlots, j = idx - f * kMotionSlots;
     if (f >= sq.L) return;
-    const bool is_trans = j == kStitchJoints;
+    const bool is_trans = j == kSmplxJoints;
     if (is_trans && a.trans == nullptr) return;
     int k = f / a.hop;
     if (k > sq.W - 1) k = sq.W - 1;
     const int i = f - k * a.hop;                       // the frame's row in window k: < F by the entry point's check on L
     const size_t row_b = (size_t)(sq.win0 + k) * a.F + i, row_o = (size_t)sq.out0 + f;
-    const float* src = is_trans ? a.trans + row_b * 3 : a.poses + (row_b * kStitchJoints + j) * 3;
-    float* dst = is_trans ? a.trans_out + row_o * 3 : a.poses_out + (row_o * kStitchJoints + j) * 3;
+    const float* src = is_trans ? a.trans + row_b * 3 : a.poses + (row_b * kSmplxJoints + j) * 3;
+    float* dst = is_trans ? a.trans_out + row_o * 3 : a.poses_out + (row_o * kSmplxJoints + j) * 3;
     const float b0 = src[0], b1 = src[1], b2 = src[2];
     if (k == 0 || i >= a.F - a.hop) {                  // one window's frame: its bits
         dst[0] = b0; dst[1] = b1; dst[2] = b2;
         return;
     }
     const size_t row_a = row_b - a.F + a.hop;          // window k - 1, row i + hop: the same frame
-    const float* pa = is_trans ? a.trans + row_a * 3 : a.poses + (row_a * kStitchJoints + j) * 3;
+    const float* pa = is_trans ? a.trans + row_a * 3 : a.poses + (row_a * kSmplxJoints + j) * 3;
     const float av[3] = {pa[0], pa[1], pa[2]}, bv[3] = {b0, b1, b2};
     const float w = a.blend[i];
     if (is_trans) {
@@ -77,7 +59,7 @@ __global__ void __launch_bounds__(kStitchBlock) k_stitch(const StitchArgs a) {
 }  // namespace
 
 hipError_t launch_stitch(const StitchArgs& a, hipStream_t stream) {
-    const long long threads = (long long)a.max_L * kStitchSlots;
+    const long long threads = (long long)a.max_L * kMotionSlots;
     const dim3 grid((unsigned)((threads + kStitchBlock - 1) / kStitchBlock), (unsigned)a.nseq);
     hipLaunchKernelGGL(k_stitch, grid, dim3(kStitchBlock), 0, stream, a);
     return hipGetLastError();

@@ -5,12 +5,11 @@
 //   - every AMUSE_EINVAL of the parameter checks (through each of the three calls that take parameters) and of the argument checks; nothing refused launches
 //   - the context: create / reserve / destroy leave nothing behind (LeakSanitizer), reserve grows only and keeps what it outgrew until destroy
 //   - the launch arithmetic: runs = ceil(T / 16), the pick stage fed with the envelope the call wrote, T == 0 launches nothing
-// tests/test_beat_host_cpu.py builds and runs it (build.sh).  Prints "beat_host ok" and returns 0, or the first failed check and 1.
+// tests/test_beat_host_cpu.py builds and runs it (tests/build_host_program.sh).  Prints "beat_host ok" and returns 0, or the first failed check and 1.
 #include <hip/hip_runtime.h>
 
 #include <climits>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <limits>
@@ -19,14 +18,7 @@
 #include "../../amuse_amd/csrc/amuse_beat_host.hpp"
 #include "../../include/amuse_hip.h"
 
-static char g_err[512];
-int amuse_failf(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
+#include "../host_check.hpp"
 
 static std::vector<amuse::BeatEnvArgs> g_env;
 static std::vector<amuse::BeatPickArgs> g_pick;
@@ -38,11 +30,6 @@ hipError_t launch_beat_envelope(const BeatEnvArgs& a, hipStream_t s) { g_env.pus
 hipError_t launch_beat_pick(const BeatPickArgs& a, hipStream_t s) { g_pick.push_back(a); g_stream = s; return g_result; }
 hipError_t launch_beat_align(const BeatAlignArgs& a, hipStream_t s) { g_align.push_back(a); g_stream = s; return g_result; }
 }  // namespace amuse
-
-#define CHECK(c)                                                          \
-    do {                                                                  \
-        if (!(c)) { printf("FAILED %s:%d: %s  [%s]\n", __FILE__, __LINE__, #c, g_err); return 1; } \
-    } while (0)
 
 static size_t launches() { return g_env.size() + g_pick.size() + g_align.size(); }
 
@@ -200,7 +187,7 @@ int main() {
     using namespace amuse;
     static_assert(sizeof(BeatEnvArgs) <= 4096 && sizeof(BeatPickArgs) <= 4096 && sizeof(BeatAlignArgs) <= 4096, "the kernel arguments must fit the 4 KiB argument segment");
     static_assert(kBeatEnvBlock == 256 && kBeatEnvLdsBytes == 4136, "the FFT shape of k_fbank: re, im, the mean's and the flux's wave sums");
-    static_assert(kBeatPickLdsBytes == 16 && kBeatAlignBlock == 64 && kBeatJoints <= kBeatAlignBlock, "a lane per joint in one wave");
+    static_assert(kBeatPickLdsBytes == 16 && kBeatAlignBlock == 64 && kSmplxJoints <= kBeatAlignBlock, "a lane per joint in one wave");
     static_assert(kBeatAlignLdsBytes == 49664 && kBeatAlignLdsBytes <= 64 * 1024, "the speed ring and the onset bits fit a workgroup's 64 KiB");
     static_assert((kBeatMaxAudioFrames / 64) * 2 == kBeatMaxAudioFrames / 32, "a ballot fills two whole words of the onset bits");
     if (int e = plan_and_row_checks()) return e;

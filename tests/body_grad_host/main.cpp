@@ -10,7 +10,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <string>
@@ -23,14 +22,7 @@
 
 long amuse_stub_live_allocations();
 
-static char g_err[512];
-int amuse_failf(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
+#include "../host_check.hpp"
 
 static std::string g_order;
 static amuse::BodyPoseArgs g_pose[3];
@@ -44,11 +36,6 @@ hipError_t launch_body_loss_reduce(const float*, int, int, double*, hipStream_t)
 hipError_t launch_body_skin_bwd(const BodySkinBwdArgs& a, int split, hipStream_t) { g_sb[g_nsb++ % 2] = a; g_split = split; g_order += 'S'; return hipSuccess; }
 hipError_t launch_body_pose_bwd(const BodyPoseBwdArgs& a, hipStream_t) { g_pb[g_npb++ % 2] = a; g_order += 'P'; return hipSuccess; }
 }  // namespace amuse
-
-#define CHECK(c)                                                          \
-    do {                                                                  \
-        if (!(c)) { printf("FAILED %s:%d: %s  [%s]\n", __FILE__, __LINE__, #c, g_err); return 1; } \
-    } while (0)
 
 namespace ab = amuse_body;
 

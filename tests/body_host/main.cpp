@@ -5,11 +5,10 @@
 //   - the per-vertex (joint, weight) lists against the dense rows (order, padding, largest non-zero count)
 //   - v_shaped / J of every subject against a double evaluation
 //   - parents validation, V not a multiple of 4, argument checks, workspace growth, create / set_subjects / destroy with no allocation left
-// tests/test_body_host_asan_cpu.py builds and runs it (build.sh).  Prints "body_host ok" and returns 0, or the first failed check and 1.
+// tests/test_body_host_asan_cpu.py builds and runs it (tests/build_host_program.sh).  Prints "body_host ok" and returns 0, or the first failed check and 1.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <random>
@@ -21,14 +20,7 @@
 
 long amuse_stub_live_allocations();
 
-static char g_err[512];
-int amuse_failf(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
+#include "../host_check.hpp"
 
 static amuse::BodyPoseArgs g_pose[3];
 static amuse::BodySkinArgs g_skin;
@@ -38,11 +30,6 @@ hipError_t launch_body_pose(const BodyPoseArgs& a, hipStream_t) { g_pose[g_npose
 hipError_t launch_body_skin(const BodySkinArgs& a, int split, int loss, hipStream_t) { g_skin = a; ++g_nskin; g_split = split; g_loss = loss; return hipSuccess; }
 hipError_t launch_body_loss_reduce(const float*, int n, int, double*, hipStream_t) { ++g_nreduce; g_reduce_n = n; return hipSuccess; }
 }  // namespace amuse
-
-#define CHECK(c)                                                          \
-    do {                                                                  \
-        if (!(c)) { printf("FAILED %s:%d: %s  [%s]\n", __FILE__, __LINE__, #c, g_err); return 1; } \
-    } while (0)
 
 namespace ab = amuse_body;
 

@@ -4,11 +4,10 @@
 //   - the layout: refused parent lists, known trees, every joint once, a parent before its children, children in ascending index, a chain and a star at the size limit
 //   - the checks of the formatter, the exporter and the decoder: every refusal returns AMUSE_EINVAL and launches nothing
 //   - the packing: S = 1, the per-launch capacity, one more, and several launches' worth - 64-bit row offsets (byte offsets beyond 2^36), counts, the longest sequence, the call-wide index
-// tests/test_bvh_host_asan_cpu.py builds and runs it (build.sh).  Prints "bvh_host ok" and returns 0, or the first failed check and 1.
+// tests/test_bvh_host_asan_cpu.py builds and runs it (tests/build_host_program.sh).  Prints "bvh_host ok" and returns 0, or the first failed check and 1.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <limits>
 #include <vector>
@@ -16,14 +15,7 @@
 #include "../../amuse_amd/csrc/amuse_bvh_host.hpp"
 #include "../../include/amuse_hip.h"
 
-static char g_err[512];
-int amuse_failf(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
+#include "../host_check.hpp"
 
 static std::vector<amuse::BvhArgs> g_motion;
 static std::vector<amuse::BvhDecodeArgs> g_decode;
@@ -35,11 +27,6 @@ hipError_t launch_bvh_format(const float*, long long n, int, unsigned char*, int
 hipError_t launch_bvh_motion(const BvhArgs& a, hipStream_t s) { g_motion.push_back(a); g_stream = s; return hipSuccess; }
 hipError_t launch_bvh_decode(const BvhDecodeArgs& a, hipStream_t s) { g_decode.push_back(a); g_stream = s; return hipSuccess; }
 }  // namespace amuse
-
-#define CHECK(c)                                                          \
-    do {                                                                  \
-        if (!(c)) { printf("FAILED %s:%d: %s  [%s]\n", __FILE__, __LINE__, #c, g_err); return 1; } \
-    } while (0)
 
 static int layout_checks() {
     int out[8] = {-7, -7, -7, -7, -7, -7, -7, -7};
@@ -162,7 +149,7 @@ static int check_checks() {
 }
 
 static int packing_checks() {
-    const int cap = amuse::kBvhMaxSeq;
+    const int cap = amuse::kSeqPerLaunch;
     float in[4] = {0, 0, 0, 0};      // (never dereferenced: the launchers are stand-ins)
     int status[1] = {0};
     int dfs[55];
@@ -199,7 +186,7 @@ static int packing_checks() {
 
 int main() {
     static_assert(sizeof(amuse::BvhArgs) <= 4096 && sizeof(amuse::BvhDecodeArgs) <= 4096, "the kernel arguments must fit the 4 KiB argument segment");
-    static_assert((long long)amuse::kBvhMaxFrames * amuse::kBvhSlots + amuse::kBvhBlock <= INT_MAX, "a launch's lane index is an int");
+    static_assert((long long)amuse::kBvhMaxFrames * amuse::kMotionSlots + amuse::kBvhBlock <= INT_MAX, "a launch's lane index is an int");
     if (int e = layout_checks()) return e;
     if (int e = check_checks()) return e;
     if (int e = packing_checks()) return e;

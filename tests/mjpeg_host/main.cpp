@@ -6,10 +6,9 @@
 //   - the plan: a sweep of sizes against the arithmetic written out again, the refused arguments
 //   - create / reserve / the calls: every refusal returns AMUSE_EINVAL and launches and allocates nothing; the workspace's sections lie inside its block and
 //     do not overlap; the workspace grows once and the outgrown block is kept; destroy leaves nothing behind
-// tests/test_mjpeg_host_asan_cpu.py builds and runs it (build.sh).  Prints "mjpeg_host ok" and returns 0, or the first failed check and 1.
+// tests/test_mjpeg_host_asan_cpu.py builds and runs it (tests/build_host_program.sh).  Prints "mjpeg_host ok" and returns 0, or the first failed check and 1.
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -19,14 +18,7 @@
 
 long amuse_stub_live_allocations();
 
-static char g_err[512];
-int amuse_failf(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
+#include "../host_check.hpp"
 
 static std::vector<amuse::MjpegTransformArgs> g_transform;
 static std::vector<amuse::MjpegEntropyArgs> g_size, g_scan, g_write;
@@ -67,11 +59,6 @@ hipError_t launch_mjpeg_write(const MjpegEntropyArgs& a, hipStream_t s) {
     return hipSuccess;
 }
 }  // namespace amuse
-
-#define CHECK(c)                                                          \
-    do {                                                                  \
-        if (!(c)) { printf("FAILED %s:%d: %s  [%s]\n", __FILE__, __LINE__, #c, g_err); return 1; } \
-    } while (0)
 
 static int table_checks() {
     unsigned char lu[64], ch[64];

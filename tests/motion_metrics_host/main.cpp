@@ -4,11 +4,10 @@
 //   - the row: 442 doubles, the block offsets of include/amuse_hip.h's table add up
 //   - the checks: every refusal returns AMUSE_EINVAL, names what it refused and launches nothing - NULL pointers, N < 1, F < 2, sizes beyond an int
 //   - the launch arithmetic: one launch per call whatever N is, pointers / N / F / stream passed through, the workgroup's LDS and the 4 KiB argument segment
-// tests/test_motion_metrics_host_asan_cpu.py builds and runs it (build.sh).  Prints "motion_metrics_host ok" and returns 0, or the first failed check and 1.
+// tests/test_motion_metrics_host_asan_cpu.py builds and runs it (tests/build_host_program.sh).  Prints "motion_metrics_host ok" and returns 0, or the first failed check and 1.
 #include <hip/hip_runtime.h>
 
 #include <climits>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -16,14 +15,7 @@
 #include "../../amuse_amd/csrc/amuse_motion_metrics_host.hpp"
 #include "../../include/amuse_hip.h"
 
-static char g_err[512];
-int amuse_failf(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
+#include "../host_check.hpp"
 
 static std::vector<amuse::MotionMetricsArgs> g_launches;
 static hipStream_t g_stream = nullptr;
@@ -31,11 +23,6 @@ static hipError_t g_result = hipSuccess;
 namespace amuse {
 hipError_t launch_motion_metrics(const MotionMetricsArgs& a, hipStream_t s) { g_launches.push_back(a); g_stream = s; return g_result; }
 }  // namespace amuse
-
-#define CHECK(c)                                                          \
-    do {                                                                  \
-        if (!(c)) { printf("FAILED %s:%d: %s  [%s]\n", __FILE__, __LINE__, #c, g_err); return 1; } \
-    } while (0)
 
 static int row_checks() {
     using namespace amuse;
@@ -98,7 +85,7 @@ int main() {
     static_assert(sizeof(amuse::MotionMetricsArgs) <= 4096, "the kernel arguments must fit the 4 KiB argument segment");
     static_assert(amuse::kMetricsBlock == 512 && amuse::kMetricsBlock <= 1024, "a workgroup of eight waves");
     static_assert(amuse::kMetricsLdsBytes == 77824 && amuse::kMetricsLdsBytes <= 160 * 1024, "the partials of eight waves fit the 160 KiB of LDS of a CU");
-    static_assert(amuse::kMetricsJoints <= 64, "a lane per joint");
+    static_assert(amuse::kSmplxJoints <= 64, "a lane per joint");
     if (int e = row_checks()) return e;
     if (int e = refusal_checks()) return e;
     if (int e = launch_checks()) return e;

@@ -5,10 +5,9 @@
 //   - create: the refusals (a face index outside 0..V-1 among them) launch and allocate nothing; the uploaded faces are the caller's
 //   - the call: every refusal returns AMUSE_EINVAL and launches nothing; M around chunk_frames gives the chunks the plan states, each with its own slice of the
 //     inputs and outputs, all inside the workspace's block; the workspace grows once and is kept; destroy leaves nothing behind
-// tests/test_render_host_asan_cpu.py builds and runs it (build.sh).  Prints "render_host ok" and returns 0, or the first failed check and 1.
+// tests/test_render_host_asan_cpu.py builds and runs it (tests/build_host_program.sh).  Prints "render_host ok" and returns 0, or the first failed check and 1.
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -18,14 +17,7 @@
 
 long amuse_stub_live_allocations();
 
-static char g_err[512];
-int amuse_failf(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
+#include "../host_check.hpp"
 
 static std::vector<amuse::RenderProjectArgs> g_project;
 static std::vector<amuse::RenderTileArgs> g_tile;
@@ -47,11 +39,6 @@ hipError_t launch_render_tile(const RenderTileArgs& a, hipStream_t s) {
     return hipSuccess;
 }
 }  // namespace amuse
-
-#define CHECK(c)                                                          \
-    do {                                                                  \
-        if (!(c)) { printf("FAILED %s:%d: %s  [%s]\n", __FILE__, __LINE__, #c, g_err); return 1; } \
-    } while (0)
 
 static int plan_checks() {
     int tx = 0, ty = 0, ch = 0;

@@ -4,10 +4,9 @@
 //   - the plan: the six known rows, equal rates, a sweep of n_in against the arithmetic written out again, the refused arguments
 //   - the bank of each row: its size (written to an exactly-sized heap block), the DC gain of every phase, the identity of equal rates
 //   - the call: every refusal returns AMUSE_EINVAL and launches nothing; the accepted call's arguments; create / destroy leave nothing behind
-// tests/test_resample_host_asan_cpu.py builds and runs it (build.sh).  Prints "resample_host ok" and returns 0, or the first failed check and 1.
+// tests/test_resample_host_asan_cpu.py builds and runs it (tests/build_host_program.sh).  Prints "resample_host ok" and returns 0, or the first failed check and 1.
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -15,25 +14,13 @@
 #include "../../amuse_amd/csrc/amuse_resample_host.hpp"
 #include "../../include/amuse_hip.h"
 
-static char g_err[512];
-int amuse_failf(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
+#include "../host_check.hpp"
 
 static std::vector<amuse::ResampleArgs> g_launches;
 static hipStream_t g_stream = nullptr;
 namespace amuse {
 hipError_t launch_resample(const ResampleArgs& a, hipStream_t s) { g_launches.push_back(a); g_stream = s; return hipSuccess; }
 }  // namespace amuse
-
-#define CHECK(c)                                                          \
-    do {                                                                  \
-        if (!(c)) { printf("FAILED %s:%d: %s  [%s]\n", __FILE__, __LINE__, #c, g_err); return 1; } \
-    } while (0)
 
 static const struct { int rate, M, L, Hw, K; } kRows[] = {{48000, 3, 1, 19, 40}, {44100, 441, 160, 17, 36}, {22050, 441, 320, 9, 20},
                                                           {8000, 1, 2, 7, 16},   {96000, 6, 1, 37, 76},     {11025, 441, 640, 7, 16}};

@@ -13,7 +13,7 @@ import numpy as np
 import smooth_ref as ref
 
 TILE = 32      # output frames of a workgroup (csrc/amuse_smooth_host.hpp kSmoothTile)
-CAP = 32       # sequences per launch (kSmoothMaxSeq; include/amuse_hip.h states it)
+CAP = 32       # sequences per launch (csrc/amuse_seq_host.hpp kSeqPerLaunch; include/amuse_hip.h states it)
 ORDER = 3
 MIXED_HW = tuple([0, 1, 4, 15, 4, 2][j % 6] for j in range(55)) + (4,)
 # 33 sequences: L = 2 m, 2 m + 1, 2 m + 2 of m = 1, 4, 15; one frame; one tile and a frame; several tiles

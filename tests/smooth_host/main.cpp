@@ -4,36 +4,23 @@
 //   - the bank: the refused arguments, the layout, known coefficients, rows that sum to 1, symmetry, idempotence (H H = H), H = I where the fit interpolates
 //   - the filter's checks: every refusal returns AMUSE_EINVAL and launches nothing; the overlap check on every pair of an output and an input range
 //   - the packing: S = 1, the per-launch capacity, one more, and several launches' worth - offsets, counts, the largest sequence, the halo, the half-windows
-// tests/test_smooth_host_asan_cpu.py builds and runs it (build.sh).  Prints "smooth_host ok" and returns 0, or the first failed check and 1.
+// tests/test_smooth_host_asan_cpu.py builds and runs it (tests/build_host_program.sh).  Prints "smooth_host ok" and returns 0, or the first failed check and 1.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <vector>
 
 #include "../../amuse_amd/csrc/amuse_smooth_host.hpp"
 #include "../../include/amuse_hip.h"
 
-static char g_err[512];
-int amuse_failf(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
+#include "../host_check.hpp"
 
 static std::vector<amuse::SmoothArgs> g_launches;
 static hipStream_t g_stream = nullptr;
 namespace amuse {
 hipError_t launch_smooth(const SmoothArgs& a, hipStream_t s) { g_launches.push_back(a); g_stream = s; return hipSuccess; }
 }  // namespace amuse
-
-#define CHECK(c)                                                          \
-    do {                                                                  \
-        if (!(c)) { printf("FAILED %s:%d: %s  [%s]\n", __FILE__, __LINE__, #c, g_err); return 1; } \
-    } while (0)
 
 static int bank_checks() {
     std::vector<float> bk(AMUSE_SMOOTH_BANK_FLOATS + 1, -77.f);      // (one float of guard behind the bank)
@@ -141,7 +128,7 @@ static int smooth_checks() {
 }
 
 static int packing_checks() {
-    const int cap = amuse::kSmoothMaxSeq;
+    const int cap = amuse::kSeqPerLaunch;
     float in[4] = {0, 0, 0, 0};      // (never dereferenced: the launcher is the stand-in; the ranges are far apart)
     float* out = reinterpret_cast<float*>(static_cast<uintptr_t>(1) << 40);
     float* tout = reinterpret_cast<float*>(static_cast<uintptr_t>(1) << 41);
@@ -174,7 +161,7 @@ static int packing_checks() {
 
 int main() {
     static_assert(sizeof(amuse::SmoothArgs) <= 4096, "the kernel arguments must fit the 4 KiB argument segment");
-    static_assert(amuse::kSmoothLdsRows * amuse::kSmoothSlots * 16 <= 64 * 1024, "the quaternion tile must fit a workgroup's LDS");
+    static_assert(amuse::kSmoothLdsRows * amuse::kMotionSlots * 16 <= 64 * 1024, "the quaternion tile must fit a workgroup's LDS");
     if (int e = bank_checks()) return e;
     if (int e = smooth_checks()) return e;
     if (int e = packing_checks()) return e;

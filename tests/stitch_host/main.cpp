@@ -4,35 +4,22 @@
 //   - the window plan: known answers, a sweep against the arithmetic written out again, the last window's audio bound, the refused arguments
 //   - the join's checks: every refusal returns AMUSE_EINVAL and launches nothing
 //   - the packing: S = 1, the per-launch capacity, one more, and several launches' worth - offsets, counts, the largest sequence of each launch
-// tests/test_stitch_host_asan_cpu.py builds and runs it (build.sh).  Prints "stitch_host ok" and returns 0, or the first failed check and 1.
+// tests/test_stitch_host_asan_cpu.py builds and runs it (tests/build_host_program.sh).  Prints "stitch_host ok" and returns 0, or the first failed check and 1.
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
 #include <cstdio>
 #include <vector>
 
 #include "../../amuse_amd/csrc/amuse_stitch_host.hpp"
 #include "../../include/amuse_hip.h"
 
-static char g_err[512];
-int amuse_failf(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
+#include "../host_check.hpp"
 
 static std::vector<amuse::StitchArgs> g_launches;
 static hipStream_t g_stream = nullptr;
 namespace amuse {
 hipError_t launch_stitch(const StitchArgs& a, hipStream_t s) { g_launches.push_back(a); g_stream = s; return hipSuccess; }
 }  // namespace amuse
-
-#define CHECK(c)                                                          \
-    do {                                                                  \
-        if (!(c)) { printf("FAILED %s:%d: %s  [%s]\n", __FILE__, __LINE__, #c, g_err); return 1; } \
-    } while (0)
 
 static int plan_checks() {
     int W = 0, L = 0, hs = 0;
@@ -110,7 +97,7 @@ static int stitch_checks() {
 }
 
 static int packing_checks() {
-    const int cap = amuse::kStitchMaxSeq;
+    const int cap = amuse::kSeqPerLaunch;
     float dummy[4] = {0, 0, 0, 0};   // (never dereferenced: the launcher is the stand-in)
     for (int S : {1, cap - 1, cap, cap + 1, 2 * cap, 3 * cap + 5}) {
         std::vector<int> W(S), L(S);

@@ -15,7 +15,7 @@ def test_mjpeg_host_program_under_asan_ubsan(tmp_path):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     if not (shutil.which(hipcc) or os.path.exists(hipcc)):
         pytest.skip("hipcc not available")
-    build = subprocess.run(["bash", str(REPO / "tests" / "mjpeg_host" / "build.sh"), str(tmp_path)], capture_output=True, text=True, timeout=900)
+    build = subprocess.run(["bash", str(REPO / "tests" / "build_host_program.sh"), "mjpeg", str(tmp_path)], capture_output=True, text=True, timeout=900)
     assert build.returncode == 0, build.stdout[-2000:] + build.stderr[-2000:]
     run = subprocess.run([str(tmp_path / "mjpeg_host")], capture_output=True, text=True, timeout=600,
                          env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1"))

@@ -111,12 +111,15 @@ __device__ __forceinline__ float2 row_stats_merge(const float2* stats, int r) {
 
 // The prologue's rows (denoiser.py:174,180-181), features f .. f + 3 of this lane's row: the static token row (pe[0] under the latent
 // rows, condition tokens) and the initial latent of feature tile t.  They go to LDS: registers are the scarce resource at 2 waves / SIMD.
+// A per-clip time token (time_tok_clip: a teacher-forced step, diffusion_forward) does not change from step to step either and is a static
+// row of its clip; the per-step one (time_tok) travels through the double buffer instead and its row here stays 0 (token assembly, below).
 template <class Args>
 __device__ __forceinline__ f32x4 static_row4(const Args& a, const Lane8& L, int f) {
     f32x4 sv = splat4(0.f);
     if (L.valid) {
         if (L.tok == 0) sv = ld4(a.pe0 + f);
         else if (L.tok >= 2) sv = ld4(a.cond_tok + ((size_t)L.clip * (a.S - 2) + (L.tok - 2)) * kD + f);
+        else if (a.time_tok_clip) sv = ld4(a.time_tok_clip + (size_t)L.clip * kD + f);
     }
     return sv;
 }
@@ -128,16 +131,48 @@ __device__ __forceinline__ f32x4 init_latent4(const Args& a, const Lane8& L, int
                       : counter_normal4(a.seed, a.clip0 + (uint64_t)L.clip, 0u, (uint32_t)(4 * t + L.g), 0u);
     return l0;
 }
-// token assembly (denoiser.py:174,180-181): feature tile t of this lane's row of the step's input.  L: lane_info's opaque re-derivation;
-// lane, g: the step loop's own copies
+// Token assembly (denoiser.py:174,180-181): feature tile t of this lane's row of the step's input is
+//   !valid ? 0 : tok == 0 ? latent + static row : tok == 1 ? time token : static row.
+// Every operand lives in LDS and a lane's token never changes, so the lane fixes ONE source of its non-latent operand per step - the time-token
+// buffer of this step for a time-token row, its static row otherwise (which holds 0 for padding rows and, under a per-clip time token, that
+// token: static_row4) - and a tile costs one unconditional ds_read_b128 beside the latent, an add and a select.  No global or flat load, no
+// lane-mask branch.
+struct TokSrc {
+    const f32x4* x;   // the lane's non-latent operand of tile 0 ...
+    int stride;       // ... and the distance to the next tile's
+    bool is_lat;
+};
 template <class Args>
-__device__ __forceinline__ f32x4 assemble_tile(const Args& a, const Lane8& L, int lane, int g, const f32x4* tokrows, const float* ttl,
-                                               const f32x4* latl, int step, int t) {
-    const f32x4 sv = tokrows[t * 64 + lane];
-    // unconditional loads (a divergent branch around them costs registers)
-    f32x4 tt = ld4(ttl + (step & 1) * kD + 16 * t + 4 * g);
-    if (a.time_tok_clip) tt = ld4(a.time_tok_clip + (size_t)(L.valid ? L.clip : 0) * kD + 16 * t + 4 * g);
-    return !L.valid ? splat4(0.f) : (L.tok == 0 ? latl[t * 64 + lane] + sv : (L.tok == 1 ? tt : sv));
+__device__ __forceinline__ TokSrc tok_src(const Args& a, const Lane8& L, int lane, int g, const f32x4* tokrows, const float* ttl, int step) {
+    const bool from_tt = L.valid && L.tok == 1 && !a.time_tok_clip;
+    return TokSrc{from_tt ? reinterpret_cast<const f32x4*>(ttl + (step & 1) * kD) + g : tokrows + lane, from_tt ? 4 : 64, L.is_lat};
+}
+__device__ __forceinline__ f32x4 assemble_pick(const TokSrc& s, const f32x4& x, const f32x4& la) {
+    const f32x4 sum = la + x;
+    return s.is_lat ? sum : x;
+}
+// Who assembles.  k_sample8x: every wave, at the step's head, all tiles at once - the reads of tiles T0 .. T0 + N - 1 (T0 may be a runtime value:
+// a reducer's own pair) issued before one wait (assemble_load), then the picks; lane: the step loop's own copy.
+template <int N>
+__device__ __forceinline__ void assemble_load(f32x4 (&x)[N], f32x4 (&la)[N], const TokSrc& s, const f32x4* latl, int lane, int T0) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        x[i] = s.x[(T0 + i) * s.stride];
+        la[i] = latl[(T0 + i) * 64 + lane];
+    }
+}
+// k_sample8 / k_sample8h: the reducer of a tile pair (B wave h: tiles 2 h, 2 h + 1), which holds the updated latent of exactly those tiles in
+// registers at the end of a step's tail.  It builds the NEXT step's two tiles there (and, in front of the first step, from the initial latent),
+// keeps them as its fp32 tiles and publishes them as one operand where a combine's result goes; every wave's step head is then a combine's
+// gather - four reads - instead of sixteen to twenty (8 waves x 16-20 KiB of LDS reads bound the head above at ~1.2 k cycles of LDS bandwidth).
+// -> the two tiles of step `step`'s input from latent tiles la; L: lane_info's opaque re-derivation
+template <class Args>
+__device__ __forceinline__ void assemble_own(f32x4 (&xo)[2], const f32x4 (&la)[2], const Args& a, const Lane8& L, const f32x4* tokrows, const float* ttl,
+                                             int step, int h) {
+    const TokSrc s = tok_src(a, L, L.lane, L.g, tokrows, ttl, step);
+    const f32x4 x0 = s.x[(2 * h) * s.stride], x1 = s.x[(2 * h + 1) * s.stride];
+    xo[0] = assemble_pick(s, x0, la[0]);
+    xo[1] = assemble_pick(s, x1, la[1]);
 }
 
 }  // namespace

@@ -23,7 +23,9 @@
 //     operands (what the 4-wave kernel's cvt_pk produces from its fp32 copy - same bits).
 //   The residual stream travels between waves as packed bf16 MFMA operands (4 x 1 KiB per tile - what every GEMM
 //   consumes); only the reducer of a feature tile keeps it in fp32 (the B waves, two tiles each, in registers).
-//   Final LayerNorm + scheduler update in the B waves on their own tiles; latent in LDS.
+//   Final LayerNorm + scheduler update in the B waves on their own tiles; latent in LDS.  With the updated latent of its two tiles still in
+//   registers a B wave also assembles the NEXT step's input for them (latent + pe[0] | time token | condition tokens: amuse_sample8.hpp
+//   assemble_own) and publishes it like a combine's result, so a step starts with that combine's four-read gather in every wave.
 //
 // LDS (163,328 B): combine matrix A8 [8 rows][8 tiles][64] f32x4 - fp32 partials off the diagonal, the published
 // bf16 operands ON it (slots (c, c), c < 4), so the gather of one combine never aliases the partial writes of the
@@ -481,36 +483,37 @@ __device__ __forceinline__ void role_loop8(const Args& a, char* smem, int w8, co
     }
     Prof8 pf{a.prof_out ? a.prof_out + (size_t)w8 * 96 : nullptr, 0, false};
     SDrop8 dr = sdrop8_of<DROP>(a);
+    // the first step's input (amuse_sample8.hpp assemble_own): each reducer's two tiles from the initial latent, published where the step head gathers
+    f32x4 xo[2] = {splat4(0.f), splat4(0.f)};
+    if constexpr (!ROLEA) {
+        const Lane8 L = lane_info(a, lane);
+        const f32x4 l[2] = {latl[(2 * h) * 64 + L.lane], latl[(2 * h + 1) * 64 + L.lane]};
+        assemble_own(xo, l, a, L, tokrows, ttl, 0, h);
+        *xb_slot(smem, h, L.lane) = __builtin_bit_cast(uint4, OP_PACK(xo[0], xo[1]));
+    }
+    __syncthreads();
 #pragma unroll 1
     for (int step = 0; step < a.T; ++step) {
-        dr.step = (uint32_t)step;
-        // ---- token assembly (denoiser.py:174,180-181): every wave builds the four packed operands, a B wave also
-        // its own two tiles in fp32
-        OPV xb[4];
-        f32x4 xo[2] = {splat4(0.f), splat4(0.f)};
-        f32x4 zn[2] = {splat4(0.f), splat4(0.f)};   // B waves: this step's ancestral noise of their two tiles, drawn ahead of the tail (below)
-        {
-            const Lane8 L = lane_info(a, lane);
-            auto assemble = [&](int t) { return assemble_tile(a, L, lane, g, tokrows, ttl, latl, step, t); };
-#pragma unroll
-            for (int c = 0; c < 4; ++c) xb[c] = OP_PACK(assemble(2 * c), assemble(2 * c + 1));
-            if constexpr (!ROLEA) {
-                xo[0] = assemble(2 * h);
-                xo[1] = assemble(2 * h + 1);
-            }
+        if constexpr (PROF) {
+            stamp8<PROF>(pf);  // (on only in the step behind the profiled one: its top closes that step, stamp to stamp)
+            pf.on = a.prof_out != nullptr && blockIdx.x == 0 && lane == 0 && step == a.prof_step;
+            stamp8<PROF>(pf);  // step top: the head (token assembly, wave 4's time-token copy) starts
         }
+        dr.step = (uint32_t)step;
+        // ---- token assembly (denoiser.py:174,180-181): done by the reducers in the previous step's tail (in front of the loop for the first step),
+        // published like a combine's result - the head is that combine's gather; a B wave carries its own two tiles in fp32 (xo)
+        OPV xb[4];
+        f32x4 zn[2] = {splat4(0.f), splat4(0.f)};   // B waves: this step's ancestral noise of their two tiles, drawn ahead of the tail (below)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) xb[c] = __builtin_bit_cast(OPV, *xb_slot(smem, c, lane));
+        // next step's time token -> the other LDS buffer (the reducers read it in this step's tail, many barriers later)
+        if (!ROLEA && w8 == 4 && lane < 32 && step + 1 < a.T)
+            st4(ttl + ((step + 1) & 1) * kD + 4 * lane, ld4(a.time_tok + (size_t)(step + 1) * kD + 4 * lane));
         if (tap && step == 0) {
             store_tap_tile(a.tap_out, 0, 2 * h, xo[0], g, r);
             store_tap_tile(a.tap_out, 0, 2 * h + 1, xo[1], g, r);
         }
-        // next step's time token -> the other LDS buffer (read a whole step and many barriers later)
-        if (!ROLEA && w8 == 4 && lane < 32 && step + 1 < a.T)
-            st4(ttl + ((step + 1) & 1) * kD + 4 * lane, ld4(a.time_tok + (size_t)(step + 1) * kD + 4 * lane));
-        if constexpr (PROF) {
-            pf.on = a.prof_out != nullptr && blockIdx.x == 0 && lane == 0 && step == a.prof_step;
-            pf.idx = 0;
-        }
-        stamp8<PROF>(pf);  // step start
+        stamp8<PROF>(pf);  // step start: operands gathered, wave 4's time-token copy done
         rg.next = ROLEA ? wbase + kR8 * 64 : wbase;  // (A: the ring already holds units 0..31 of this step)
         // ---- SkipTransformerEncoder.forward (cross_attention.py:41-64)
 #pragma unroll 1
@@ -620,11 +623,16 @@ __device__ __forceinline__ void role_loop8(const Args& a, char* smem, int w8, co
                     if (a.traj_out && L.is_lat) st4(a.traj_out + ((size_t)step * a.B + L.clip) * kD + f, l[i]);
                 }
             }
+            // the next step's input from the updated latent, published for every wave's gather behind the step barrier (assemble_own)
+            if (step + 1 < a.T) {
+                assemble_own(xo, l, a, L, tokrows, ttl, step + 1, h);
+                *xb_slot(smem, h, L.lane) = __builtin_bit_cast(uint4, OP_PACK(xo[0], xo[1]));
+            }
         } else {
             __syncthreads();
         }
         stamp8<PROF>(pf);  // scheduler update done (B waves) / reached the step barrier
-        __syncthreads();  // the updated latent is visible to every wave's token assembly
+        __syncthreads();  // the next step's operands are visible to every wave's gather
     }
 }
 

@@ -430,32 +430,38 @@ __device__ __forceinline__ void role_loop8x(const SampleKernelArgs& a, char* sme
     Prof8 pf{a.prof_out ? a.prof_out + (size_t)w8 * 96 : nullptr, 0, false};
 #pragma unroll 1
     for (int step = 0; step < a.T; ++step) {
-        // ---- token assembly (denoiser.py:174,180-181): every wave builds the four split operands, a B wave also
-        // its own two tiles in fp32
+        if constexpr (PROF) {
+            stamp8<PROF>(pf);  // (on only in the step behind the profiled one: its top closes that step, stamp to stamp)
+            pf.on = a.prof_out != nullptr && blockIdx.x == 0 && lane == 0 && step == a.prof_step;
+            stamp8<PROF>(pf);  // step top: the head (token assembly, wave 4's time-token copy) starts
+        }
+        // ---- token assembly (denoiser.py:174,180-181): every wave builds the four split operands, a B wave also its own two tiles in fp32.
+        // (k_sampler8.hip lets the reducers assemble in the tail and publish; here that form measured no faster than the serial head it replaces -
+        // the tail is this kernel's longer lone chain and a split operand costs two publishes and two gathers - and this one 0.6 ms of 70.4 faster.)
         F16Pair xs[4];
         f32x4 xo[2] = {splat4(0.f), splat4(0.f)};
         {
+            // all LDS reads of the head in one batch, one wait (amuse_sample8.hpp: token assembly)
             const Lane8 L = lane_info(a, lane);
-            auto assemble = [&](int t) { return assemble_tile(a, L, lane, g, tokrows, ttl, latl, step, t); };
+            const TokSrc ts = tok_src(a, L, lane, g, tokrows, ttl, step);
+            f32x4 x[kTiles], la[kTiles], xr[2], lr[2];
+            assemble_load<kTiles>(x, la, ts, latl, lane, 0);
+            if constexpr (!ROLEA) assemble_load<2>(xr, lr, ts, latl, lane, 2 * h);
 #pragma unroll
-            for (int c = 0; c < 4; ++c) xs[c] = split_f16(assemble(2 * c), assemble(2 * c + 1));
+            for (int c = 0; c < 4; ++c) xs[c] = split_f16(assemble_pick(ts, x[2 * c], la[2 * c]), assemble_pick(ts, x[2 * c + 1], la[2 * c + 1]));
             if constexpr (!ROLEA) {
-                xo[0] = assemble(2 * h);
-                xo[1] = assemble(2 * h + 1);
+                xo[0] = assemble_pick(ts, xr[0], lr[0]);
+                xo[1] = assemble_pick(ts, xr[1], lr[1]);
             }
-        }
-        if (tap && step == 0) {
-            store_tap_tile(a.tap_out, 0, 2 * h, xo[0], g, r);
-            store_tap_tile(a.tap_out, 0, 2 * h + 1, xo[1], g, r);
         }
         // next step's time token -> the other LDS buffer (read a whole step and many barriers later)
         if (!ROLEA && w8 == 4 && lane < 32 && step + 1 < a.T)
             st4(ttl + ((step + 1) & 1) * kD + 4 * lane, ld4(a.time_tok + (size_t)(step + 1) * kD + 4 * lane));
-        if constexpr (PROF) {
-            pf.on = a.prof_out != nullptr && blockIdx.x == 0 && lane == 0 && step == a.prof_step;
-            pf.idx = 0;
+        if (tap && step == 0) {
+            store_tap_tile(a.tap_out, 0, 2 * h, xo[0], g, r);
+            store_tap_tile(a.tap_out, 0, 2 * h + 1, xo[1], g, r);
         }
-        stamp8<PROF>(pf);  // step start
+        stamp8<PROF>(pf);  // step start: assembly and wave 4's time-token copy done
         rg.next = ROLEA ? wbase + kR8 * 64 : wbase;  // (A: the ring already holds units 0..31 of this step)
         // ---- SkipTransformerEncoder.forward (cross_attention.py:41-64)
 #pragma unroll 1

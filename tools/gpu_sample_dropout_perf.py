@@ -55,8 +55,9 @@ for p in (0.0, 0.1):
     for w in (0, 4):
         v = st[w]
         v = v[:int((v != 0).sum())]
-        blocks = v[1:1 + 45].reshape(9, 5)
-        prev = np.concatenate([[v[0]], blocks[:-1, -1]])
+        # stamps: step top | step start (behind the head) | 9 blocks x 5 | tail | the next step's top
+        blocks = v[2:2 + 45].reshape(9, 5)
+        prev = np.concatenate([[v[1]], blocks[:-1, -1]])
         seg = np.diff(np.concatenate([prev[:, None], blocks], axis=1), axis=1).sum(axis=0)
-        print(f"  p = {p:.1f} wave {w}: step {int(v[-1] - v[0]):7d}  " + "  ".join(f"{nm} {int(x):6d}" for nm, x in zip(names, seg)))
+        print(f"  p = {p:.1f} wave {w}: step {int(v[47] - v[0]):7d}  head {int(v[1] - v[0]):5d}  " + "  ".join(f"{nm} {int(x):6d}" for nm, x in zip(names, seg)))
 eng.close()

@@ -8,6 +8,8 @@ front of the four blocks with a skip linear, two in the step's tail; the reducer
 that do, the one with the fewest instructions is taken (Dijkstra over (node, next waypoint)); lane-mask branches follow the lanes (s_cbranch_execz falls through,
 s_cbranch_execnz is taken), and the walk must run the ancestral-noise draw and the scheduler update once each (MUST_RUN below).  What the shortest walk leaves out: every debugging tap and optional output, and
 the extra work in front of a skip block (a B wave's 8 early units, an A wave's u = W[:, 128:] . skip: 8 MFMAs and 4 LDS reads) - listed under the table.
+The STEP HEAD (token assembly, wave 4's time-token copy: role loop header -> the `step start` stamp) gets a table of its own, read off the phase-stamped
+instantiation, which is the one that marks where the head ends (head_rows).
 
 Usage: python tools/isa_phase_table.py [k_sampler8.s] > profiles/rNN_k_sample8_phase_instructions.txt      (without an argument it runs `make isa` itself)"""
 import heapq
@@ -217,6 +219,39 @@ def fold(role, iv):
     return {n: (sorted(v, key=lambda c: sum(c.values()))[len(v) // 2], sum(v, Counter()), len(v)) for n, v in occ.items()}
 
 
+def head_rows(asm: str):
+    """The step head - token assembly and wave 4's time-token copy - of both roles: role -> count vector of the text between the role loop's header and
+    the `step start` stamp.  The product instantiation carries no stamp, so this reads the phase-stamped one (k_sample8<true, false>): the head is
+    its text up to the third s_memtime behind the header (two stamps at the step's top, the third behind the head).  A count of the TEXT, lane-mask
+    regions included (some lane runs each of them), which is what a wave issues as long as the head is laid out in one piece - it is straight-line code."""
+    lines = asm.splitlines()
+    start = next((i for i, l in enumerate(lines) if re.match(r"^_Z\w*k_sample8\w?ILb1ELb0E\w*:", l)), None)
+    if start is None:
+        return {}
+    end = next(i for i in range(start, len(lines)) if lines[i].strip() == "s_endpgm")
+    lines = lines[start:end + 1]
+    out = {}
+    for role, lab in role_headers(lines, None).items():
+        i = next(k for k, l in enumerate(lines) if l.startswith(lab + ":"))
+        c, stamps = Counter(), 0
+        for l in lines[i + 1:]:
+            l = l.strip()
+            if not l or l[0] in ".;" or l.endswith(":"):
+                continue
+            ins = l.split(";")[0].strip()
+            if not ins:
+                continue
+            if ins.startswith("s_memtime"):
+                stamps += 1
+                if stamps == 3:
+                    break
+            c[classify(ins)] += 1
+            c["flat"] += ins.startswith("flat_load")
+            c["vmcnt"] += ins.startswith("s_waitcnt") and "vmcnt" in ins
+        out[role] = c
+    return out
+
+
 def report(asm_path: Path, out=sys.stdout):
     lines, sym = kernel_text(asm_path.read_text())
     nodes, labels = build_cfg(lines)
@@ -236,13 +271,20 @@ def report(asm_path: Path, out=sys.stdout):
             print(f"{name:68s} {n:3d} " + " ".join(f"{one[c]:9d}" for c in CLASSES) + "   |           " + " ".join(f"{allc[c]:6d}" for c in CLASSES[:4]), file=out)
         print(f"{'TOTAL per step':68s}     " + " ".join(f"{tot[c]:9d}" for c in CLASSES), file=out)
         totals[role] = tot
+    hd = head_rows(asm_path.read_text())
+    if hd:
+        print("\n## step head: role loop header -> `step start` stamp, text of the phase-stamped instantiation k_sample8<true, false> (its three stamps included)", file=out)
+        print(f"{'role':68s}     " + " ".join(f"{c:>9s}" for c in CLASSES) + "   | flat_load  waits on vmcnt", file=out)
+        for role in ("B", "A"):
+            c = hd[role]
+            print(f"{role + ' wave':68s}     " + " ".join(f"{c[k]:9d}" for k in CLASSES) + f"   | {c['flat']:9d}  {c['vmcnt']:14d}", file=out)
     avg = (totals["A"]["VALU"] + totals["B"]["VALU"]) / 2
     print(f"\nVALU per wave and step, mean of the two roles: {avg:.0f}   (B {totals['B']['VALU']}, A {totals['A']['VALU']})", file=out)
     print(f"MFMA per step: A {totals['A']['MFMA']}, B {totals['B']['MFMA']}", file=out)
     print("(x: occurrences per step; left columns: a typical occurrence, the median one by size; right columns: the sum over the step.  The first phase of block 0 holds the\n"
-          " step head - token assembly -, the first phase of every later block the few instructions behind the previous block's last waypoint, and one of the nine\n"
+          " step head - the gather of the step's operands -, the first phase of every later block the few instructions behind the previous block's last waypoint, and one of the nine\n"
           " the reducers' noise draw where the kernel makes it ahead of the tail.  Left out by the shortest walk: taps and optional outputs, and in front of each of the\n"
-          " four skip blocks a B wave's 8 early units and an A wave's u = W[:, 128:] . skip - 8 MFMAs, 4 LDS reads, 2 LDS writes.  SQ_INSTS_VALU counts MFMAs as VALU.)", file=out)
+          " four skip blocks a B wave's 8 early units and an A wave's u = W[:, 128:] . skip - 8 MFMAs, 4 LDS reads, 2 LDS writes -, and in the tail a B wave's assembly of the\n next step's two tiles (behind `step + 1 < T`: 2 LDS reads, the adds and selects of two tiles, the pack, 1 LDS write).  SQ_INSTS_VALU counts MFMAs as VALU.)", file=out)
     return totals
 
 

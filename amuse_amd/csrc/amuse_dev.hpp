@@ -566,15 +566,19 @@ __device__ __forceinline__ void exchange_sum(f32x4 (&part)[kTiles], f32x4* exch,
 constexpr int kExchBytes = 2 * 4 * kTiles * 64 * 16;  // 64 KiB
 
 // ---- Philox4x32-10 (counter-based normals below, train-mode sampling dropout masks)
+// round i of the ten under key (k0, k1): a caller that spreads a draw over its own schedule walks the rounds itself (k_sampler8.hip)
+__device__ __forceinline__ void philox4x32_round(uint32_t (&c)[4], uint32_t k0, uint32_t k1, uint32_t i) {
+    k0 += i * 0x9E3779B9u; k1 += i * 0xBB67AE85u;
+    // each 32 x 32 -> 64 product as ONE multiply (v_mad_u64_u32) instead of a v_mul_hi_u32 / v_mul_lo_u32 pair: the integer multiplies run at a quarter of
+    // the VALU rate and are most of a draw's time
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
+    const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0, hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
+    const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
+    c[0] = n0; c[1] = lo1; c[2] = n2; c[3] = lo0;
+}
 __device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
 #pragma unroll
-    for (int i = 0; i < 10; ++i) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
-        const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
-        c[0] = n0; c[1] = lo1; c[2] = n2; c[3] = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
+    for (uint32_t i = 0; i < 10; ++i) philox4x32_round(c, k0, k1, i);
 }
 // ---- train-mode sampling dropout (amuse_hip.h amuse_set_sample_dropout): keep bits of elements 4 e4 .. 4 e4 + 3 of dropout site
 // ls = 4 layer + site; element e uses draw e % 4 of Philox4x32-10(key = seed, counter = (clip, step, ls << 16 | e / 4, 2 + epoch)),
@@ -711,9 +715,8 @@ __device__ __forceinline__ void combine_rs(f32x4 (&part)[kTiles], f32x4 (&x)[kTi
 }
 
 // ---- counter-based normals: Philox4x32-10, key = seed, counter = (clip, step, feature/4, stream)
-__device__ __forceinline__ f32x4 counter_normal4(uint64_t seed, uint64_t clip, uint32_t step, uint32_t q, uint32_t stream) {
-    uint32_t c[4] = {(uint32_t)clip, step, q, stream};
-    philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+// counter_normal4 = philox_normal4 of the ten rounds' result
+__device__ __forceinline__ f32x4 philox_normal4(const uint32_t (&c)[4]) {
     float u[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) u[i] = (float)(c[i] >> 8) * 5.9604644775390625e-8f + 2.98023223876953125e-8f;
@@ -723,6 +726,11 @@ __device__ __forceinline__ f32x4 counter_normal4(uint64_t seed, uint64_t clip, u
     const float r1 = __builtin_amdgcn_sqrtf(-1.38629436111989061883f * __builtin_amdgcn_logf(u[2]));
     return f32x4{r0 * __builtin_amdgcn_cosf(u[1]), r0 * __builtin_amdgcn_sinf(u[1]),
                  r1 * __builtin_amdgcn_cosf(u[3]), r1 * __builtin_amdgcn_sinf(u[3])};
+}
+__device__ __forceinline__ f32x4 counter_normal4(uint64_t seed, uint64_t clip, uint32_t step, uint32_t q, uint32_t stream) {
+    uint32_t c[4] = {(uint32_t)clip, step, q, stream};
+    philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+    return philox_normal4(c);
 }
 
 // ---- scheduler.step on one element (diffusers 0.17.1 DDIM / DDPM; amuse_hip.h amuse_schedule has the coefficients):

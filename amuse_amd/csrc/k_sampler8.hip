@@ -29,8 +29,8 @@
 //
 // LDS (163,328 B): combine matrix A8 [8 rows][8 tiles][64] f32x4 - fp32 partials off the diagonal, the published
 // bf16 operands ON it (slots (c, c), c < 4), so the gather of one combine never aliases the partial writes of the
-// next - | row statistics | bf16 skip stack | small parameters | static token rows | latent | double-buffered time
-// token.
+// next - | row statistics (and, in their reservation's last 32 B, the step's scheduler coefficients) | bf16 skip stack | small
+// parameters | static token rows | latent | double-buffered time token.
 #include "amuse_sample8.hpp"
 
 // This file is compiled twice: as is (bf16 operands: k_sample8 / launch_sample8) and through k_sampler8h.hip with AMUSE_OP_F16
@@ -60,6 +60,7 @@ namespace {
 
 // (amuse_sample8.hpp: combine matrix A8, then the row statistics at kStat8Off)
 constexpr int kSkip8Off = kStat8Off + 8 * 16 * 8;              // [4 levels][4 pairs][64] uint4
+constexpr int kCoef8Off = kSkip8Off - 32;                      // the step's 8 scheduler coefficients: the last 32 B of the statistics' 1 KiB, which use 512 B
 constexpr int kPv8Off = kSkip8Off + 4 * 4 * 64 * 16;
 constexpr int kPv8Floats = kLayers * kEncPv + 4 * kD + 2 * kD;
 constexpr int kTokRows8Off = kPv8Off + kPv8Floats * 4;         // [8 tiles][64] f32x4
@@ -78,6 +79,15 @@ constexpr int kC2N0 = 16, kC2N1 = 12;
 // units a B wave issues during the A waves' attention phase; the rest of its 32 follow behind its first FFN MFMAs
 // (18 / 20 / 21 / 22 / 23 / 24 / 26 with kALate = 8: 33.5 / 33.0 / 33.1 / 32.8 / 32.9 / 33.4 / 33.7 ms)
 constexpr int kBEarly = 22;
+// ... and go out in chunks of kDrawChunk with one slice of the step's noise draw behind each chunk (last block only, role_loop8): the ten Philox rounds spread
+// over all slices but the last, which holds Box-Muller.  Behind the whole fetch - and behind a wait for it - the draw cost 1.4 k cycles of the step's chain; sliced
+// it still costs 0.7 k (the four reducers draw at the same time, and an in-order wave blocked at a load cannot run the VALU work behind it), which is why the
+// multiplies themselves were halved (amuse_dev.hpp philox4x32_round).  2 / 4 / 8 with the paired multiplies: 31.69 / 31.63 / 31.83 ms at 256 clips against 31.86;
+// 2 / 4 with the 64-bit multiply: 31.94 / 31.42 against 31.90 (docs/history.md 4.1b, round 10).
+constexpr int kDrawChunk = 4;
+constexpr int kDrawSlices = (kBEarly + kDrawChunk - 1) / kDrawChunk;
+constexpr int kDrawRounds = (10 + kDrawSlices - 2) / (kDrawSlices - 1);   // Philox rounds per slice
+static_assert(kDrawSlices >= 2, "one slice of rounds, one of Box-Muller");
 // units of an A wave's FFN half (its last ones, F2b and the tail of F2a) that go out behind ITS first FFN MFMAs instead of behind the out_proj
 // combine's gather.  The reducers leave that gather at the same moment and need their own late units first (F2a reads them ~0.7 k cycles
 // later, the A wave's F2b is the last thing it runs and it waits at the linear2 combine afterwards anyway): issued behind the gather, the A waves'
@@ -372,13 +382,38 @@ __device__ __forceinline__ uint32_t sdrop8_row_bits(const SampleKernelArgs& a, c
     return sdrop_bits4(d.seed, cu, d.step, ls, e4, d.epoch2, d.thr) | (sdrop_bits4(d.seed, cu, d.step, ls, e4 + 4, d.epoch2, d.thr) << 4);
 }
 
+// A noise draw in progress: the Philox counters of a reducer's two tiles, and whether this lane draws at all.  Local to the early fetch of ONE block.
+struct Draw8 {
+    uint32_t c[2][4];
+    bool on;
+};
+template <int I>
+struct Slice {
+    static constexpr int value = I;
+};
+struct NoDraw {
+    template <int I>
+    __device__ void operator()(Draw8&, Slice<I>) const {}
+};
+// The reducers' early fetch: units C0 .. kBEarly - 1 of their FFN half into slots C0 .., slice i of `early` behind chunk i.  One body for every block - the
+// slices sit behind a uniform branch that touches no ring slot (combine_publish_c2 has the reason).
+template <int C0, class Early>
+__device__ __forceinline__ void early_fetch(Ring& rg, Draw8& dw, Early& early) {
+    if constexpr (C0 < kBEarly) {
+        constexpr int N = kBEarly - C0 < kDrawChunk ? kBEarly - C0 : kDrawChunk;
+        ring_issue<N, kR8, C0>(rg);
+        early(dw, Slice<C0 / kDrawChunk>{});
+        early_fetch<C0 + N>(rg, dw, early);
+    }
+}
+
 // One TransformerEncoderLayer.forward_post (cross_attention.py:259-272), A / B role split.  The two roles are
 // separate instantiations (and the whole step loop is instantiated per role, OP_KERNEL below): sharing one body
 // behind a runtime branch makes hipcc's register allocator spill hundreds of VGPRs at the merges.
 // xb: the residual stream as four packed bf16 operands (every wave); xo: this B wave's two feature tiles in fp32.
 // DROP: train-mode sampling - the A waves draw the attention bits in front of in_proj and their FFN bits in the out_proj combine's
 // waiting time, the B waves all of theirs (both combines, FFN) while the A waves run attention
-template <bool ROLEA, bool PROF, bool DROP, class Early = NoHook>
+template <bool ROLEA, bool PROF, bool DROP, class Early = NoDraw>
 __device__ __forceinline__ void encoder_block8(OPV (&xb)[4], f32x4 (&xo)[2], Ring& rg, const float* pv,
                                                const bool (&kvalid)[4], char* lds, int h, int lane, bool next_has_skip,
                                                const uint4* skip_next, Prof8& pf, const SampleKernelArgs& a,
@@ -431,8 +466,9 @@ __device__ __forceinline__ void encoder_block8(OPV (&xb)[4], f32x4 (&xo)[2], Rin
         combine_publish_c2<kC2N0, kC2N1, 32 - kC2N0 - kC2N1>(part, xb, lds, h, lane, rg, next_has_skip, skip_next);
     } else {
         // ---- ring empty on entry: fetch this wave's FFN half while the A waves run attention
-        ring_issue<kBEarly, kR8, 0>(rg);
-        early();   // work of the reducers' waiting time that no other wave's result feeds (role_loop8: the step's ancestral noise)
+        // ... with work of the reducers' waiting time that no other wave's result feeds between the loads (role_loop8: the step's ancestral noise)
+        Draw8 dw;
+        early_fetch<0>(rg, dw, early);
         // bits 0..7: dropout1 of tiles 2 h, 2 h + 1; 8..15: dropout2 of the same; 16..31: the FFN's inner dropout
         uint32_t bbits = 0;
         if constexpr (DROP)
@@ -460,6 +496,7 @@ __device__ __forceinline__ void role_loop8(const Args& a, char* smem, int w8, co
     f32x4* latl = reinterpret_cast<f32x4*>(smem + kLat8Off);
     float* ttl = reinterpret_cast<float*>(smem + kTT8Off);
     float2* stats = reinterpret_cast<float2*>(smem + kStat8Off);
+    const float* cfl = reinterpret_cast<const float*>(smem + kCoef8Off);   // this step's scheduler coefficients (step top)
     const float* pv_skip = pvl + kLayers * kEncPv;
     const float* pv_final = pv_skip + 4 * kD;
     const int lane = L0.lane, g = L0.g, r = L0.r, h = w8 & 3;
@@ -506,9 +543,15 @@ __device__ __forceinline__ void role_loop8(const Args& a, char* smem, int w8, co
         f32x4 zn[2] = {splat4(0.f), splat4(0.f)};   // B waves: this step's ancestral noise of their two tiles, drawn ahead of the tail (below)
 #pragma unroll
         for (int c = 0; c < 4; ++c) xb[c] = __builtin_bit_cast(OPV, *xb_slot(smem, c, lane));
-        // next step's time token -> the other LDS buffer (the reducers read it in this step's tail, many barriers later)
-        if (!ROLEA && w8 == 4 && lane < 32 && step + 1 < a.T)
-            st4(ttl + ((step + 1) & 1) * kD + 4 * lane, ld4(a.time_tok + (size_t)(step + 1) * kD + 4 * lane));
+        // next step's time token -> the other LDS buffer (the reducers read it in this step's tail, many barriers later); in the same load and store, by lanes
+        // 32 and 33, THIS step's eight scheduler coefficients -> LDS: the reducers read them in the last block (is there noise to draw?) and in the tail, where
+        // an LDS read neither waits for the weight stream's loads (vmcnt retires in order) nor costs a trip to memory on the reducers' lone stretch
+        if (!ROLEA && w8 == 4) {
+            const bool tt = lane < 32;
+            const float* src = tt ? a.time_tok + (size_t)(step + 1) * kD + 4 * lane : a.coef + (size_t)step * 8 + 4 * (lane & 1);
+            float* dst = reinterpret_cast<float*>(smem + (tt ? kTT8Off + (((step + 1) & 1) * kD + 4 * lane) * 4 : kCoef8Off + 16 * (lane & 1)));
+            if (tt ? step + 1 < a.T : lane < 34) st4(dst, ld4(src));
+        }
         if (tap && step == 0) {
             store_tap_tile(a.tap_out, 0, 2 * h, xo[0], g, r);
             store_tap_tile(a.tap_out, 0, 2 * h + 1, xo[1], g, r);
@@ -543,15 +586,31 @@ __device__ __forceinline__ void role_loop8(const Args& a, char* smem, int w8, co
             stamp8<PROF>(pf);  // 0: block start (after the skip linear, if any)
             // The noise of the scheduler update depends on (seed, clip, step, feature) alone, not on the network: Philox4x32-10 (80 integer multiplies in two
             // serial chains) and Box-Muller for two tiles, which the tail used to walk with the whole workgroup waiting.  The reducers draw it in the LAST
-            // block instead, behind their early fetch, while they wait for the A waves' attention anyway; eight registers carry it to the tail.
-            auto early = [&]() {
+            // block instead, INSIDE their early fetch (slice I behind its chunk I: kDrawChunk), while they wait for the A waves' attention anyway; eight
+            // registers carry it to the tail.  counter_normal4's arithmetic, the two tiles' rounds side by side; sigma comes from LDS (step top), so no wait
+            // here covers the ring's loads.  Every lane computes - a lane mask would cost a branch per slice - and the lanes that do not draw keep their 0.
+            auto early = [&](Draw8& dw, auto slice) {
                 if constexpr (!ROLEA && !DROP) {   // (the train-mode instantiations have no register to spare: they draw in the tail)
+                    constexpr int I = decltype(slice)::value;
                     if (blk == kLayers - 1 && !a.no_update && !a.step_noise) {
-                        const Lane8 L = lane_info(a, lane);
-                        if (a.coef[(size_t)step * 8 + 5] != 0.f && L.is_lat) {
+                        if constexpr (I == 0) {
+                            const Lane8 L = lane_info(a, lane);
+                            dw.on = L.is_lat && cfl[5] != 0.f;
 #pragma unroll
-                            for (int i = 0; i < 2; ++i)
-                                zn[i] = counter_normal4(a.seed, a.clip0 + (uint64_t)L.clip, (uint32_t)step, (uint32_t)(4 * (2 * h + i) + L.g), 1u);
+                            for (int i = 0; i < 2; ++i) {
+                                dw.c[i][0] = (uint32_t)(a.clip0 + (uint64_t)L.clip); dw.c[i][1] = (uint32_t)step;
+                                dw.c[i][2] = (uint32_t)(4 * (2 * h + i) + L.g); dw.c[i][3] = 1u;
+                            }
+                        }
+#pragma unroll
+                        for (int rd = I * kDrawRounds; rd < (I + 1) * kDrawRounds && rd < 10 && I < kDrawSlices - 1; ++rd) {
+                            philox4x32_round(dw.c[0], (uint32_t)a.seed, (uint32_t)(a.seed >> 32), (uint32_t)rd);
+                            philox4x32_round(dw.c[1], (uint32_t)a.seed, (uint32_t)(a.seed >> 32), (uint32_t)rd);
+                        }
+                        if constexpr (I == kDrawSlices - 1) {
+                            const f32x4 z0 = philox_normal4(dw.c[0]), z1 = philox_normal4(dw.c[1]);
+                            zn[0] = dw.on ? z0 : zn[0];
+                            zn[1] = dw.on ? z1 : zn[1];
                         }
                     }
                 }
@@ -570,12 +629,11 @@ __device__ __forceinline__ void role_loop8(const Args& a, char* smem, int w8, co
         // ---- final LayerNorm (SkipTransformerEncoder.norm) + scheduler.step (diffusers 0.17.1 DDIM / DDPM;
         // amuse_hip.h amuse_schedule) on the B waves' own tiles; the latent lives in LDS
         // The reducers walk this tail alone on their SIMD (the A waves are parked at the step barrier), so every latency in it is
-        // step time.  The step's coefficients (global memory) are fetched BEFORE the barrier and land while the statistics are computed
-        // and exchanged; behind it the final LayerNorm's parameters and this wave's two latent tiles are read up front, beside the
-        // statistics, and the two tiles go through each stage side by side (eight independent update chains) instead of tile after
-        // tile.  Same operations on the same operands.
+        // step time.  The step's coefficients (in LDS since the step top) are read BEFORE the barrier; behind it the final LayerNorm's
+        // parameters and this wave's two latent tiles are read up front, beside the statistics, and the two tiles go through each stage
+        // side by side (eight independent update chains) instead of tile after tile.  Same operations on the same operands.
         if constexpr (!ROLEA) {
-            const float* cf = a.coef + (size_t)step * 8;
+            const float* cf = cfl;
             const float sb = cf[0], sa = cf[1], c0 = cf[2], cx = cf[3], ce = cf[4], sg = cf[5], clipv = cf[6];
             const float2 st = row_stats32(xo);
             if (g == 0) stats[h * 16 + r] = st;

@@ -35,6 +35,7 @@ EXPORTS = [
     "amuse_body_create", "amuse_body_destroy", "amuse_body_set_subjects", "amuse_body_reserve", "amuse_body_forward", "amuse_body_vertex_loss", "amuse_body_info",
     "amuse_body_enable_grad", "amuse_body_vertex_loss_grad",
     "amuse_longform_plan", "amuse_stitch_windows",
+    "amuse_seam_plan", "amuse_seam_cost", "amuse_seam_path", "amuse_seam_select",
     "amuse_smooth_banks", "amuse_smooth_motion",
     "amuse_bvh_layout", "amuse_bvh_format", "amuse_bvh_motion", "amuse_bvh_decode",
     "amuse_resample_plan", "amuse_resampler_create", "amuse_resampler_destroy", "amuse_resample", "amuse_debug_resample_bank",
@@ -236,6 +237,12 @@ def load() -> C.CDLL:
     lib.amuse_longform_plan.argtypes = [C.c_longlong, C.c_int, ip, ip, ip]
     lib.amuse_stitch_windows.argtypes = [fp, fp, C.c_int, ip, ip, C.c_int, C.c_int, fp, fp, fp, vp]
     lib.amuse_longform_plan.restype = lib.amuse_stitch_windows.restype = C.c_int
+    # long-form candidates (csrc/amuse_seam.hip): the plan (host only), the seam-cost matrix, the best path and the gather, all context-free
+    lib.amuse_seam_plan.argtypes = [C.c_int, ip, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_size_t)]
+    lib.amuse_seam_cost.argtypes = [fp, fp, C.c_int, ip, ip, C.c_int, C.c_int, C.c_int, fp, fp, C.c_float, vp, vp, vp]
+    lib.amuse_seam_path.argtypes = [vp, C.c_int, ip, C.c_int, vp, vp, vp]
+    lib.amuse_seam_select.argtypes = [fp, fp, vp, C.c_int, C.c_int, C.c_int, fp, fp, vp]
+    lib.amuse_seam_plan.restype = lib.amuse_seam_cost.restype = lib.amuse_seam_path.restype = lib.amuse_seam_select.restype = C.c_int
     # motion smoothing (csrc/amuse_smooth.hip): the bank needs no GPU; the filter is context-free (frames and half_window are HOST arrays)
     lib.amuse_smooth_banks.argtypes = [C.c_int, C.POINTER(C.c_float)]
     lib.amuse_smooth_motion.argtypes = [fp, fp, C.c_int, ip, C.POINTER(C.c_ubyte), fp, fp, fp, vp]

@@ -252,14 +252,20 @@ class PretrainedLPDM_v1:
         con, emo, sty = self.audio_engine.features_ragged(chunks)
         return [(con[k:k + 1], emo[k:k + 1], sty[k:k + 1]) for k in range(len(chunks))]
 
-    def infer_long(self, waves, hop_frames: int = 270, framerate=16000, baseline=False, sample_rate=None, smooth=None):
+    def infer_long(self, waves, hop_frames: int = 270, framerate=16000, baseline=False, sample_rate=None, smooth=None, candidates: int = 1):
         """AN EXTENSION (the reference has no such path: it asks for 10 s WAVs, scripts/trainer.py:506): waveforms of ANY length -> [{"poses": (L, 55, 3),
         "trans": (L, 3)}, ...] with L = max(300, floor(3 n / 1600)) frames each (amuse_amd/longform.py).  `waves`: a list of (C, n) or (n,) 16 kHz waveforms.
         The mean of the WHOLE waveform is removed once (trainer.py:521), the waveform is cut into the plan's windows (stride hop_frames, the last one short),
         all windows of all waveforms are embedded as one batch (process_seq_list) and sampled by ONE diffusion_backward - one clip index per window from the
         clip counter, in waveform order and then window order - and ONE stitch joins them.  The windows are sampled independently; the crossfade over the
-        frames two neighbouring windows share hides the seam, it does not make them agree.  A waveform of at most 160,000 samples is one window: bitwise
-        process_single_seq + diffusion_backward.
+        frames two neighbouring windows share hides the seam, it does not make them agree (`candidates` below at least CHOOSES windows that agree better).
+        A waveform of at most 160,000 samples is one window: bitwise process_single_seq + diffusion_backward.
+        candidates K (an extension of its own, amuse_amd/seam.py; 1: this code is not entered - the same bytes and the same clip counter): K in 2..64 samples
+        K candidates of EVERY window in the one diffusion_backward - row g K + c is candidate c of window g, conditions repeated K times (the front-end still
+        runs once per window), clip index = clip counter + g K + c, the counter advances by K x the windows - then seam.best_windows scores every pair of
+        neighbouring windows' candidates over the frames they share and keeps the path of least total cost, which is what the stitch joins.  Every returned
+        dict gains "seam": {"choice": [candidate per window], "total": cost of the chosen path, "total_first": cost of the all-first-candidates path};
+        reading that small report is the one host synchronisation added.  A one-window waveform takes candidate 0.
         sample_rate (an extension of its own, amuse_amd/resample.py): the rate of `waves` in Hz.  None or 16000: the waveforms are read as 16 kHz, as everywhere
         on this path.  Another rate: channel 0 of every waveform goes through the HIP resampler first and everything above applies to its output.  (`framerate`
         is NOT this: it mirrors the reference's argument, which nothing reads.)
@@ -285,13 +291,27 @@ class PretrainedLPDM_v1:
             return []
         embs = self.process_seq_list(chunks, framerate=framerate, baseline=baseline)
         cat = lambda k: torch.cat([torch.as_tensor(e[k]).to(self.device, torch.float32).reshape(1, -1) for e in embs])
-        out = self.diffusion_backward(len(chunks), cat(0), cat(1), cat(2))
+        K, seam_info = int(candidates), None
+        if K == 1:
+            out = self.diffusion_backward(len(chunks), cat(0), cat(1), cat(2))
+        else:
+            from . import seam
+            if not 2 <= K <= seam.MAX_CANDIDATES:
+                raise ValueError(f"candidates {candidates} outside 1..{seam.MAX_CANDIDATES}")
+            con, emo, sty = (cat(k).repeat_interleave(K, dim=0) for k in range(3))
+            out = self.diffusion_backward(len(chunks) * K, con, emo, sty)
+            out["poses"], out["trans"], seam_info = seam.best_windows(out["poses"], out["trans"], windows, frames, K, hop_frames, F=self.seq_len)
         poses, trans = longform.stitch(out["poses"], out["trans"], windows, frames, hop_frames, F=self.seq_len)
         if smooth is not None:
             from . import smooth as smooth_mod
             poses, trans = smooth_mod.smooth(poses, trans, frames, **smooth_mod.options(**smooth))
         offs = np.concatenate([[0], np.cumsum(frames)]).astype(int)
-        return [{"poses": poses[offs[k]:offs[k + 1]], "trans": trans[offs[k]:offs[k + 1]]} for k in range(len(frames))]
+        res = [{"poses": poses[offs[k]:offs[k + 1]], "trans": trans[offs[k]:offs[k + 1]]} for k in range(len(frames))]
+        if seam_info is not None:
+            from . import seam
+            for r, rep in zip(res, seam.report(seam_info, windows, K)):
+                r["seam"] = rep
+        return res
 
     def motion_to_latent(self, motion, sample: bool = True, clip_index0: Optional[int] = None):
         """The motion half of _loader_helper_v1 (infer_ldm.py:453-465): `motion` (frames, 168) = 55 x 3 SMPL-X

@@ -3,7 +3,8 @@ amuse_longform_plan / amuse_stitch_windows; csrc/k_stitch.hip).
 
 AN EXTENSION - the reference has no such path: it asks for pre-cut audio ("Make sure each audio is a 10 sec wav file", scripts/trainer.py:506).  The windows are
 sampled INDEPENDENTLY (the Denoiser's state is one latent per clip; nothing is shared between windows inside the sampler); the crossfade over the frames two
-neighbouring windows both produced hides the seam, it does not make the windows agree.
+neighbouring windows both produced hides the seam, it does not make the windows agree.  (amuse_amd/seam.py - `--long-form-candidates K`, infer_long(candidates=K) -
+samples K candidates of every window and joins the ones that agree best where they meet; for K = 1 the sentence stands.)
 
 The plan is the library's (`plan` calls it; nothing here restates its arithmetic), the join is a HIP kernel (`stitch`); there is no other implementation."""
 from __future__ import annotations

@@ -26,6 +26,7 @@ Outputs: <renders>/Custom_audios_<stamp>_E<epoch>/rep<i>/rst_<k>/seq_<n>/<actor>
 
 Beyond the reference (which asks for 10 s WAVs, trainer.py:506): `--fn infer_gesture --long-form [--hop-frames 270]` turns a WAV of any length into ONE NPZ of
 floor(30 x seconds) frames - overlapping 10 s windows, sampled independently, crossfaded where they overlap (amuse_amd/longform.py).  Off by default.
+`--long-form-candidates K` samples K candidates of every window and joins the path of least seam cost (amuse_amd/seam.py).  Off by default (K = 1).
 `--fn infer_gesture | edit_gesture --resample` converts a WAV of another rate to the 16 kHz the front-end is built for, in a HIP kernel
 (amuse_amd/resample.py); the reference reads every file as 16 kHz whatever its header says.  Off by default.
 `--fn infer_gesture | edit_gesture --preview --smplx-models DIR [--preview-size 512] [--preview-stride 10] [--preview-frames]` writes, beside every
@@ -240,6 +241,13 @@ def build_parser() -> argparse.ArgumentParser:
                          "windows agree.  A WAV of at most 160,000 samples gives the bytes it gives without the switch")
     ap.add_argument("--hop-frames", type=int, default=270, help="--long-form: frames between window starts, a multiple of 3 in 150..300 (default 270: one second "
                                                                 "of overlap; 300: plain concatenation)")
+    ap.add_argument("--long-form-candidates", type=int, default=1, metavar="K",
+                    help="--long-form: K candidates of every window (1..64, default 1: nothing changes by a bit) are sampled in the WAV's one batch, every pair "
+                         "of neighbouring windows' candidates is scored by how far their shared frames are apart as rotations, and the windows on the path of "
+                         "least total seam cost are the ones joined - all in HIP kernels (amuse_amd/seam.py).  An extension and this project's own method, "
+                         "compared with no other implementation; whether a trained checkpoint's candidates differ enough at the seams for the choice to matter "
+                         "has not been measured.  A WAV of one window is not expanded.  One line per WAV reports the cost of the all-first-candidates path "
+                         "-> the chosen path's.  The NPZ layout is unchanged; needs an overlap (--hop-frames below 300)")
     ap.add_argument("--resample", action="store_true",
                     help="infer_gesture / edit_gesture: a WAV whose header states another rate than 16,000 Hz is converted to 16 kHz on the GPU before the "
                          "front-end reads it - an extension, the reference drops the rate and reads every file as 16 kHz (so a 48 kHz recording is animated as "
@@ -362,7 +370,24 @@ def check_switches(args):
             longform.plan(0, args.hop_frames)      # the library's own check of the hop, before anything is loaded
         except _lib.AmuseHipError as e:
             raise SystemExit(f"--hop-frames {args.hop_frames}: {e}")
+    if args.long_form_candidates != 1:
+        if not args.long_form:
+            raise SystemExit("--long-form-candidates belongs to --long-form: it chooses among candidates of a long WAV's windows")
+        from . import seam
+        if not 1 <= args.long_form_candidates <= seam.MAX_CANDIDATES:
+            raise SystemExit(f"--long-form-candidates {args.long_form_candidates} outside 1..{seam.MAX_CANDIDATES}")
+        if args.hop_frames >= 300:
+            raise SystemExit(f"--long-form-candidates needs frames that two windows share: --hop-frames {args.hop_frames} leaves none")
     return smooth_opts, bvh_opts
+
+
+def long_form_config(args, test_cfg: dict) -> None:
+    """--long-form [--hop-frames H] [--long-form-candidates K] -> TRAIN_PARAM.test (the keys are this path's own; without a switch the configuration is left as
+    it is, and long_form_candidates is written only when K > 1)"""
+    if args.long_form:
+        test_cfg["long_form"], test_cfg["hop_frames"] = True, int(args.hop_frames)
+        if args.long_form_candidates > 1:
+            test_cfg["long_form_candidates"] = int(args.long_form_candidates)
 
 
 def post_run(args, tr, written, models, bvh_opts, device) -> None:
@@ -463,8 +488,7 @@ def main(argv=None):
     tp["test"]["audio_metrics"] = bool(args.audio_metrics)
     if args.resample:        # (as below: the key is this path's own; without the switch the configuration is left as it is)
         tp["test"]["resample"] = True
-    if args.long_form:       # (the keys are this path's own; without the switch the configuration is left as it is)
-        tp["test"]["long_form"], tp["test"]["hop_frames"] = True, int(args.hop_frames)
+    long_form_config(args, tp["test"])
     if smooth_opts is not None:     # (as above: the key is this path's own)
         tp["test"]["smooth"] = smooth_opts
     if args.motion_metrics:  # (the keys are this path's own; without the switch the configuration is left as it is)

@@ -270,7 +270,9 @@ def run_jobs(model, jobs: List[dict], return_latents: bool = False, batched: boo
     """Sample every job; returns, per job and in job order, the reference's `rst` entry
     {"feats": (bsz,300,168), "audio", "info"[, "swap_info"]} (trainer.py:884-890) [+ "latents"].
     A job that carries "long_form": {"frames": L, "hop": h} is ONE waveform cut into bsz overlapping windows (an extension, amuse_amd/longform.py): its rows
-    are sampled like any job's - one clip index per window - and joined before they are packed, so it yields feats (1, L, 168).
+    are sampled like any job's - one clip index per window - and joined before they are packed, so it yields feats (1, L, 168).  With "K": K > 1 in that dict
+    (amuse_amd/seam.py) the job's bsz = W K rows are K candidates of every window, candidate fastest: the windows on the path of least seam cost are selected
+    before the join, and the job's entry gains "seam": {"choice", "total", "total_first"} (reading that small report is the one host synchronisation added).
     smooth (an extension, amuse_amd/smooth.py; None: nothing changes by a bit): {"window", "order"[, "hands_window"]} - every motion of every job goes through
     the Savitzky-Golay filter on SO(3) after the long-form join and before it is packed, each clip (or joined motion) as a sequence of its own: whatever reads
     the result - the NPZ, the metrics, the previews - sees the smoothed motion.  Per job, so a sharded run keeps the single-process bytes.
@@ -295,10 +297,18 @@ def run_jobs(model, jobs: List[dict], return_latents: bool = False, batched: boo
     offs = np.concatenate([[0], np.cumsum([j["bsz"] for j in jobs])]).astype(int)
 
     def finish(j, poses, trans, lat):
-        lf = jobs[j].get("long_form")
+        lf, seam_report = jobs[j].get("long_form"), None
         if lf is not None:      # the job's rows are the windows of ONE waveform (amuse_amd/longform.py): joined into one motion of lf["frames"] frames
             from . import longform
-            poses, trans = (t[None] for t in longform.stitch(poses, trans, [jobs[j]["bsz"]], [lf["frames"]], lf["hop"], F=poses.shape[1]))
+            K = int(lf.get("K", 1))
+            W = jobs[j]["bsz"] // K
+            if K > 1:           # the job's rows are K candidates of every window, candidate fastest (amuse_amd/seam.py): the path of least seam cost is joined
+                from . import seam
+                poses, trans, info = seam.best_windows(poses, trans, [W], [lf["frames"]], K, lf["hop"], F=poses.shape[1])
+                seam_report = seam.report(info, [W], K)[0]      # the one host synchronisation the choice adds: its small report
+                print(f"[amuse_amd] long-form candidates: {jobs[j]['take']}: K = {K}, {W} windows, seam cost {seam_report['total_first']:.6g} (first candidates) "
+                      f"-> {seam_report['total']:.6g} (chosen: {seam_report['choice']})")
+            poses, trans = (t[None] for t in longform.stitch(poses, trans, [W], [lf["frames"]], lf["hop"], F=poses.shape[1]))
         if smooth is not None:  # amuse_amd/smooth.py: after the join, so the filter runs across the seams as well
             from . import smooth as smooth_mod
             poses, trans = smooth_mod.smooth_batch(poses, trans, smooth)
@@ -307,6 +317,8 @@ def run_jobs(model, jobs: List[dict], return_latents: bool = False, batched: boo
             r["swap_info"] = jobs[j]["swap_info"]
         if return_latents:
             r["latents"] = lat
+        if seam_report is not None:
+            r["seam"] = seam_report
         out[j] = r
 
     if not batched:
@@ -514,9 +526,16 @@ class trainer:
         through the front-end as one batch.  A WAV of at most 160,000 samples is one window holding the whole waveform: the job the default path builds."""
         from . import longform
         hop = int(self.config["TRAIN_PARAM"]["test"].get("hop_frames", longform.DEFAULT_HOP))
+        # TRAIN_PARAM.test.long_form_candidates K > 1 (amuse_amd.main --long-form-candidates; amuse_amd/seam.py): a WAV of W > 1 windows is a job of bsz = W K
+        # clips, candidate fastest - the front-end still runs once per window, its embeddings are repeated K times - and carries K in its long_form dict;
+        # run_jobs chooses before it joins.  A WAV of one window has no seam and is not expanded.  Still one job per WAV, so the candidates stay on one rank.
+        K = int(self.config["TRAIN_PARAM"]["test"].get("long_form_candidates", 1))
+        if not 1 <= K <= 64:
+            raise ValueError(f"TRAIN_PARAM.test.long_form_candidates {K} outside 1..64")
         n = self._long_form_samples(audios)
         plans = [longform.plan(k, hop) for k in n]
-        mine = local_jobs([(p["windows"], False, False) for p in plans], self.rank, self.world)
+        cand = [K if p["windows"] > 1 else 1 for p in plans]
+        mine = local_jobs([(p["windows"] * c, False, False) for p, c in zip(plans, cand)], self.rank, self.world)
         chunks = []
         for k, a in enumerate(audios):
             if mine[k]:
@@ -535,12 +554,16 @@ class trainer:
         jobs, pos = [], 0
         for k, a in enumerate(audios):
             W, lf = plans[k]["windows"], {"frames": plans[k]["frames"], "hop": hop}
+            if cand[k] > 1:
+                lf["K"] = cand[k]
             if not mine[k]:
-                jobs.append(_remote_job("scott", a.stem, W, "scott", long_form=lf))
+                jobs.append(_remote_job("scott", a.stem, W * cand[k], "scott", long_form=lf))
                 continue
             con, emo, sty = (torch.cat([torch.as_tensor(e[i]).reshape(1, -1) for e in embs[pos:pos + W]]) for i in range(3))
             pos += W
-            jobs.append(_job("scott", a.stem, con, emo, sty, W, "scott", None, None, None, long_form=lf))
+            if cand[k] > 1:
+                con, emo, sty = (t.repeat_interleave(cand[k], dim=0) for t in (con, emo, sty))
+            jobs.append(_job("scott", a.stem, con, emo, sty, W * cand[k], "scott", None, None, None, long_form=lf))
         return jobs, mine
 
     # ------------------------------------------------------------------ motion metrics (opt-in)

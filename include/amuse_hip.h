@@ -652,7 +652,8 @@ int amuse_body_info(const amuse_body_ctx* ctx, int what);
  * AN EXTENSION: the reference has no such path - it asks for 10 s WAVs ("Make sure each audio is a 10 sec wav file", scripts/trainer.py:506).  A longer waveform is
  * cut into overlapping windows of the model's clip (F = 300 frames = 160,000 samples: 16 kHz audio, 30 fps motion, the rates the reference assumes of every file;
  * nothing resamples), every window is embedded and sampled as a clip of its own - INDEPENDENTLY: the Denoiser's state is one latent per clip, nothing is shared
- * between windows - and the frames two neighbouring windows both produced are crossfaded.  The crossfade hides the seam; it does not make the windows agree.
+ * between windows - and the frames two neighbouring windows both produced are crossfaded.  The crossfade hides the seam; it does not make the windows agree
+ * (the long-form candidates section below CHOOSES, among K samples of every window, the ones that agree best where they meet; for K = 1 the sentence stands).
  *
  * The window plan, stated once; needs no GPU and no context.  hop_frames h: the stride between window starts, a multiple of 3 (so that the hop is the whole
  * number h / 3 * 1600 of samples) with 150 <= h <= 300 (so that at most two windows cover a frame); the product's default is 270, one second of overlap.
@@ -680,6 +681,48 @@ int amuse_longform_plan(long long n_samples, int hop_frames, int* windows, int* 
  * (W_s - 1) hop < L_s <= (W_s - 1) hop + F; the pointers above non-NULL; the call's window rows and 56 x its output frames within an int. */
 int amuse_stitch_windows(const float* poses, const float* trans, int S, const int* windows, const int* frames, int F, int hop, const float* blend,
                          float* poses_out, float* trans_out, void* stream);
+
+/* ------------------------------------------------------------------ long-form candidates (csrc/amuse_seam_host.hpp, amuse_seam.hip, k_seam.hip; amuse_amd/seam.py)
+ * AN EXTENSION of the extension above, off by default: K candidates of every window are sampled in the one batch long-form inference launches anyway, every
+ * (candidate of window k, candidate of window k + 1) pair is scored by how far the frames the two windows share are apart AS ROTATIONS, and the path through the
+ * windows with the least total cost is what the join above then crossfades.  The project's OWN method: compared with no other implementation, checked against its
+ * own float64 restatement (tests/seam_ref.py) only.  Whether the candidates of a TRAINED checkpoint differ enough at the seams for the choice to matter has not
+ * been measured by anybody (profiles/seam_cost.txt: random-init weights only).
+ *
+ * Batch layout: row g K + c is candidate c of window g (windows in sequence order, then window order, as above; candidate fastest).  K = 1 is the join's layout.
+ * All four calls are context-free; the last three are stream-ordered, allocate nothing, copy nothing and never synchronise: they can be captured.  Per-sequence
+ * offsets travel by value in the kernel arguments, 32 sequences per launch.  Every check is made before any HIP call and answers AMUSE_EINVAL.
+ *
+ * amuse_seam_plan: host only.  *seams = sum (W_s - 1); *workspace_bytes = seams x 2 x K x (F - hop) x 55 x 16: the unit quaternions of every overlap row, each
+ * converted ONCE (0 without a seam).  The one statement of both numbers; either pointer may be NULL.  Checked: S >= 1; windows given, 1 <= W_s <= 32768; K in
+ * 1..64; F >= 2; F / 2 <= hop < F when any W_s > 1 (hop <= F otherwise); the call's batch rows x F and seams x K x K within an int. */
+int amuse_seam_plan(int S, const int* windows, int K, int F, int hop, long long* seams, size_t* workspace_bytes);
+/* The cost matrix.
+ *   poses dev [sum W_s K][F][55][3] axis-angle, trans dev [sum W_s K][F][3] or NULL (then trans_weight must be 0);  windows / frames: HOST int [S], as for the join,
+ *   with its (W - 1) hop < L <= (W - 1) hop + F check;  row_weight dev [F - hop], joint_weight dev [55], trans_weight: REQUIRED finite and >= 0 - the two device
+ *   arrays cannot be checked without a copy, so they are not: a negative or non-finite weight gives a cost that means nothing (trans_weight is checked);
+ *   workspace dev, 16-byte aligned, what amuse_seam_plan asks for;  cost_out dev double [seams][K][K], the seams of sequence s from sum_{s' < s} (W_s' - 1).
+ * Seam k of a sequence, a = candidate of window k, b = candidate of window k + 1, over the overlap rows that reach the output, i < O_k = min(F - hop, L - (k + 1) hop):
+ *   cost[k][a][b] = sum_i row_weight[i] ( sum_j joint_weight[j] theta_ij^2 + trans_weight |t_a(i + hop) - t_b(i)|^2 )
+ * theta_ij, in fp32: q = axis-angle -> unit quaternion of joint j of a's row i + hop and of b's row i (the join's arithmetic, series below 1e-6); r = conj(q_a) q_b;
+ * theta = 2 atan2(|r.xyz|, |r.w|) - no acos, and the hemisphere by the absolute value: the 2 pi - theta alias of a rotation costs what the rotation costs.  The
+ * translation's differences are fp32.  The squares, the products with the weights and all sums are double, in ONE order: per joint (and for the translation) over
+ * the rows i = 0, 1, .. as acc += row_weight[i] * (weight * square); then those 56 sums (and 8 zeros) as 64 lanes by the xor butterfly at distances 32, 16, 8, 4,
+ * 2, 1.  A pair's cost has the same bits whatever K, launch, sequence position or batch it is computed in.  No atomics.
+ * With no seam in the call nothing is launched and row_weight, workspace and cost_out may be NULL. */
+int amuse_seam_cost(const float* poses, const float* trans, int S, const int* windows, const int* frames, int K, int F, int hop, const float* row_weight,
+                    const float* joint_weight, float trans_weight, void* workspace, double* cost_out, void* stream);
+/* The best path: exact dynamic programming in double, one wave per sequence, a lane per candidate.
+ *   cost dev double [seams][K][K] as above;  choice_out dev int [sum W_s]: the chosen BATCH ROW g K + c of every window;  total_out dev double [S].
+ *   best[0][c] = 0;  best[k][b] = min over a = 0, 1, .. of v(best[k - 1][a] + cost[k - 1][a][b]);  the end candidate: the minimiser of best[W - 1][.];  then back
+ *   along the minimisers.  v(x) = x if x is finite, +infinity otherwise.  Every minimum starts from (+infinity, candidate 0) and is replaced on `<` only: ties go to
+ *   the lowest index, and where nothing is finite the candidate is 0 (and the total +infinity).  W = 1: candidate 0, total 0.  Any W (back-pointers are kept in LDS
+ *   for 960 windows at a time; longer sequences repeat the forward pass). */
+int amuse_seam_path(const double* cost, int S, const int* windows, int K, int* choice_out, double* total_out, void* stream);
+/* The gather: output row r is a BITWISE copy of input row choice[r], into the layout the join reads.
+ *   poses dev [n_in][F][55][3], trans dev [n_in][F][3];  choice dev int [n];  poses_out dev [n][F][55][3], trans_out dev [n][F][3].  trans and trans_out are NULL
+ *   together.  A choice outside 0 .. n_in - 1 is never read: its output row is NaN.  No output range may overlap an input range or the other output. */
+int amuse_seam_select(const float* poses, const float* trans, const int* choice, int n, int n_in, int F, float* poses_out, float* trans_out, void* stream);
 
 /* ------------------------------------------------------------------ motion smoothing (csrc/amuse_smooth_host.hpp, amuse_smooth.hip, k_smooth.hip; amuse_amd/smooth.py)
  * AN EXTENSION, off by default: the reference writes the decoder's rows as they come, frame by frame.  A Savitzky-Golay filter over time, on SO(3) for the
